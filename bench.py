@@ -9,7 +9,9 @@ torch.distributed.run, one rank per GPU) every rank processes its own 64-crop sh
 scaling); RCCL carries the one-off weight broadcast and the per-step gather of per-hand MANO
 parameters to rank 0.
 
-Prints ONE JSON line on rank 0 (see the field list in DESIGN.md section "Measurement").
+Prints ONE JSON line on rank 0 (see the field list in DESIGN.md section "Measurement").  A plain run sets up, warms up, times
+--steps steps and prints the line; --full adds what the headline does not need (the event-timed roofline pass, the side
+configurations, the CPU baselines).  --dump-outputs DIR writes the last timed step's outputs for output-for-output comparisons.
 """
 from __future__ import annotations
 
@@ -19,6 +21,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -41,6 +44,26 @@ def flops_per_hand(cfg: synth.HamerConfig) -> dict:
     patch = 2 * T * 3 * v.patch * v.patch * D
     kv = 2 * T * d.context_dim * d.depth * 2 * d.inner
     return {"vit": patch + v.depth * blk, "decoder_kv": kv, "total_mfma": patch + v.depth * blk + kv}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: what the timed path returned in its last step, one out_dir/<name>.npy per array (float64 stays
+    float64, everything else becomes float32), so that two builds can be compared output for output on the same seeded
+    inputs.  Every array has one row per hand; above DUMP_LIMIT_BYTES in all, the same seeded sample of rows is kept of each."""
+    arrays = {k: (v.detach().float().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = len(next(iter(arrays.values())))
+        keep = np.sort(np.random.default_rng(0).choice(n, max(1, n * DUMP_LIMIT_BYTES // (total + 8 * n)), replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        arrays["sampled_rows"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def host_threads() -> int:
@@ -209,7 +232,16 @@ def run_e2e(args, dev, dtype, yolo_weights="synthetic:2:-2.2:0", chunks_per_pass
                 step()
             el, hands_all, st, od = timed(args.steps)
         hands = hands_all // args.steps                        # hands FORWARDED per pass, all ranks (boxes without area never get there)
-        files = len(glob.glob(os.path.join(od, "*.npy")))
+        files = sorted(glob.glob(os.path.join(od, "*.npy")))
+        if getattr(args, "dump_outputs", None) and rank == 0:
+            # the hands of the last timed pass in file order, left before right: one row per hand in every array
+            rows = [(int(os.path.basename(f)[1:-4]), float(side == "right"), r) for f in files
+                    for side, r in sorted(np.load(f, allow_pickle=True).item().items()) if r is not None]
+            dump_outputs(args.dump_outputs, {"frame": np.array([n for n, _, _ in rows], np.float64),
+                                             "is_right": np.array([s for _, s, _ in rows], np.float64),
+                                             **{k: np.stack([r[k] for _, _, r in rows]) if rows else np.zeros((0,))
+                                                for k in ("betas", "theta", "cam_t")}})
+        files = len(files)
         roof = None
         if want_roofline and not multi:
             # the two MFMA kernel families of this workload, each launch timed alone: one pass of the same driver with the
@@ -267,7 +299,7 @@ E2E_WEIGHTS_4_HANDS = "synthetic:2:-2.53:0"     # objectness bias calibrated on 
 
 def side_configs(args, dev, cfg, sd, mano_cpu, eng, contract_value, ctxs):
     """The other single-GPU BASELINE configurations, timed briefly in the same process so that the driver's one command observes
-    them too.  Not the contract line: `value` above stays configs[1].  ~40 s in all."""
+    them too; --full only.  Not the contract line: `value` above stays configs[1].  ~40 s in all."""
     import types
     out = {}
     t_all = time.perf_counter()
@@ -432,7 +464,16 @@ def main():
     ap.add_argument("--det-frames", type=int, default=0, help="e2e: frames per detector pass after the first (default: infer.DET_FRAMES)")
     ap.add_argument("--hands4", action="store_true", help="e2e: detector weights calibrated to ~4 hands per frame (configs[2]'s wording) instead of ~8.6")
     ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's own steps, also what it does not need: the event-timed roofline pass, the side "
+                         "configurations (default line only) and the CPU baselines; --no-roofline / --no-side / --no-cpu-baseline "
+                         "leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32, rank 0's share; at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(relaunch_under_torchrun(args.gpus))         # children do the work; nothing here has initialised HIP
@@ -458,7 +499,7 @@ def main():
 
     if args.workload in ("e2e", "e2e-depth"):
         res = run_e2e(args, dev, dtype, yolo_weights=E2E_WEIGHTS_4_HANDS if args.hands4 else "synthetic:2:-2.2:0",
-                      chunks_per_pass=args.chunks, rank=rank, world=world, want_roofline=not args.no_roofline)
+                      chunks_per_pass=args.chunks, rank=rank, world=world, want_roofline=args.full and not args.no_roofline)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
@@ -501,6 +542,7 @@ def main():
                 eng.forward(img, c.out, workspace=c.workspace)
                 if shard._multi():        # N > 1 (or the HAMER_RCCL_AT_WORLD1=1 opt-in on one GPU): RCCL gather of the MANO parameters
                     shard.gather_mano(shard.pack_mano(c.out), dst=0)
+            return c.out
         units_per_step = world * B
     torch.cuda.synchronize()
 
@@ -529,6 +571,9 @@ def main():
     else:
         for c in ctxs:
             assert torch.isfinite(c.out["pred_vertices"]).all()
+    if args.dump_outputs and rank == 0:
+        # shard1024: the gathered [rotmats(144) | betas(10) | cam(3)] rows of the whole job; crops: this rank's forward outputs
+        dump_outputs(args.dump_outputs, {"mano_params": last} if args.workload == "shard1024" else last)
 
     res = None
     if rank == 0:
@@ -560,7 +605,7 @@ def main():
         img = img if args.workload != "shard1024" else mine[:B].contiguous()
 
     # ---- roofline of the dominant kernel (the MFMA GEMM), HIP events on the launch stream
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         nprof = min(args.steps, 5)
         with L.profile(capacity=nprof * 512) as prof:
             for _ in range(nprof):
@@ -607,9 +652,9 @@ def main():
         res["config"]["rccl_at_world1"] = "HAMER_RCCL_AT_WORLD1=1: weight broadcast and per-step MANO gather ran through RCCL on one rank"
     default_line = (world == 1 and not shard.FORCE_COLLECTIVES and args.workload == "crops" and args.dtype == "fp16" and B == 64 and not args.token_merge
                     and not args.fold_ln and args.gemm_variant < 0)
-    if rank == 0 and default_line and not args.no_side:
+    if rank == 0 and args.full and default_line and not args.no_side:
         res["side_configs"] = side_configs(args, dev, cfg, sd, mano_cpu, eng, res["value"], ctxs)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(cfg, sd, mano_cpu)
     if dist.is_initialized():
         dist.barrier()

@@ -532,3 +532,22 @@ def test_tome_schedule_parser_matches_oracle():
     for n, r in ((32, (8, -1)), (6, (8, -1)), (12, 5), (4, [7, 2]), (24, (6, 0.5)), (8, (3, 1))):
         assert parse_tome_r(n, r) == T.parse_r(n, r), (n, r)
     assert sum(parse_tome_r(32, (8, -1))) == 241
+
+
+def test_bench_dump_outputs_dtypes_and_size_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one <name>.npy per array, float32 (float64 kept); above the size limit every array keeps the
+    same seeded rows, listed in sampled_rows.npy, and the files stay within the limit."""
+    import bench
+    arrays = {"v": torch.arange(64 * 30, dtype=torch.float16).reshape(64, 30), "f": np.arange(64, dtype=np.float64)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    v, f = np.load(tmp_path / "all" / "v.npy"), np.load(tmp_path / "all" / "f.npy")
+    assert sorted(os.listdir(tmp_path / "all")) == ["f.npy", "v.npy"]
+    assert v.dtype == np.float32 and f.dtype == np.float64 and np.array_equal(v, arrays["v"].float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    rows = np.load(tmp_path / "s1" / "sampled_rows.npy").astype(np.int64)
+    assert 0 < len(rows) < 64 and np.array_equal(np.load(tmp_path / "s1" / "v.npy"), v[rows])
+    assert np.array_equal(np.load(tmp_path / "s1" / "f.npy"), f[rows])
+    assert sum(np.load(tmp_path / "s1" / n).nbytes for n in os.listdir(tmp_path / "s1")) <= 4096
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "sampled_rows.npy"))

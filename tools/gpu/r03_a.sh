@@ -7,7 +7,7 @@ step tests; timeout -k 10 900 python -m pytest tests/test_gpu_kernels.py tests/t
 step ab_resid; VARIANTS=200,201 SHAPES=proj,fc2 ROUNDS=8 REPS=5 timeout -k 10 300 python tools/bench_gemm_ab.py > $O/ab_resid_warm.log 2>&1 || exit 1
 COLD_RESID=1 VARIANTS=200,201 SHAPES=proj,fc2 ROUNDS=8 REPS=5 timeout -k 10 300 python tools/bench_gemm_ab.py > $O/ab_resid_cold.log 2>&1 || exit 1
 cat $O/ab_resid_warm.log $O/ab_resid_cold.log
-step bench; timeout -k 10 600 python bench.py > $O/bench.json.log 2>$O/bench.err || exit 1
+step bench; timeout -k 10 600 python bench.py --full > $O/bench.json.log 2>$O/bench.err || exit 1
 cat $O/bench.json.log
 step hamer_tests; timeout -k 10 900 python -m pytest tests/test_gpu_hamer.py -x -q -m gpu > $O/t_hamer.log 2>&1; rc=$?; tail -3 $O/t_hamer.log; [ $rc -le 1 ] || exit $rc
 step yolo16; timeout -k 10 300 python tools/prof_yolo.py 16 > $O/yolo_layers_16.log 2>&1 || exit 1

@@ -4,7 +4,7 @@ set -o pipefail
 O=gpurun_out/r03g; mkdir -p $O
 timeout -k 10 1100 python -m pytest tests -q -m gpu > $O/t_all.log 2>&1; rc=$?; tail -6 $O/t_all.log; [ $rc -le 1 ] || exit $rc
 for F in 16 1; do timeout -k 10 200 python tools/prof_yolo.py $F 3 > $O/yolo_layers_$F.log 2>&1 || exit 1; tail -2 $O/yolo_layers_$F.log; done
-SECONDS=0; timeout -k 10 900 python bench.py > $O/bench.json.log 2>$O/bench.err || { tail -20 $O/bench.err; exit 1; }
+SECONDS=0; timeout -k 10 900 python bench.py --full > $O/bench.json.log 2>$O/bench.err || { tail -20 $O/bench.err; exit 1; }
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r03g/bench.json.log').read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out/r03x; mkdir -p $O
-rocprofv3 --kernel-trace -d $O/trace -o e2e --output-format csv -- python3 bench.py --workload e2e --hands4 --chunks 4 --steps 3 --warmup 1 > $O/e2e.log 2>&1 || { tail $O/e2e.log; exit 1; }
+rocprofv3 --kernel-trace -d $O/trace -o e2e --output-format csv -- python3 bench.py --full --workload e2e --hands4 --chunks 4 --steps 3 --warmup 1 > $O/e2e.log 2>&1 || { tail $O/e2e.log; exit 1; }
 tail -c 400 $O/e2e.log
 F=$(find $O/trace -name '*kernel_trace.csv' | head -1)
 python3 - "$F" <<'PY'

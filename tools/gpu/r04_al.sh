@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r04al; mkdir -p $O
 timeout -k 10 300 python3 -m pytest tests/test_gpu_yolo.py -x -q -m gpu -k "maxpool" > $O/t.log 2>&1 || { tail -30 $O/t.log; exit 1; }
 tail -1 $O/t.log
-timeout -k 10 600 python3 bench.py > $O/bench.json.log 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $O/bench.json.log 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
 python3 - <<'PY'
 import json
 r=json.loads(open('gpurun_out/r04al/bench.json.log').read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 O=gpurun_out/r04ao; mkdir -p $O
-timeout -k 10 600 python3 bench.py > $O/bench.json.log 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $O/bench.json.log 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
 python3 - <<'PY'
 import json
 r=json.loads(open('gpurun_out/r04ao/bench.json.log').read().strip().splitlines()[-1])

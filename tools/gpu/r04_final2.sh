@@ -7,9 +7,9 @@ timeout -k 10 1000 python3 -m pytest tests -x -q -m gpu > $O/t.log 2>&1 || { tai
 tail -3 $O/t.log
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.build(); g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -2 $O/smoke.log
-HAMER_BENCH_REHEARSAL=1 timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --workload e2e --hands4 --chunks 2 --steps 2 --warmup 1 --no-roofline > $O/e2e_2ranks.log 2>&1 || { tail -30 $O/e2e_2ranks.log; exit 1; }
+HAMER_BENCH_REHEARSAL=1 timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --workload e2e --hands4 --chunks 2 --steps 2 --warmup 1 --no-roofline > $O/e2e_2ranks.log 2>&1 || { tail -30 $O/e2e_2ranks.log; exit 1; }
 tail -c 300 $O/e2e_2ranks.log; echo
-timeout -k 10 600 python3 bench.py > $O/bench.json.log 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+timeout -k 10 600 python3 bench.py --full > $O/bench.json.log 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
 python3 - <<'PY'
 import json
 r=json.loads(open('gpurun_out/r04final2/bench.json.log').read().strip().splitlines()[-1])

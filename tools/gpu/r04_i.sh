@@ -6,7 +6,7 @@ timeout -k 10 300 python3 tools/probes/e2e_trace.py 64 > $O/trace64.log 2>&1 || 
 tail -16 $O/trace64.log
 timeout -k 10 900 python3 -m pytest tests/test_gpu_hamer.py tests/test_gpu_yolo.py tests/test_gpu_chain.py tests/test_gpu_api.py tests/test_gpu_loaders.py -x -q -m gpu -k "batch_invariant or tome_vith_geometry or forward_decode or folder_of or estimate_from or overflow or process_batch" > $O/t.log 2>&1 || { tail -40 $O/t.log; exit 1; }
 tail -3 $O/t.log
-HAMER_BENCH_SIDE=e2e timeout -k 10 600 python3 bench.py --no-cpu-baseline > $O/bench.json.log 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+HAMER_BENCH_SIDE=e2e timeout -k 10 600 python3 bench.py --full --no-cpu-baseline > $O/bench.json.log 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
 python3 - <<'PY'
 import json
 r=json.loads(open('gpurun_out/r04i/bench.json.log').read().strip().splitlines()[-1])

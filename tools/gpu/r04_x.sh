@@ -9,7 +9,7 @@ tail -3 $O/t.log
 ABLATION_LIB=1 VARIANTS=26,36 ROUNDS=8 REPS=5 timeout -k 10 300 python3 tools/bench_gemm_ab.py > $O/ab.log 2>&1 || { tail -20 $O/ab.log; exit 1; }
 tail -11 $O/ab.log
 for i in 1 2; do
-  timeout -k 10 300 python3 bench.py --no-side --no-cpu-baseline > $O/bench$i.log 2>&1 || { tail -20 $O/bench$i.log; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --no-side --no-cpu-baseline > $O/bench$i.log 2>&1 || { tail -20 $O/bench$i.log; exit 1; }
   python3 -c "
 import json; r=json.loads(open('$O/bench$i.log').read().strip().splitlines()[-1]); print('bench', r['value'], r['ms_per_step'], r['model_mfma_frac'], r['roofline']['frac'], r['roofline']['per_epilogue'])"
 done

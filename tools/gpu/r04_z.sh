@@ -7,7 +7,7 @@ timeout -k 10 900 python3 -m pytest tests/test_gpu_chain.py tests/test_gpu_api.p
 tail -3 $O/t.log
 timeout -k 10 300 python3 tools/probes/e2e_trace.py 64 > $O/trace64.log 2>&1 || { tail -30 $O/trace64.log; exit 1; }
 tail -15 $O/trace64.log
-HAMER_BENCH_SIDE=e2e timeout -k 10 600 python3 bench.py --no-cpu-baseline > $O/bench.json.log 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
+HAMER_BENCH_SIDE=e2e timeout -k 10 600 python3 bench.py --full --no-cpu-baseline > $O/bench.json.log 2> $O/bench.err || { tail -30 $O/bench.err; exit 1; }
 python3 - <<'PY'
 import json
 r=json.loads(open('gpurun_out/r04z/bench.json.log').read().strip().splitlines()[-1])
