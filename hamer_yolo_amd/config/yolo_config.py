@@ -14,6 +14,7 @@ class Config:
     agnostic_nms = True
     device = "cuda"
     save_path = "./output"
+    precise = False       # True: the fp32 detector route (the reference's CPU branch, detector.py:110-112 half = False)
 
 
 yolo_opt = Config()

@@ -1,0 +1,208 @@
+// hm_conv2d_nhwc for HM_DTYPE_F32: the YOLOv7 convolutions in fp32 operands (the reference's CPU branch, detector.py:110-112
+// with half = False), as an implicit GEMM on the fp32-input MFMA.
+//   rows (M)    : output pixels n*Hout*Wout (NHWC, pixel stride ldy), 32 per MFMA block
+//   columns (N) : output channels, 32 per MFMA block
+//   K           : (ky, kx, ci) as the 16-bit route lays out its weights, zero padded to Kpad (% 64 == 0)
+// v_mfma_f32_32x32x2_f32 (cdna_hip_programming.md §3 'FP32-input MFMA'): f32 in, f32 accumulate, bit-for-bit a k-ordered fmaf
+// chain; 64 cycles issue and dependent latency per SIMD (MI355X_MICROARCH.md, MFMA cycle table), so the 2 x 2 independent 32x32
+// accumulators of a wave keep the pipe busy from one wave per SIMD.  157 TF/s peak = the f32 vector rate, 1/16 of the 16-bit MFMA.
+//
+// Numerics contract: every output is bias + (a sum over K in ONE fixed order that depends on k*k*Cin only): no split-K, no K groups,
+// no tile-dependent reduction.  An output's value therefore does not depend on the tile shape, the grid, the batch it rides in or
+// its place in that batch -- the fp32 route is deterministic and batch-invariant by construction.
+//
+// Tiles: 256 threads = 4 waves; a wave owns RB x CB blocks of 32x32.  K moves in stages of 32 fp32: every thread fetches its
+// float4 pieces of the next stage into registers (dwordx4 loads, in flight while the MFMAs run), then writes them to the other
+// half of a double-buffered LDS tile -- one barrier per stage.  LDS rows are 32 + 4 floats (144 B): 16-byte aligned for
+// ds_read_b128, and the 32 rows one MFMA operand read touches start in different banks.
+// Within a stage the K order is: for each group g of 8 k, lanes 0-31 (k-slot 0 of the MFMA) hold k = 8g + e and lanes 32-63
+// (k-slot 1) hold k = 8g + 4 + e, e = 0..3 the MFMA's index in the group -- one 16-byte LDS read per operand and group, the
+// same mapping on both operands.
+#include <math.h>
+#include "common.h"
+#include "hamer_hip_internal.h"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(16))) float f32x16_t;
+
+constexpr int F32_BK = 32;             // K per stage
+constexpr int F32_LDK = F32_BK + 4;    // LDS row stride in floats
+
+struct ConvF32Args {
+  const float* X;      // [N][H][Wd][ldx], already offset to the first input channel
+  const float* W;      // [Cout][Kpad]
+  const float* bias;   // [Cout]
+  float* Y;            // [M][ldy], already offset to the channel slice
+  int H, Wd, Hout, Wout, Cin, cin_log2, ksz, stride, pad, taps, ldx, ldy, Kpad, nk, M, Cout, act;
+};
+
+template <int WM, int WN, int RB, int CB>
+constexpr int conv_f32_lds_bytes() { return 2 * (WM * RB * 32 + WN * CB * 32) * F32_LDK * 4; }
+
+template <int WM, int WN, int RB, int CB>
+__global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32Args a) {
+  static_assert(WM * WN == 4, "4 waves");
+  constexpr int BM = WM * RB * 32, BN = WN * CB * 32;
+  constexpr int AL = BM / 32, BL = BN / 32;         // float4 pieces per thread and stage: 8 per tile row, 32 rows per pass
+  constexpr int STAGE = (BM + BN) * F32_LDK;         // floats per LDS buffer
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave % WM, wn = wave / WM;
+  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN;
+  const int q = tid & 7, r0 = tid >> 3;
+
+  // the A rows this thread fetches: image base and the input coordinate of tap (0, 0); a row past M gets a coordinate that
+  // every bounds test rejects, so it reads zeros and is never stored
+  const float* abase[AL];
+  int aiy[AL], aix[AL];
+#pragma unroll
+  for (int i = 0; i < AL; ++i) {
+    const int m = m0 + r0 + 32 * i;
+    abase[i] = a.X;
+    aiy[i] = -(1 << 28); aix[i] = 0;
+    if (m < a.M) {
+      const int ox = m % a.Wout, t = m / a.Wout, oy = t % a.Hout, n = t / a.Hout;
+      abase[i] = a.X + (size_t)n * a.H * a.Wd * a.ldx;
+      aiy[i] = oy * a.stride - a.pad; aix[i] = ox * a.stride - a.pad;
+    }
+  }
+  const float* brow[BL];
+  bool bok[BL];
+#pragma unroll
+  for (int i = 0; i < BL; ++i) {
+    const int co = n0 + r0 + 32 * i;
+    bok[i] = co < a.Cout;
+    brow[i] = a.W + (size_t)(bok[i] ? co : 0) * a.Kpad + 4 * q;
+  }
+
+  f32x4_t ra[AL], rb[BL];
+  auto fetch = [&](int kb) {
+    const int k0 = kb + 4 * q;                       // 4 consecutive k of one tap (Cin >= 8, a power of two)
+    const int tap = k0 >> a.cin_log2, ci = k0 & (a.Cin - 1);
+    const int ky = tap / a.ksz, kx = tap - ky * a.ksz;
+    const bool tap_ok = tap < a.taps;                // K padding: zeros
+#pragma unroll
+    for (int i = 0; i < AL; ++i) {
+      const int iy = aiy[i] + ky, ix = aix[i] + kx;
+      ra[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+      if (tap_ok && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.Wd)
+        ra[i] = *(const f32x4_t*)(abase[i] + ((size_t)iy * a.Wd + ix) * a.ldx + ci);
+    }
+#pragma unroll
+    for (int i = 0; i < BL; ++i) {
+      rb[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+      if (bok[i]) rb[i] = *(const f32x4_t*)(brow[i] + kb);
+    }
+  };
+  auto stash = [&](int buf) {
+    float* s = smem + buf * STAGE;
+#pragma unroll
+    for (int i = 0; i < AL; ++i) *(f32x4_t*)(s + (r0 + 32 * i) * F32_LDK + 4 * q) = ra[i];
+#pragma unroll
+    for (int i = 0; i < BL; ++i) *(f32x4_t*)(s + (BM + r0 + 32 * i) * F32_LDK + 4 * q) = rb[i];
+  };
+
+  f32x16_t acc[RB][CB];
+#pragma unroll
+  for (int i = 0; i < RB; ++i)
+#pragma unroll
+    for (int j = 0; j < CB; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  const int arow = (wm * RB * 32 + (lane & 31)) * F32_LDK + 4 * (lane >> 5);
+  const int brow_l = (BM + wn * CB * 32 + (lane & 31)) * F32_LDK + 4 * (lane >> 5);
+  const int nk = a.nk;
+  fetch(0);
+  stash(0);
+  __syncthreads();
+  for (int st = 0; st < nk; ++st) {
+    const int cur = st & 1;
+    if (st + 1 < nk) fetch((st + 1) * F32_BK);
+    const float* s = smem + cur * STAGE;
+#pragma unroll
+    for (int g = 0; g < F32_BK / 8; ++g) {
+      f32x4_t av[RB], bv[CB];
+#pragma unroll
+      for (int i = 0; i < RB; ++i) av[i] = *(const f32x4_t*)(s + arow + i * 32 * F32_LDK + 8 * g);
+#pragma unroll
+      for (int j = 0; j < CB; ++j) bv[j] = *(const f32x4_t*)(s + brow_l + j * 32 * F32_LDK + 8 * g);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < RB; ++i)
+#pragma unroll
+          for (int j = 0; j < CB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][e], bv[j][e], acc[i][j], 0, 0, 0);
+    }
+    if (st + 1 < nk) stash(cur ^ 1);
+    __syncthreads();
+  }
+
+  // epilogue: 32x32 C/D map -- column (output channel) = lane & 31, row (pixel) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5);
+  // 32 lanes store 128 contiguous bytes of one pixel
+#pragma unroll
+  for (int j = 0; j < CB; ++j) {
+    const int co = n0 + (wn * CB + j) * 32 + (lane & 31);
+    if (co >= a.Cout) continue;
+    const float b = a.bias[co];
+#pragma unroll
+    for (int i = 0; i < RB; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = m0 + (wm * RB + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (m >= a.M) continue;
+        float v = acc[i][j][r] + b;
+        if (a.act) v = v / (1.0f + expf(-v));        // SiLU as torch's CPU kernel writes it: x / (1 + exp(-x)), IEEE division
+        a.Y[(size_t)m * a.ldy + co] = v;
+      }
+  }
+}
+
+template <int WM, int WN, int RB, int CB>
+int launch_conv_f32(const ConvF32Args& g, hipStream_t s) {
+  constexpr int BM = WM * RB * 32, BN = WN * CB * 32, LDS = conv_f32_lds_bytes<WM, WN, RB, CB>();
+  auto kern = conv_f32_kernel<WM, WN, RB, CB>;
+  static HmLdsOnce lds_once;
+  if (const int rc = lds_once.ensure((const void*)kern, LDS, "hm_conv2d_nhwc (fp32): cannot raise the dynamic LDS limit")) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.Cout + BN - 1) / BN)), dim3(256), LDS, s, g);
+  return hm_check_launch("hm_conv2d_nhwc (fp32)");
+}
+
+}  // namespace
+
+int hm_conv2d_f32(const hm_conv_args* a, hipStream_t stream) {
+  const hm_conv_args& c = *a;
+  if (!c.X || !c.W || !c.Y || !c.bias) return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): null operand");
+  if (c.N <= 0 || c.H <= 0 || c.W_in <= 0 || c.Cin <= 0 || c.Cout <= 0) return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): empty problem");
+  if ((c.ksize != 1 && c.ksize != 3 && c.ksize != 5 && c.ksize != 7) || (c.stride != 1 && c.stride != 2))
+    return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): kernel size 1, 3, 5 or 7, stride 1 or 2");
+  if (c.act < 0 || c.act > 1 || c.resid || (c.out_f32 && c.act))
+    return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): act is 0 or 1 (SiLU), no resid / ReLU");
+  int lg = 0;
+  while ((1 << lg) < c.Cin) ++lg;
+  if ((1 << lg) != c.Cin || c.Cin < 8) return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): Cin must be a power of two >= 8");
+  const int taps = c.ksize * c.ksize;
+  if (c.Kpad % 64 != 0 || c.Kpad < taps * c.Cin) return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): Kpad must be a multiple of 64 covering k*k*Cin");
+  if (c.ldx % 4 != 0 || c.ldx < c.Cin || c.ldy < c.Cout)
+    return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): ldx % 4 == 0, ldx >= Cin, ldy >= Cout");
+  if ((((uintptr_t)c.X | (uintptr_t)c.W) & 15) || (((uintptr_t)c.Y | (uintptr_t)c.bias) & 3))
+    return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): X / W 16-byte aligned, Y / bias 4-byte aligned");
+  const int pad = c.ksize / 2;
+  const int Hout = (c.H + 2 * pad - c.ksize) / c.stride + 1, Wout = (c.W_in + 2 * pad - c.ksize) / c.stride + 1;
+  if ((size_t)c.N * Hout * Wout >= (1ull << 31) || (size_t)c.N * c.H * c.W_in >= (1ull << 31))
+    return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): more than 2^31 pixels");
+  ConvF32Args g{};
+  g.X = (const float*)c.X; g.W = (const float*)c.W; g.bias = c.bias; g.Y = (float*)c.Y;
+  g.H = c.H; g.Wd = c.W_in; g.Hout = Hout; g.Wout = Wout; g.Cin = c.Cin; g.cin_log2 = lg; g.ksz = c.ksize; g.stride = c.stride;
+  g.pad = pad; g.taps = taps; g.ldx = c.ldx; g.ldy = c.ldy; g.Kpad = c.Kpad; g.M = c.N * Hout * Wout; g.Cout = c.Cout;
+  g.nk = (taps * c.Cin + F32_BK - 1) / F32_BK;       // stages up to k*k*Cin: the zero tail of Kpad adds nothing (Conv 0: 72 -> 96, not 128)
+  g.act = c.act;
+  HmProfScope prof(HM_K_CONV, c.ksize * 10 + c.stride, g.M, g.Cout, taps * c.Cin, stream);
+  // the tile changes which threads compute an output, never its arithmetic (see the numerics contract above)
+  if (c.Cout <= 32) return launch_conv_f32<4, 1, 2, 1>(g, stream);                  // 256 x 32: Conv 0 (32), the detect heads (24)
+  if (c.Cout <= 64) return launch_conv_f32<4, 1, 2, 2>(g, stream);                  // 256 x 64
+  const long tiles = (long)((g.M + 127) / 128) * ((g.Cout + 127) / 128);
+  if (tiles < hm_device_cu_count()) return launch_conv_f32<2, 2, 1, 1>(g, stream);  // 64 x 64: the small maps of one frame
+  return launch_conv_f32<2, 2, 2, 2>(g, stream);                                    // 128 x 128
+}

@@ -4220,7 +4220,7 @@ extern "C" int hm_gemm_fp8(const hm_gemm_fp8_args* a, void* stream_) {
 }
 
 extern "C" size_t hm_conv_splitk_bytes(const hm_conv_args* a) {
-  if (!a || a->out_f32 || a->resid || !a->bias || a->ksize <= 0 || a->stride <= 0 || a->Kpad % 64 != 0) return 0;
+  if (!a || a->dtype == HM_DTYPE_F32 || a->out_f32 || a->resid || !a->bias || a->ksize <= 0 || a->stride <= 0 || a->Kpad % 64 != 0) return 0;
   const int pad = a->ksize / 2;
   KArgs k{};
   k.Hout = (a->H + 2 * pad - a->ksize) / a->stride + 1; k.Wout = (a->W_in + 2 * pad - a->ksize) / a->stride + 1;
@@ -4232,6 +4232,7 @@ extern "C" size_t hm_conv_splitk_bytes(const hm_conv_args* a) {
 extern "C" int hm_conv2d_nhwc(const hm_conv_args* a, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!a) return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc: null args");
+  if (a->dtype == HM_DTYPE_F32) return hm_conv2d_f32(a, stream);      // conv_f32.hip
   const hm_conv_args& c = *a;
   if (!c.X || !c.W || !c.Y || !c.zeros) return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc: null operand");
   if (c.N <= 0 || c.H <= 0 || c.W_in <= 0 || c.Cin <= 0 || c.Cout <= 0) return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc: empty problem");
@@ -4270,6 +4271,7 @@ extern "C" int hm_conv2d_stem_pair(const hm_conv_args* first, const hm_conv_args
   hipStream_t stream = (hipStream_t)stream_;
   if (!first || !second) return hm_set_error(HM_ERR_ARG, "hm_conv2d_stem_pair: null args");
   const hm_conv_args &a = *first, &b = *second;
+  if (a.dtype == HM_DTYPE_F32 || b.dtype == HM_DTYPE_F32) return hm_set_error(HM_ERR_ARG, "hm_conv2d_stem_pair: no fp32 form (the fp32 route runs its convolutions one by one)");
   const bool fused = hm_option(HM_OPT_CONV_STEM_PAIR) == 0 && hm_option(HM_OPT_CONV_DIRECT) != 1 &&
       a.X && a.W && a.Y && a.bias && a.zeros && b.W && b.Y && b.bias && a.dtype == b.dtype && (a.dtype == HM_DTYPE_F16 || a.dtype == HM_DTYPE_BF16) &&
       a.ksize == 3 && a.stride == 1 && a.Cin == 8 && a.ldx == 8 && a.Cout == 32 && a.ldy == 32 && a.act == 1 && !a.out_f32 && !a.resid && a.Kpad >= 96 && a.Kpad % 8 == 0 &&

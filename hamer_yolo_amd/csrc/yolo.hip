@@ -85,6 +85,8 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const uint8_t* __restric
     }
   }
   vec8 o8;
+  // u / 255 as an IEEE division (the reference: torch.from_numpy(img).float() / 255.0 divides; a reciprocal multiply differs
+  // for 126 of the 256 byte values, which the fp32 route would carry)
   o8[0] = (E)((float)v[2] / 255.0f); o8[1] = (E)((float)v[1] / 255.0f); o8[2] = (E)((float)v[0] / 255.0f);
 #pragma unroll
   for (int e = 3; e < 8; ++e) o8[e] = (E)0.0f;
@@ -245,6 +247,14 @@ int with_dtype(int dtype, F&& f) {
   return hm_set_error(HM_ERR_ARG, "bad dtype");
 }
 
+// the detector ops that also have an fp32 form (HM_DTYPE_F32, the precise route): pooling, upsampling, letterbox.  with_dtype
+// stays 16-bit only -- the RootNet ops share it and have no fp32 route
+template <class F>
+int with_dtype_or_f32(int dtype, F&& f) {
+  if (dtype == HM_DTYPE_F32) return f((float*)nullptr);
+  return with_dtype(dtype, static_cast<F&&>(f));
+}
+
 }  // namespace
 
 extern "C" int hm_maxpool_nhwc(const void* x, int ldx, void* y, int ldy, int N, int H, int W, int C, int k, int stride,
@@ -256,7 +266,7 @@ extern "C" int hm_maxpool_nhwc(const void* x, int ldx, void* y, int ldy, int N, 
   const size_t total = (size_t)N * Ho * Wo * (C / 8);
   hipStream_t s = (hipStream_t)stream_;
   HmProfScope prof(HM_K_OTHER, 1, N * Ho * Wo, C, k, s);
-  const int rc = with_dtype(dtype, [&](auto* tag) {
+  const int rc = with_dtype_or_f32(dtype, [&](auto* tag) {
     using E = std::remove_pointer_t<decltype(tag)>;
     hipLaunchKernelGGL(maxpool_kernel<E>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const E*)x, ldx, (E*)y, ldy, N, H, W, C, k, stride, pad, Ho, Wo);
     return HM_OK;
@@ -327,7 +337,7 @@ extern "C" int hm_upsample2x_nhwc(const void* x, int ldx, void* y, int ldy, int 
   const size_t total = (size_t)N * 4 * H * W * (C / 8);
   hipStream_t s = (hipStream_t)stream_;
   HmProfScope prof(HM_K_OTHER, 2, N * 4 * H * W, C, 0, s);
-  const int rc = with_dtype(dtype, [&](auto* tag) {
+  const int rc = with_dtype_or_f32(dtype, [&](auto* tag) {
     using E = std::remove_pointer_t<decltype(tag)>;
     hipLaunchKernelGGL(upsample2x_kernel<E>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const E*)x, ldx, (E*)y, ldy, N, H, W, C);
     return HM_OK;
@@ -378,7 +388,7 @@ extern "C" int hm_letterbox(const uint8_t* frame, const hm_letterbox_plan* plan,
   const int total = plan->out_h * plan->out_w;
   hipStream_t s = (hipStream_t)stream_;
   HmProfScope prof(HM_K_OTHER, 3, plan->out_h, plan->out_w, 0, s);
-  const int rc = with_dtype(dtype, [&](auto* tag) {
+  const int rc = with_dtype_or_f32(dtype, [&](auto* tag) {
     using E = std::remove_pointer_t<decltype(tag)>;
     hipLaunchKernelGGL(letterbox_kernel<E>, dim3((total + 255) / 256), dim3(256), 0, s, frame, *plan, tab_dev, (E*)x8, u8_chw, (size_t)0);
     return HM_OK;
@@ -394,7 +404,7 @@ extern "C" int hm_letterbox_batch(const uint8_t* frames, size_t frame_stride_byt
   const int total = plan->out_h * plan->out_w;
   hipStream_t s = (hipStream_t)stream_;
   HmProfScope prof(HM_K_OTHER, 3, plan->out_h, plan->out_w, nb, s);
-  const int rc = with_dtype(dtype, [&](auto* tag) {
+  const int rc = with_dtype_or_f32(dtype, [&](auto* tag) {
     using E = std::remove_pointer_t<decltype(tag)>;
     hipLaunchKernelGGL(letterbox_kernel<E>, dim3((total + 255) / 256, nb), dim3(256), 0, s, frames, *plan, tab_dev, (E*)x8, (uint8_t*)nullptr,
                        frame_stride_bytes);

@@ -39,14 +39,23 @@ def process_batch_manopara(input_folder, output_folder, k_real=None, hamer=None,
     return stats
 
 
-def main(argv=None):
-    """``python -m hamer_yolo_amd.d_infer --input <RGB_dir> --output <out_dir> --intrinsics <cam_K.txt>``."""
+def _parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="YOLOv7 -> RootNet depth + HaMeR -> MANO parameters (.npy per image)")
     ap.add_argument('--input', type=str, required=True)
     ap.add_argument('--output', type=str, required=True)
     ap.add_argument('--intrinsics', type=str, required=True, help="3x3 camera matrix txt")
     ap.add_argument('--obj', type=str, default=None, help="also reconstruct OBJ meshes into this folder")
-    args = ap.parse_args(argv)
+    ap.add_argument('--precise-detector', action='store_true',
+                    help="run YOLOv7 in fp32 (the reference's CPU branch) instead of fp16: its boxes, at about twice the detector time")
+    return ap
+
+
+def main(argv=None):
+    """``python -m hamer_yolo_amd.d_infer --input <RGB_dir> --output <out_dir> --intrinsics <cam_K.txt>``."""
+    args = _parser().parse_args(argv)
+    if args.precise_detector:
+        from .config.yolo_config import yolo_opt
+        yolo_opt.precise = True
     k_real = load_intrinsics(args.intrinsics)
     hamer = hamer_inference(hamer_opt)
     process_batch_manopara(args.input, args.output, k_real, hamer=hamer)

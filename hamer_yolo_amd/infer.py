@@ -1028,8 +1028,7 @@ def load_intrinsics(txt_path):
         return None
 
 
-def main(argv=None):
-    """CLI of infer.py:1479-1536: ``python -m hamer_yolo_amd.infer --input <RGB_dir> --output <out_dir>``."""
+def _parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="YOLOv7 -> HaMeR -> MANO parameters (.npy per image)")
     ap.add_argument('--input', type=str, required=True)
     ap.add_argument('--output', type=str, required=True)
@@ -1037,13 +1036,23 @@ def main(argv=None):
     ap.add_argument('--obj', type=str, default=None, help="also reconstruct OBJ meshes into this folder")
     ap.add_argument('--ckpt', type=str, default=None, help="hamer.ckpt path or synthetic:<seed> (default: config/hamer_config.py)")
     ap.add_argument('--yolo-weights', type=str, default=None, help="yolov7 .pt path or synthetic:<seed> (default: config/yolo_config.py)")
-    args = ap.parse_args(argv)
+    ap.add_argument('--precise-detector', action='store_true',
+                    help="run YOLOv7 in fp32 (the reference's CPU branch) instead of fp16: its boxes, at about twice the detector time")
+    return ap
+
+
+def main(argv=None):
+    """CLI of infer.py:1479-1536: ``python -m hamer_yolo_amd.infer --input <RGB_dir> --output <out_dir>``."""
+    args = _parser().parse_args(argv)
     k_real = load_intrinsics(args.intrinsics) if args.intrinsics else None
     if args.ckpt:
         hamer_opt.ckpt_path = args.ckpt
-    if args.yolo_weights:
+    if args.yolo_weights or args.precise_detector:
         from .config.yolo_config import yolo_opt
-        yolo_opt.weights = args.yolo_weights
+        if args.yolo_weights:
+            yolo_opt.weights = args.yolo_weights
+        if args.precise_detector:
+            yolo_opt.precise = True
     # under `python -m torch.distributed.run --nproc-per-node N -m hamer_yolo_amd.infer ...` every rank takes its share of
     # the folder on its own GPU (RANK / LOCAL_RANK / WORLD_SIZE from the environment); a plain launch is one process
     from . import shard

@@ -4,7 +4,8 @@
 device, save_path}`` (config/yolo_config.py:4-13); ``detect(image)`` takes an HxWx3 uint8 BGR frame and returns
 ``(pred, dets_list)``: ``pred`` a list with one (n, 6) tensor [x1, y1, x2, y2, conf, cls] in frame pixels (rounded),
 ``dets_list`` a list with one list of ``[label, [x1, y1, x2, y2]]``, label 'right' iff cls == 1
-(detector.py:144-147).  ``augment`` is ignored exactly as in the reference (TracedModel.forward drops it,
+(detector.py:144-147).  ``Detector(config, precise=True)`` (default: ``config.precise``, else False) runs the network in
+fp32 -- the reference's CPU branch (detector.py:110-112, ``half = False``) -- instead of its GPU branch's fp16.  ``augment`` is ignored exactly as in the reference (TracedModel.forward drops it,
 utils/torch_utils.py:371-374).  Everything between the frame upload and the box list is HIP
 (letterbox, 92 implicit-GEMM convolutions, pooling, decode, NMS, scale_coords).
 """
@@ -69,7 +70,9 @@ class _Model:
 
 
 class Detector():
-    def __init__(self, config):
+    def __init__(self, config, precise=None):
+        """precise: None reads ``getattr(config, "precise", False)``; True runs the fp32 route (YoloEngine dtype torch.float32:
+        the reference's CPU-branch arithmetic, boxes equal to its fp32 detector's), False the default fp16 route."""
         weights, imgsz, self.device = config.weights, config.imgsz, config.device
         self.device = torch.device(self.device if torch.cuda.is_available() else 'cpu')
         if self.device.type != 'cuda':
@@ -77,7 +80,9 @@ class Detector():
         sd, nc, names = attempt_load(weights)
         stride = 32
         self.imgsz = int(np.ceil(imgsz / stride) * stride)               # check_img_size, general.py:126-131
-        self.engine = YoloEngine(sd, nc=nc, device=self.device, new_shape=self.imgsz, stride=stride, names=names)
+        self.precise = bool(getattr(config, "precise", False) if precise is None else precise)
+        self.engine = YoloEngine(sd, nc=nc, device=self.device, dtype=torch.float32 if self.precise else torch.float16,
+                                 new_shape=self.imgsz, stride=stride, names=names)
         self.model = _Model(self.engine)
         self.opt = config
         self.detect_savepath = config.save_path

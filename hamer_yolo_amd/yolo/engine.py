@@ -1,7 +1,9 @@
 """YoloEngine: device-resident fused YOLOv7 weights + a planned op list per input size.
 
 Load time (host, once): BN / RepConv / implicit folding (fuse.py), weights re-laid out as
-[Cout][ky][kx][Cin] 16-bit rows padded to a multiple of 64 (the implicit-GEMM K axis).
+[Cout][ky][kx][Cin] rows padded to a multiple of 64 (the implicit-GEMM K axis), in the engine's dtype: 16-bit (the
+reference's GPU branch) or fp32 (``dtype=torch.float32``, the precise route: the reference's CPU branch, no split-K,
+no fused stem, deterministic and batch-invariant convolutions -- conv_f32.hip).
 Plan time (host, once per letterboxed size): every tensor gets a home in an NHWC arena; a tensor
 that feeds a Concat lives directly in a channel slice of the concat's buffer, so Concat costs
 nothing (reference: Model.forward_once, yolo.py:609-639, copies on every torch.cat).
@@ -50,7 +52,11 @@ class YoloEngine:
         self.lib = L.load()
         self.device = torch.device(device)
         self.dtype = dtype
-        self.dt = L.HM_DTYPE_BF16 if dtype == torch.bfloat16 else L.HM_DTYPE_F16
+        dts = {torch.float16: L.HM_DTYPE_F16, torch.bfloat16: L.HM_DTYPE_BF16, torch.float32: L.HM_DTYPE_F32}
+        if dtype not in dts:
+            raise ValueError(f"YoloEngine dtype must be torch.float16, torch.bfloat16 or torch.float32, not {dtype}")
+        self.dt = dts[dtype]
+        self.esz = torch.empty((), dtype=dtype).element_size()   # bytes per activation / weight element
         self.nc, self.no = nc, nc + 5
         self.new_shape, self.stride = new_shape, stride
         self.layers = arch.yolov7_layers()
@@ -70,9 +76,10 @@ class YoloEngine:
         self.names = list(names) if names is not None else [str(i) for i in range(nc)]   # Model.names of the checkpoint
         self._plans: Dict[Tuple[int, int], dict] = {}
         self._stacked: Dict[Tuple[str, str], Tuple[torch.Tensor, torch.Tensor]] = {}   # stacked weights of fused 1x1 pairs
+        f32 = dtype == torch.float32                         # the fp32 route has neither a split-K nor a fused stem form
         self.fuse_pairs = True        # E-ELAN cv1 / cv2 as one launch (round 3); False: one launch per convolution, as the reference's graph
-        self.split_k = True           # give the library split-K scratch for the small maps of the neck (round 3)
-        self.fuse_stem = True         # Conv 0 + Conv 1 as one launch, the 32-channel full-size map never written (round 4); False: two launches
+        self.split_k = not f32        # give the library split-K scratch for the small maps of the neck (round 3)
+        self.fuse_stem = not f32      # Conv 0 + Conv 1 as one launch, the 32-channel full-size map never written (round 4); False: two launches
 
     # ------------------------------------------------------------------ planning
     def _plan(self, H: int, W: int, nb: int = 1) -> dict:
@@ -132,10 +139,10 @@ class YoloEngine:
         offs, total = {}, 0
         for b, n in sizes.items():
             offs[b] = total
-            total += (n * 2 + 255) // 256 * 256
+            total += (n * self.esz + 255) // 256 * 256
         arena = torch.zeros(total, dtype=torch.uint8, device=self.device)
         base = arena.data_ptr()
-        esz = 2
+        esz = self.esz
 
         def addr(buf, ch_off=0):
             return base + offs[buf] + ch_off * esz
@@ -270,7 +277,9 @@ class YoloEngine:
         self._plans[key] = plan
         return plan
 
-    PLAN_BYTES_BUDGET = 32 << 30      # arenas of cached plans (a 48-frame 1080p plan is ~7 GB; the folder drivers' last pass may be any size)
+    # arenas of cached plans (a 48-frame 1080p plan is ~7 GB in 16 bits, ~14 GB on the fp32 route: the two plans that always stay
+    # fit either way; the folder drivers' last pass may be any size)
+    PLAN_BYTES_BUDGET = 32 << 30
 
     def _evict_plans(self) -> None:
         """Before a NEW plan is built: drop the least recently used plans while the cached arenas exceed the budget (the two
@@ -291,7 +300,7 @@ class YoloEngine:
         b, o, ld = p["home"][i]
         h, w = p["hw"][i]
         start = p["offs"][b]
-        buf = p["arena"][start:start + h * w * ld * 2].view(self.dtype).reshape(h, w, ld)
+        buf = p["arena"][start:start + h * w * ld * self.esz].view(self.dtype).reshape(h, w, ld)
         return buf[:, :, o:o + p["ch"][i]].permute(2, 0, 1).float().cpu()
 
     # ------------------------------------------------------------------ run
@@ -299,7 +308,7 @@ class YoloEngine:
         H, W, _ = frame.shape
         p = plan or self._plan(H, W)
         lp = p["lp"]
-        L.check(self.lib.hm_letterbox(frame.data_ptr(), C.byref(lp), p["tab"].data_ptr(), p["img_ptr"] + index * lp.out_h * lp.out_w * 16,
+        L.check(self.lib.hm_letterbox(frame.data_ptr(), C.byref(lp), p["tab"].data_ptr(), p["img_ptr"] + index * lp.out_h * lp.out_w * 8 * self.esz,
                                       self.dt, p["u8"].data_ptr() if want_u8 else None, L.current_stream()), "hm_letterbox")
         return p
 

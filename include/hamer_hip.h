@@ -24,9 +24,10 @@
 extern "C" {
 #endif
 
-#define HM_VERSION 401   /* 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
+#define HM_VERSION 402   /* 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
 
-enum { HM_DTYPE_BF16 = 0, HM_DTYPE_F16 = 1 };
+enum { HM_DTYPE_BF16 = 0, HM_DTYPE_F16 = 1,
+       HM_DTYPE_F32 = 2 /* the YOLOv7 detector path only (same value as HM_OUT_F32): see its section below */ };
 
 /* GEMM epilogues */
 enum {
@@ -331,11 +332,21 @@ int hm_hamer_forward(const hm_hamer_weights* w, const float* img, int B, const h
 /* ---------------------------------------------------------------- YOLOv7 detector path
  * Activations are NHWC 16-bit tensors addressed as (base pointer, pixel stride in elements): a
  * producer can write straight into a channel slice of a concat buffer (Concat, common.py:60-66,
- * costs nothing), a consumer can read a slice the same way. */
+ * costs nothing), a consumer can read a slice the same way.
+ *
+ * HM_DTYPE_F32 (round 5): the reference's CPU branch (detector.py:110-112 with half = False) -- activations, the image and the
+ * weights in fp32.  Taken by hm_conv2d_nhwc (act 0 or 1, no resid), hm_maxpool_nhwc, hm_upsample2x_nhwc, hm_letterbox,
+ * hm_letterbox_batch (x8 in fp32: 8 channels, 3 real, u / 255 correctly rounded as torch divides) and the conv / maxpool /
+ * upsample ops of hm_yolo_run; the strides (ldx, ldy, ldr) stay in elements.  Every other entry point, hm_conv2d_stem_pair
+ * (HM_OP_CONV_PAIR) among them, rejects it with HM_ERR_ARG.  The convolution (conv_f32.hip) runs on the fp32-input MFMA: each
+ * output is bias + a sum over K in one order fixed by k*k*Cin alone -- no split-K (hm_conv_splitk_bytes returns 0, splitk_ws is
+ * ignored), no K groups, none of the HM_OPT_CONV_* tuning options -- so results are deterministic and batch-invariant, and a
+ * convolution is within ~1e-6 * sum|x * w| of exact (the fp32 MFMA is a k-ordered fmaf chain); pooling, upsampling and the
+ * letterbox are exact. */
 typedef struct hm_conv_args {
-  const void* X;      /* [N][H][W_in][ldx] 16-bit, pointer already offset to the first input channel   */
-  const void* W;      /* [Cout][Kpad] 16-bit, K order (ky, kx, ci), zero padded to Kpad (% 64 == 0)   */
-  void* Y;            /* [N][Hout][Wout][ldy] 16-bit (or f32 when out_f32), offset to the channel slice */
+  const void* X;      /* [N][H][W_in][ldx] 16-bit (fp32 with HM_DTYPE_F32), pointer already offset to the first input channel */
+  const void* W;      /* [Cout][Kpad] 16-bit (fp32 with HM_DTYPE_F32), K order (ky, kx, ci), zero padded to Kpad (% 64 == 0) */
+  void* Y;            /* [N][Hout][Wout][ldy] 16-bit (or f32 when out_f32 or HM_DTYPE_F32), offset to the channel slice */
   const float* bias;  /* [Cout]                                                                        */
   const void* zeros;  /* >= 16 zero bytes on the device: source of padding taps                        */
   int N, H, W_in, Cin, Cout, ksize, stride, ldx, ldy, Kpad;
@@ -353,9 +364,11 @@ typedef struct hm_conv_args {
 } hm_conv_args;
 
 /* Conv2d(k in {1,3,5,7}, stride in {1,2}, pad k/2) + bias (+ SiLU / ReLU / residual add + ReLU) as an implicit GEMM on MFMA.
- * Cin must be a power of two >= 8 (the 3-channel image is stored with 8 channels). */
+ * Cin must be a power of two >= 8 (the 3-channel image is stored with 8 channels).
+ * HM_DTYPE_F32: act 0 or 1, no resid; X / W 16-byte aligned, ldx % 4 == 0; zeros and splitk_ws are not used; the HM_OPT_CONV_*
+ * options do not apply (one kernel, its tile chosen by Cout and the tile count, with no effect on the result). */
 int hm_conv2d_nhwc(const hm_conv_args* args, void* stream);
-/* bytes of splitk_ws this convolution would use (0: it is never split) */
+/* bytes of splitk_ws this convolution would use (0: it is never split -- always for HM_DTYPE_F32) */
 size_t hm_conv_splitk_bytes(const hm_conv_args* args);
 /* Two consecutive convolutions of which the second is the ONLY reader of the first's output: Conv 0 and Conv 1 of yolov7.yaml
  * (yolo.py Model.forward_once walks them one after the other; 3 -> 32, k3 s1, then 32 -> 64, k3 s2, both SiLU).  Where the fused
