@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from .infer import *  # noqa: F401,F403
-from .infer import (FRAMES_PER_STEP, _default_models, _detection_list, _imread_bgr, _list_images, _record_from, hamer_inference,  # noqa: F401
+from .infer import (FRAMES_PER_STEP, _default_models, _detection_list, _imread_bgr, _list_images, _record_from, _render_args, hamer_inference,  # noqa: F401
                     hamer_opt, hand_record, iter_folder_results, load_intrinsics, reconstruct_and_save_obj_with_wrapper)
 from .rootnet.Model_RGB import get_model  # noqa: F401
 
@@ -47,6 +47,7 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument('--obj', type=str, default=None, help="also reconstruct OBJ meshes into this folder")
     ap.add_argument('--precise-detector', action='store_true',
                     help="run YOLOv7 in fp32 (the reference's CPU branch) instead of fp16: its boxes, at about twice the detector time")
+    _render_args(ap)
     return ap
 
 
@@ -61,6 +62,11 @@ def main(argv=None):
     process_batch_manopara(args.input, args.output, k_real, hamer=hamer)
     if args.obj:
         reconstruct_and_save_obj_with_wrapper(args.output, args.obj, hamer)
+    if args.render:
+        from .infer import _rank_world
+        from .render import render_folder
+        rank, world = _rank_world(None, None)
+        render_folder(args.input, args.output, args.render, hamer, k_real, style=args.render_style, rank=rank, world=world)
 
 
 if __name__ == '__main__':

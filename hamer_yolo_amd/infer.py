@@ -87,8 +87,9 @@ class hamer_inference():
         self.mano = self.model.mano
 
     def get_mesh_renderer(self):
-        """infer.py:148-152 builds pyrender's MeshRenderer; rendering is out of scope, the MANO model
-        (with ``.faces``) is what reconstruct_and_save_obj_with_wrapper needs."""
+        """infer.py:148-152 builds pyrender's MeshRenderer; no pyrender object is built here (returns None): the overlays are
+        drawn by render.render_folder / ``--render`` on the GPU.  The MANO model (with ``.faces``) is what
+        reconstruct_and_save_obj_with_wrapper needs."""
         self.mano = self.model.mano
         return None
 
@@ -978,29 +979,36 @@ def write_obj(path: str, vertices: np.ndarray, faces: np.ndarray):
             f.write(f"f {t[0]} {t[1]} {t[2]}\n")
 
 
+def mano_hand_vertices(hamer_instance, hands: List[Dict]) -> torch.Tensor:
+    """MANO vertices (B, V, 3) fp32 on the device for the hand records ``hands`` (the dicts of a ``.npy``): axis-angle ->
+    rotation matrices per hand, then ONE MANO forward for all hands.  Shared by reconstruct_and_save_obj_with_wrapper and
+    render.render_folder; a hand's vertices do not depend on the batch (the MANO kernel gives every hand its own workgroups)."""
+    device = hamer_instance.device
+    mpd = {k: v.to(device) for k, v in hamer_instance.mano.params.items() if v.dtype == torch.float32}
+    sixes, betas = [], []
+    for hd in hands:
+        betas.append(torch.tensor(np.atleast_2d(hd['betas']), dtype=torch.float32, device=device))
+        go = axis_angle_to_rotation_matrix_torch(torch.tensor(np.atleast_2d(hd['pose_global']), dtype=torch.float32, device=device))
+        hp = axis_angle_to_rotation_matrix_torch(torch.tensor(hd['pose_hand'].reshape(-1, 3), dtype=torch.float32, device=device))
+        R = torch.cat([go, hp], 0)                                   # (16,3,3)
+        sixes.append(torch.cat([R[:, :, 0], R[:, :, 1]], dim=1).reshape(1, 96))   # rot6d of an exact rotation is itself
+    cam = torch.tensor([[1.0, 0.0, 0.0]], device=device).expand(len(hands), 3).contiguous()
+    return ops.mano_forward(mpd, torch.cat(sixes), torch.cat(betas), cam)["verts"]
+
+
 def reconstruct_and_save_obj_with_wrapper(npy_folder, output_obj_folder, hamer_instance):
     """infer.py:1321-1436: .npy (axis-angle) -> rotation matrices -> MANO -> 778-vertex mesh; left hands are
     mirrored (x := -x, face winding flipped); += cam_t; one OBJ per image."""
-    device = hamer_instance.device
     os.makedirs(output_obj_folder, exist_ok=True)
     mano = hamer_instance.mano
-    mpd = {k: v.to(device) for k, v in mano.params.items() if v.dtype == torch.float32}
     for npy_path in sorted(glob.glob(os.path.join(npy_folder, '*.npy'))):
         file_name = os.path.splitext(os.path.basename(npy_path))[0]
         try:
             data = np.load(npy_path, allow_pickle=True).item()
+            hands = [data[t] for t in ['right', 'left'] if data[t] is not None]
             verts_all, faces_all, off = [], [], 0
-            for hand_type in ['right', 'left']:
-                hd = data[hand_type]
-                if hd is None:
-                    continue
-                betas = torch.tensor(np.atleast_2d(hd['betas']), dtype=torch.float32, device=device)
-                go = axis_angle_to_rotation_matrix_torch(torch.tensor(np.atleast_2d(hd['pose_global']), dtype=torch.float32, device=device))
-                hp = axis_angle_to_rotation_matrix_torch(torch.tensor(hd['pose_hand'].reshape(-1, 3), dtype=torch.float32, device=device))
-                R = torch.cat([go, hp], 0)                                   # (16,3,3)
-                six = torch.cat([R[:, :, 0], R[:, :, 1]], dim=1).reshape(1, 96)   # rot6d of an exact rotation is itself
-                o = ops.mano_forward(mpd, six, betas, torch.tensor([[1.0, 0.0, 0.0]], device=device))
-                vertices = o["verts"][0].cpu().numpy()
+            mano_verts = mano_hand_vertices(hamer_instance, hands).cpu().numpy() if hands else []
+            for hd, vertices in zip(hands, mano_verts):
                 faces = mano.faces.astype(np.int32)
                 if not hd['is_right']:
                     vertices[:, 0] = -vertices[:, 0]
@@ -1038,7 +1046,15 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument('--yolo-weights', type=str, default=None, help="yolov7 .pt path or synthetic:<seed> (default: config/yolo_config.py)")
     ap.add_argument('--precise-detector', action='store_true',
                     help="run YOLOv7 in fp32 (the reference's CPU branch) instead of fp16: its boxes, at about twice the detector time")
+    _render_args(ap)
     return ap
+
+
+def _render_args(ap: argparse.ArgumentParser) -> None:
+    ap.add_argument('--render', type=str, default=None, metavar="DIR",
+                    help="after the records are written, draw the hand meshes onto their frames into DIR (<name>.jpg)")
+    ap.add_argument('--render-style', type=str, default="flat", choices=["flat", "shaded"],
+                    help="flat: the reference's 0.6 green blend (reconstruct.py); shaded: opaque normal-shaded meshes")
 
 
 def main(argv=None):
@@ -1069,6 +1085,10 @@ def main(argv=None):
         dist.barrier()
     if args.obj and rank == 0:
         reconstruct_and_save_obj_with_wrapper(args.output, args.obj, hamer)
+    if args.render:
+        from .render import render_folder
+        n = render_folder(args.input, args.output, args.render, hamer, k_real, style=args.render_style, rank=rank, world=world)
+        print(f"{n} overlays written to {args.render}" + (f" (rank {rank})" if world > 1 else ""))
 
 
 if __name__ == '__main__':

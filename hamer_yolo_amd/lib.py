@@ -32,7 +32,7 @@ EXPORTS = [
     "hm_conv2d_nhwc", "hm_conv2d_stem_pair", "hm_maxpool_nhwc", "hm_upsample2x_nhwc", "hm_letterbox_plan_make", "hm_letterbox_tables",
     "hm_letterbox", "hm_yolo_decode", "hm_nms_workspace_bytes", "hm_yolo_nms", "hm_yolo_run", "hm_gemm_set_variant", "hm_gemm_set_group_m", "hm_ln_finalize", "hm_layernorm_accum", "hm_gemm_fp8", "hm_layernorm_mx8", "hm_vit_attention_mx8", "hm_nchw3_to_nhwc8", "hm_gap_linear",
     "hm_tome_index_bytes", "hm_tome_attention", "hm_tome_merge", "hm_set_option", "hm_get_option", "hm_tome_merge_metric", "hm_conv_splitk_bytes", "hm_yolo_decode_batch", "hm_letterbox_batch",
-    "hm_option_count", "hm_gemm_px_grid", "hm_absmax16",
+    "hm_option_count", "hm_gemm_px_grid", "hm_absmax16", "hm_mesh_overlay_workspace_bytes", "hm_mesh_overlay",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -107,6 +107,13 @@ class YoloOp(C.Structure):
 class LetterboxPlan(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("src_h", "src_w", "new_w", "new_h", "top", "left", "out_h", "out_w")] + \
                [("gain", C.c_float), ("pad_x", C.c_float), ("pad_y", C.c_float)]
+
+
+HM_STYLE_FLAT, HM_STYLE_SHADED = 0, 1      # hm_mesh_overlay styles
+
+
+class Mesh(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("frame", "v0", "nv", "f0", "nf")] + [("color_bgr", C.c_uint8 * 3), ("reserved", C.c_uint8)]
 
 
 class ProfRecord(C.Structure):
@@ -192,6 +199,9 @@ def load() -> C.CDLL:
     lib.hm_get_option.argtypes = [i]
     lib.hm_option_count.argtypes = []
     lib.hm_gemm_px_grid.argtypes = [i, i]
+    lib.hm_mesh_overlay_workspace_bytes.argtypes = [i, i, i, i, i]
+    lib.hm_mesh_overlay_workspace_bytes.restype = C.c_size_t
+    lib.hm_mesh_overlay.argtypes = [vp, i, i, i, vp, vp, i, vp, i, C.POINTER(Mesh), i, i, d, vp, vp, C.c_size_t, vp]
     lib.hm_prof_begin.argtypes = [i]
     lib.hm_prof_collect.argtypes = [C.POINTER(ProfRecord), i]
     lib.hm_prof_end.argtypes = []
@@ -199,7 +209,8 @@ def load() -> C.CDLL:
         if not hasattr(lib, name):
             raise HipLibraryError(f"{LIB_PATH} does not export {name}")
         fn = getattr(lib, name)
-        if name not in ("hm_version", "hm_last_error_string", "hm_hamer_workspace_bytes", "hm_nms_workspace_bytes", "hm_tome_index_bytes", "hm_conv_splitk_bytes"):
+        if name not in ("hm_version", "hm_last_error_string", "hm_hamer_workspace_bytes", "hm_nms_workspace_bytes", "hm_tome_index_bytes", "hm_conv_splitk_bytes",
+                        "hm_mesh_overlay_workspace_bytes"):
             fn.restype = i
     if lib.hm_version() != HM_VERSION:
         raise HipLibraryError(f"{LIB_PATH} reports HM_VERSION {lib.hm_version()}, this binding is written for {HM_VERSION}: "

@@ -1,0 +1,238 @@
+"""Hand meshes drawn onto their frames on the GPU (reference: hamer/reconstruct.py project_and_draw / main, :50-178; the
+pyrender look of infer.py get_mesh_renderer / image_fusion and utils/mesh_renderer.py approximated by the ``shaded``
+style).  The drawing rule is stated in include/hamer_hip.h (hm_mesh_overlay) and DESIGN.md section 8.
+
+* ``overlay_frames``: device frames + meshes -> device frames, one hm_mesh_overlay call.
+* ``render_folder``: the ``.npy`` records of a folder job -> one overlay image per frame with hands, a batched MANO forward per
+  pass of equally sized frames, PIL encoding on a small thread pool."""
+from __future__ import annotations
+
+import glob
+import os
+from concurrent.futures import ThreadPoolExecutor
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import lib as L
+
+COLOR_RIGHT = (0, 255, 0)          # BGR: reconstruct.py's default green
+COLOR_LEFT = (0, 255, 0)
+STYLES = {"flat": L.HM_STYLE_FLAT, "shaded": L.HM_STYLE_SHADED}
+FRAMES_PER_PASS = 16               # frames per overlay call of the folder paths: host memory and the key buffer scale with it
+PASSES_IN_FLIGHT = 2               # passes whose encoded files may still be pending before the next pass is decoded
+
+_ws: Dict[tuple, list] = {}        # (device index, stream) -> [workspace tensor, bytes known to hold 0xFF from offset 0]
+
+
+def _workspace(device: torch.device, stream: int, need: int, key_bytes: int) -> torch.Tensor:
+    """One growing workspace per (device, stream): calls on one stream are ordered, so they may share it; calls on two streams
+    never do.  Its first ``key_bytes`` bytes hold 0xFF on return (the key buffer's contract).  ``release_workspaces`` frees
+    them."""
+    key = (device.index if device.index is not None else torch.cuda.current_device(), stream)
+    ent = _ws.get(key)
+    if ent is None or ent[0].numel() < need:
+        _ws.pop(key, None)
+        ent = _ws[key] = [torch.full((need,), 255, dtype=torch.uint8, device=device), need]
+    if ent[1] < key_bytes:                       # bytes past the last call's keys held its face records
+        ent[0][ent[1]:key_bytes].fill_(255)
+    ent[1] = key_bytes                           # the call keeps its keys clean and writes records after them
+    return ent[0]
+
+
+def release_workspaces() -> None:
+    """Drop the cached overlay workspaces (N*H*W*8 bytes of keys each, ~265 MB for 16 frames of 1080p).  Safe with work
+    still enqueued: each workspace was allocated on the stream that uses it, and the caching allocator hands a freed block
+    out again only in that stream's order."""
+    _ws.clear()
+
+
+def _mesh_color(m: dict, color_right, color_left):
+    if m.get("color") is not None:
+        return tuple(int(c) for c in m["color"])
+    return tuple(color_right if m.get("is_right", True) else color_left)
+
+
+def overlay_frames(frames_dev: torch.Tensor, K, meshes: Sequence[dict], style: str = "flat", alpha: float = 0.6,
+                   color_right=COLOR_RIGHT, color_left=COLOR_LEFT, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """frames_dev (N,H,W,3) uint8 BGR on the GPU; K (3,3) for every frame or (N,3,3); meshes: dicts with ``frame``,
+    ``vertices`` (V,3) camera-frame, ``faces`` (F,3) 0-based into the mesh's own vertices, and ``is_right`` or ``color``
+    (B, G, R).  Returns a new (N,H,W,3) uint8 device tensor (or fills ``out``).  Enqueued on the current stream."""
+    if style not in STYLES:
+        raise ValueError(f"style must be one of {sorted(STYLES)}, got {style!r}")
+    if not (frames_dev.is_cuda and frames_dev.dtype == torch.uint8 and frames_dev.dim() == 4 and frames_dev.shape[3] == 3):
+        raise ValueError("frames_dev must be a (N,H,W,3) uint8 GPU tensor")
+    frames_dev = frames_dev.contiguous()
+    dev = frames_dev.device
+    N, H, W, _ = frames_dev.shape
+    Kt = torch.as_tensor(np.asarray(K.cpu() if torch.is_tensor(K) else K, dtype=np.float64))
+    Kt = Kt.expand(N, 3, 3) if Kt.dim() == 2 else Kt
+    if tuple(Kt.shape) != (N, 3, 3):
+        raise ValueError(f"K must be (3,3) or ({N},3,3), got {tuple(Kt.shape)}")
+    Kd = Kt.contiguous().to(dev)
+    table = (L.Mesh * max(len(meshes), 1))()
+    verts, faces, v0, f0 = [], [], 0, 0
+    checked = {}                                 # (id of a faces object, nv) -> its range is known good (one sync per object)
+    for i, m in enumerate(meshes):
+        v = torch.as_tensor(m["vertices"]).to(dev, torch.float64).reshape(-1, 3)
+        f = torch.as_tensor(m["faces"]).to(dev, torch.int32).reshape(-1, 3)
+        ck = (id(m["faces"]), v.shape[0])
+        if f.numel() and ck not in checked:
+            if v.shape[0] == 0 or int(f.min()) < 0 or int(f.max()) >= v.shape[0]:
+                raise ValueError(f"mesh {i}: face corner outside its {v.shape[0]} vertices")
+            checked[ck] = m["faces"]
+        if not 0 <= int(m["frame"]) < N:
+            raise ValueError(f"mesh {i}: frame {m['frame']} outside the batch of {N}")
+        t = table[i]
+        t.frame, t.v0, t.nv, t.f0, t.nf = int(m["frame"]), v0, v.shape[0], f0, f.shape[0]
+        t.color_bgr[:] = _mesh_color(m, color_right, color_left)
+        verts.append(v); faces.append(f); v0 += v.shape[0]; f0 += f.shape[0]
+    vd = torch.cat(verts).contiguous() if verts else torch.zeros(0, 3, dtype=torch.float64, device=dev)
+    fd = torch.cat(faces).contiguous() if faces else torch.zeros(0, 3, dtype=torch.int32, device=dev)
+    if out is None:
+        out = torch.empty_like(frames_dev)
+    elif not (out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == tuple(frames_dev.shape) and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(frames_dev.shape)} on {dev}")
+    lib = L.load()
+    need = lib.hm_mesh_overlay_workspace_bytes(N, H, W, len(meshes), f0)
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, L.current_stream(), need, N * H * W * 8)
+        L.check(lib.hm_mesh_overlay(L.ptr(frames_dev), N, H, W, L.ptr(Kd), L.ptr(vd) if v0 else None, v0,
+                                    L.ptr(fd) if f0 else None, f0, table, len(meshes), STYLES[style], float(alpha), L.ptr(out),
+                                    L.ptr(ws), ws.numel(), L.current_stream()), "hm_mesh_overlay")
+    return out
+
+
+def default_camera(H: int, W: int, cfg) -> np.ndarray:
+    """The camera the records were made with when no intrinsics are given (infer.py _estimate, no-intrinsics branch):
+    fx = fy = EXTRA.FOCAL_LENGTH / MODEL.IMAGE_SIZE * max(H, W), principal point at the frame centre."""
+    f = float(cfg.EXTRA.FOCAL_LENGTH) / float(cfg.MODEL.IMAGE_SIZE) * max(H, W)
+    return np.array([[f, 0.0, W / 2.0], [0.0, f, H / 2.0], [0.0, 0.0, 1.0]], np.float64)
+
+
+def camera_vertices(hamer, hands: List[dict]) -> torch.Tensor:
+    """(B, V, 3) fp32 camera-frame vertices of the hand records: MANO (one forward), x := -x for left hands, += cam_t --
+    the vertices of the OBJ reconstruct_and_save_obj_with_wrapper writes, before its ``%.8f`` text."""
+    from .infer import mano_hand_vertices
+    dev = hamer.device
+    verts = mano_hand_vertices(hamer, hands)
+    sign = torch.tensor([[1.0, 1.0, 1.0] if h["is_right"] else [-1.0, 1.0, 1.0] for h in hands], device=dev)
+    cam_t = torch.tensor(np.stack([np.asarray(h["cam_t"], np.float32).reshape(3) for h in hands]), device=dev)
+    return verts * sign[:, None, :] + cam_t[:, None, :]
+
+
+def _encode_threads() -> int:
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    return max(1, min(16, n))
+
+
+def _save(path: str, img_bgr: np.ndarray) -> None:
+    from PIL import Image
+    Image.fromarray(np.ascontiguousarray(img_bgr[:, :, ::-1])).save(path)
+
+
+def frame_size(path: str) -> Optional[tuple]:
+    """(H, W) of an image from its header (PIL opens lazily: no pixel is decoded); None when unreadable."""
+    try:
+        from PIL import Image
+        with Image.open(path) as im:
+            w, h = im.size
+        return h, w
+    except Exception:
+        return None
+
+
+def size_passes(sizes: Sequence[Optional[tuple]], per_pass: int) -> List[tuple]:
+    """[(size, [indices])] -- the items grouped by frame size (first-seen order, input order inside a group) and cut into
+    passes of at most ``per_pass``; items of size None are left out."""
+    groups: Dict[tuple, List[int]] = {}
+    for i, hw in enumerate(sizes):
+        if hw is not None:
+            groups.setdefault(tuple(hw), []).append(i)
+    return [(hw, idx[s:s + per_pass]) for hw, idx in groups.items() for s in range(0, len(idx), per_pass)]
+
+
+class PassWriter:
+    """Encodes a pass's images on ``pool`` and keeps at most ``in_flight`` passes pending: submitting one more first waits
+    for the oldest, so host memory holds a bounded number of decoded outputs however long the folder."""
+
+    def __init__(self, pool, in_flight: int = PASSES_IN_FLIGHT):
+        self.pool, self.in_flight, self.pending, self.written = pool, in_flight, [], 0
+
+    def _finish_oldest(self):
+        for f in self.pending.pop(0):
+            f.result()
+            self.written += 1
+
+    def submit(self, items) -> None:
+        """items: (path, (H,W,3) uint8 BGR)."""
+        while len(self.pending) >= self.in_flight:
+            self._finish_oldest()
+        self.pending.append([self.pool.submit(_save, p, img) for p, img in items])
+
+    def close(self) -> int:
+        while self.pending:
+            self._finish_oldest()
+        return self.written
+
+
+def decode_pass(pool, paths: Sequence[str], hw: tuple):
+    """The frames of one pass as one (n, H, W, 3) uint8 array (decoded on ``pool``) and the indices that decoded to (H, W)."""
+    from .infer import _imread_bgr
+    frames = list(pool.map(_imread_bgr, paths))
+    ok = [i for i, fr in enumerate(frames) if fr is not None and fr.shape[:2] == tuple(hw)]
+    for i in sorted(set(range(len(paths))) - set(ok)):
+        print(f"Skipping {paths[i]}: image load failed")
+    return (np.stack([frames[i] for i in ok]) if ok else None), ok
+
+
+def render_folder(image_folder, npy_folder, out_folder, hamer, k_real=None, style: str = "flat", rank: int = 0, world: int = 1,
+                  ext: str = ".jpg", frames_per_pass: int = FRAMES_PER_PASS) -> int:
+    """Draw the hands of every ``<name>.npy`` record of ``npy_folder`` onto ``image_folder``'s ``<name>.*`` frame and write
+    ``out_folder/<name><ext>`` (``.jpg`` as the reference; any extension PIL writes).  Frames are grouped by the size their
+    headers give and drawn in passes of ``frames_per_pass``: per pass the frames are decoded, ONE MANO forward runs for all its
+    hands (the formulation of reconstruct_and_save_obj_with_wrapper), one overlay call, one copy back, and the encodes go to
+    a ``PassWriter`` -- host memory stays bounded by a few passes whatever the folder's length.  ``k_real`` None: the camera
+    the records were made with (``default_camera``).  ``rank`` / ``world``: this process draws ``shard_paths(records, rank,
+    world)``.  Returns the number of images written; the overlay workspaces are released at the end."""
+    from .infer import _list_images, shard_paths
+    os.makedirs(out_folder, exist_ok=True)
+    frames_by_stem = {os.path.splitext(os.path.basename(p))[0]: p for p in _list_images(image_folder)}
+    records = shard_paths(sorted(glob.glob(os.path.join(npy_folder, "*.npy"))), rank, world)
+    jobs = []
+    for npy in records:
+        stem = os.path.splitext(os.path.basename(npy))[0]
+        if stem not in frames_by_stem:
+            continue
+        data = np.load(npy, allow_pickle=True).item()
+        hands = [data[t] for t in ("right", "left") if data.get(t) is not None]
+        if hands:
+            jobs.append((stem, frames_by_stem[stem], hands))
+    dev = hamer.device
+    faces = torch.as_tensor(np.asarray(hamer.mano.faces, np.int32), device=dev)
+    try:
+        with ThreadPoolExecutor(_encode_threads()) as pool:
+            writer = PassWriter(pool)
+            sizes = list(pool.map(frame_size, [j[1] for j in jobs]))
+            for i in (i for i, hw in enumerate(sizes) if hw is None):
+                print(f"Skipping {jobs[i][0]}: image load failed")
+            for (H, W), part in size_passes(sizes, frames_per_pass):
+                batch, ok = decode_pass(pool, [jobs[i][1] for i in part], (H, W))
+                if batch is None:
+                    continue
+                part = [part[k] for k in ok]
+                K = np.asarray(k_real, np.float64) if k_real is not None else default_camera(H, W, hamer.cfg)
+                hands = [(n, h) for n, i in enumerate(part) for h in jobs[i][2]]
+                verts = camera_vertices(hamer, [h for _, h in hands])
+                meshes = [{"frame": n, "vertices": verts[j], "faces": faces, "is_right": bool(h["is_right"])}
+                          for j, (n, h) in enumerate(hands)]
+                out = overlay_frames(torch.from_numpy(batch).to(dev), K, meshes, style=style)
+                res = out.cpu().numpy()
+                writer.submit([(os.path.join(out_folder, jobs[i][0] + ext), res[n]) for n, i in enumerate(part)])
+            return writer.close()
+    finally:
+        release_workspaces()

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define HM_VERSION 402   /* 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
+#define HM_VERSION 402   /* 402 also carries the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
 
 enum { HM_DTYPE_BF16 = 0, HM_DTYPE_F16 = 1,
        HM_DTYPE_F32 = 2 /* the YOLOv7 detector path only (same value as HM_OUT_F32): see its section below */ };
@@ -444,6 +444,46 @@ typedef struct hm_yolo_op {
   hm_conv_args conv;
 } hm_yolo_op;
 int hm_yolo_run(const hm_yolo_op* ops_host, int n_ops, void* stream);
+
+/* Mesh overlay (hamer/reconstruct.py project_and_draw, :50-86): every face of every mesh filled into its
+ * frame, then blended with it.  The drawing rule, bit-exact (tests/render_rule.py restates it in numpy):
+ *  - geometry: a mesh is camera-frame vertices (fp64; the OBJ of reconstruct_and_save_obj_with_wrapper: MANO vertices,
+ *    x := -x for left hands, + cam_t) and triangles of one frame.  A corner's z == 0 becomes 1e-5, then in fp64, without
+ *    contraction and in this order, w = K20*x + K21*y + K22*z, u = (K00*x + K01*y + K02*z) / w, v = (K10*x + K11*y + K12*z) / w,
+ *    each truncated toward zero to int32 (astype(np.int32)).  Deviation: a face is skipped if a corner has z <= 0, if
+ *    |u| or |v| >= 2^24 (or is not a number), or if a corner index lies outside [0, nv) (the reference draws something
+ *    undefined in the first two cases);
+ *  - coverage: integer pixel (x, y) of the frame lies in the CLOSED triangle of the three integer corners (int64 edge
+ *    functions, winding-independent); a face of area 0 covers the integer points of its three segments.  cv2's own
+ *    scanline edge rule is not reproduced: the bytes are exact to this rule, unpinned against cv2.fillConvexPoly;
+ *  - visibility: a pixel takes the covering face of smallest key (fp32(((z0 + z1) + z2) / 3 in fp64), global face id), the
+ *    reference's painter's order (nearest drawn last), ties to the lower id.  The global face id is the face's row in
+ *    `faces`, so the result depends neither on the order of the mesh table nor on scheduling;
+ *  - HM_STYLE_FLAT (reconstruct.py): colour per mesh (BGR); a covered pixel becomes rint_half_even(a*c + b*i) per channel in
+ *    fp32 (product, product, sum), a = (float)alpha, b = (float)(1.0 - alpha) (cv2.addWeighted(overlay, 0.6, image, 0.4, 0));
+ *  - HM_STYLE_SHADED (an approximation of MeshRenderer + image_fusion, not pyrender's lighting): base colour (1.0, 1.0, 0.9)
+ *    RGB times I = 0.3 + 0.7*|n.z| (n the fp64 unit face normal, 0 for a face of area 0 in space), each channel
+ *    rint_half_even(255 * base * I) in fp64, replacing the pixel opaquely; the mesh colour is not used;
+ *  - every pixel no face covers is byte-identical to the input. */
+enum { HM_STYLE_FLAT = 0, HM_STYLE_SHADED = 1 };
+typedef struct hm_mesh {
+  int32_t frame;          /* frame of the batch the mesh is drawn into                                       */
+  int32_t v0, nv;         /* its vertices: rows v0 .. v0 + nv - 1 of verts                                   */
+  int32_t f0, nf;         /* its faces: rows f0 .. f0 + nf - 1 of faces, corner indices relative to v0 (0 .. nv-1);
+                             two meshes never share a face row                                                 */
+  uint8_t color_bgr[3];   /* HM_STYLE_FLAT colour                                                              */
+  uint8_t reserved;
+} hm_mesh;
+/* Workspace of one call; the first N*H*W*8 bytes are the per-pixel key buffer, which must hold 0xFF bytes on entry.  Fill
+ * the workspace with 0xFF once when it is allocated: every call resets the keys it wrote, so it stays reusable. */
+size_t hm_mesh_overlay_workspace_bytes(int N, int H, int W, int n_meshes, int n_faces);
+/* frames [N][H][W][3] u8 BGR (device), K [N][3][3] fp64 per frame (device), verts [n_verts][3] fp64 (device), faces
+ * [n_faces][3] int32 (device), meshes_host [n_meshes] (HOST, read before return), out [N][H][W][3] u8 (device, never
+ * overlapping frames).  0 <= alpha <= 1.  Three launches (setup, raster, compose) and one memset of the workspace's
+ * counters; no host synchronisation.  n_meshes == 0 copies the frames. */
+int hm_mesh_overlay(const uint8_t* frames, int N, int H, int W, const double* K, const double* verts, int n_verts,
+                    const int32_t* faces, int n_faces, const hm_mesh* meshes_host, int n_meshes, int style, double alpha,
+                    uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Optional per-launch timing (HIP events on the launch stream); kinds below. */
 enum { HM_K_GEMM = 0, HM_K_LAYERNORM = 1, HM_K_ATTENTION = 2, HM_K_IM2COL = 3, HM_K_LINEAR_F32 = 4,
