@@ -33,6 +33,7 @@ EXPORTS = [
     "hm_letterbox", "hm_yolo_decode", "hm_nms_workspace_bytes", "hm_yolo_nms", "hm_yolo_run", "hm_gemm_set_variant", "hm_gemm_set_group_m", "hm_ln_finalize", "hm_layernorm_accum", "hm_gemm_fp8", "hm_layernorm_mx8", "hm_vit_attention_mx8", "hm_nchw3_to_nhwc8", "hm_gap_linear",
     "hm_tome_index_bytes", "hm_tome_attention", "hm_tome_merge", "hm_set_option", "hm_get_option", "hm_tome_merge_metric", "hm_conv_splitk_bytes", "hm_yolo_decode_batch", "hm_letterbox_batch",
     "hm_option_count", "hm_gemm_px_grid", "hm_absmax16", "hm_mesh_overlay_workspace_bytes", "hm_mesh_overlay",
+    "hm_sar_saigb", "hm_sar_graph_mix", "hm_sar_linear", "hm_sar_softargmax", "hm_sar_postprocess",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -114,6 +115,13 @@ HM_STYLE_FLAT, HM_STYLE_SHADED = 0, 1      # hm_mesh_overlay styles
 
 class Mesh(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("frame", "v0", "nv", "f0", "nf")] + [("color_bgr", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class SarHand(C.Structure):
+    """hm_sar_hand: one hand of hm_sar_postprocess."""
+    _fields_ = [("bb2img", C.c_float * 6), ("depth_box", C.c_float), ("flip", C.c_int32), ("img_w", C.c_int32),
+                ("img_h", C.c_int32), ("depth_w", C.c_int32), ("depth_h", C.c_int32), ("depth_offset", C.c_int64),
+                ("fx", C.c_double), ("fy", C.c_double), ("fu", C.c_double), ("fv", C.c_double)]
 
 
 class ProfRecord(C.Structure):
@@ -202,6 +210,11 @@ def load() -> C.CDLL:
     lib.hm_mesh_overlay_workspace_bytes.argtypes = [i, i, i, i, i]
     lib.hm_mesh_overlay_workspace_bytes.restype = C.c_size_t
     lib.hm_mesh_overlay.argtypes = [vp, i, i, i, vp, vp, i, vp, i, C.POINTER(Mesh), i, i, d, vp, vp, C.c_size_t, vp]
+    lib.hm_sar_saigb.argtypes = [vp, vp, vp, vp, vp, i, vp]
+    lib.hm_sar_graph_mix.argtypes = [vp, i, vp, i, vp, vp]
+    lib.hm_sar_linear.argtypes = [vp, i, i, vp, vp, vp, i, i, vp]
+    lib.hm_sar_softargmax.argtypes = [vp] * 10 + [i, vp]
+    lib.hm_sar_postprocess.argtypes = [vp, vp, vp, vp, vp, vp, i, i, vp]
     lib.hm_prof_begin.argtypes = [i]
     lib.hm_prof_collect.argtypes = [C.POINTER(ProfRecord), i]
     lib.hm_prof_end.argtypes = []

@@ -47,8 +47,10 @@ class RootNetEngine:
             put(pre + "conv2", *fold(pre + "conv2", pre + "bn2"))
             if ds:
                 put(pre + "downsample", *fold(pre + "downsample.0", pre + "downsample.1"))
-        self.depth_w = root_sd["depth_layer.weight"].reshape(-1).to(self.device, torch.float32).contiguous()
-        self.depth_b = float(root_sd["depth_layer.bias"].reshape(-1)[0])
+        self.depth_w, self.depth_b = None, 0.0          # a checkpoint without ``rootnet``: features only (the SAR head's)
+        if root_sd is not None:
+            self.depth_w = root_sd["depth_layer.weight"].reshape(-1).to(self.device, torch.float32).contiguous()
+            self.depth_b = float(root_sd["depth_layer.bias"].reshape(-1)[0])
 
     def _conv(self, name, x, n, h, w, stride, act, resid=None):
         wt, bs, cin, co, k = self.w[name]
@@ -80,7 +82,12 @@ class RootNetEngine:
     def forward(self, img: torch.Tensor, k_value: torch.Tensor) -> torch.Tensor:
         """depth (B,) = (GAP(features) . w + b) * k_value (ResRootNet.forward_coord, Model_RGB.py:282-292)."""
         kv = k_value.to(self.device, torch.float32).contiguous()      # (a pageable upload waits for the stream: before the backbone is queued)
-        f = self.features(img)
+        return self.depth_of(self.features(img), kv)
+
+    def depth_of(self, f: torch.Tensor, kv: torch.Tensor) -> torch.Tensor:
+        """ResRootNet.forward_coord on features already computed: f (B, 8, 8, 512), kv (B,) fp32 on the device -> (B,)."""
+        if self.depth_w is None:
+            raise RuntimeError("RootNet is not loaded in the checkpoint!")
         B, h, w, c = f.shape
         depth = torch.empty(B, device=self.device, dtype=torch.float32)
         L.check(self.lib.hm_gap_linear(L.ptr(f), h * w, c, L.ptr(self.depth_w), self.depth_b, L.ptr(kv), L.ptr(depth), B, self.dt,

@@ -374,3 +374,39 @@ def rootnet_state_dict(seed: int = 0):
     root = {"depth_layer.weight": uniform("depth_layer.weight", (1, 512, 1, 1), 0.05, 0.02, seed=seed),
             "depth_layer.bias": uniform("depth_layer.bias", (1,), 0.05, 0.3, seed=seed)}
     return net, root
+
+
+SAR_NV, SAR_NJ, SAR_HM = 778, 21, 32
+
+
+def sar_head_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Seeded weights with the ``head.*`` keys of the reference's SAR state dict (SARhead, rootnet/Model_RGB.py:198-222 with
+    resnet34: in_channels 512, 8 feature maps of 64 cells, 778 vertices, 21 joints, 32 x 32 heatmaps).
+
+    Calibrated so the soft-argmax sees PEAKED heatmaps (a near-uniform softmax puts every coordinate at the centre and
+    coordinate parity would prove nothing): the xy logits have a spread of ~3 after ``beta``, the z logits ~0.3 (depths of
+    +-0.1 m after depth_box).  Each ``adj`` is the identity plus ~8 random neighbours of weight 0.3 per row plus a small
+    dense term, so L = A / rowsum(A) mixes a node mostly with a few others and every entry of the dense product is used."""
+    sd: Dict[str, torch.Tensor] = {}
+    h = "head."
+    sd[h + "saigb.template"] = uniform(h + "saigb.template", (SAR_NV, 3), 0.08, 0.0, seed=seed)
+    sd[h + "saigb.group.0.weight"] = uniform(h + "saigb.group.0.weight", (8 * SAR_NV, 512, 1, 1), 0.11, 0.0, seed=seed)
+    sd[h + "saigb.group.0.bias"] = uniform(h + "saigb.group.0.bias", (8 * SAR_NV,), 0.3, 0.0, seed=seed)
+    cells = SAR_HM * SAR_HM
+    for br, out_gain in (("reg_xy", 5.0), ("reg_z", 0.05)):
+        for layer, (cin, gain) in (("0", (515, 2.0)), ("3", (cells, out_gain))):
+            pre = f"{h}gbbmr.{br}.{layer}."
+            sd[pre + "fc.weight"] = uniform(pre + "fc.weight", (cells, cin), gain * (3.0 / cin) ** 0.5, 0.0, seed=seed)
+            sd[pre + "fc.bias"] = uniform(pre + "fc.bias", (cells,), 0.1, 0.0, seed=seed)
+            dense = uniform(pre + "adj", (SAR_NV, SAR_NV), 0.004, 0.0, seed=seed)
+            pick = uniform(pre + "adj.neighbours", (SAR_NV, SAR_NV), 1.0, 0.0, seed=seed) > 0.98
+            sd[pre + "adj"] = torch.eye(SAR_NV) + dense + 0.3 * pick.float()
+    for name in ("mesh2pose_hm", "mesh2pose_dm"):
+        sd[f"{h}gbbmr.{name}.weight"] = uniform(f"{h}gbbmr.{name}.weight", (SAR_NJ, SAR_NV), 0.08, 0.0, seed=seed)
+        sd[f"{h}gbbmr.{name}.bias"] = uniform(f"{h}gbbmr.{name}.bias", (SAR_NJ,), 0.1, 0.0, seed=seed)
+    sd[h + "gbbmr.soft_heatmap.beta.weight"] = uniform(h + "gbbmr.soft_heatmap.beta.weight", (SAR_NV + SAR_NJ, 1, 1, 1), 0.3, 1.0,
+                                                       seed=seed)
+    ar = torch.arange(0.0, float(SAR_HM))
+    sd[h + "gbbmr.soft_heatmap.wx"] = ar.view(1, SAR_HM).repeat(SAR_HM, 1)        # SoftHeatmap.__init__ (:79-83)
+    sd[h + "gbbmr.soft_heatmap.wy"] = ar.view(SAR_HM, 1).repeat(1, SAR_HM)
+    return sd

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define HM_VERSION 402   /* 402 also carries the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
+#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
 
 enum { HM_DTYPE_BF16 = 0, HM_DTYPE_F16 = 1,
        HM_DTYPE_F32 = 2 /* the YOLOv7 detector path only (same value as HM_OUT_F32): see its section below */ };
@@ -484,6 +484,47 @@ size_t hm_mesh_overlay_workspace_bytes(int N, int H, int W, int n_meshes, int n_
 int hm_mesh_overlay(const uint8_t* frames, int N, int H, int W, const double* K, const double* verts, int n_verts,
                     const int32_t* faces, int n_faces, const hm_mesh* meshes_host, int n_meshes, int style, double alpha,
                     uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- SAR hand-mesh head of the RootNet checkpoint (rootnet/Model_RGB.py:76-177 SoftHeatmap / GraphConv / SAIGB / GBBMR,
+ * :198-222 SARhead, :428-480 post_processing, :500-570 EstimateRGB.run).  f16 operands, fp32 accumulation; activations are
+ * node-major across the batch, [778][B][C].  No split-K and no batch-dependent reduction order: a hand's numbers are the
+ * same alone and inside any batch.  All pointers are device pointers unless marked HOST. */
+
+/* SAIGB (:119-136): feat [B][8][8][512] f16 (NHWC backbone output), w [6224][512] f16 (the 1x1 conv), bias [6224] f32,
+ * tmpl [778][3] f32 (head.saigb.template) -> g [778][B][544] f16: node v, hand b holds LeakyReLU_0.1(conv + bias) of
+ * channels 8v .. 8v+7 x the 64 positions (the .view(-1, 778, 512) of NCHW), then the 3 template values, then 29 zeros. */
+int hm_sar_saigb(const void* feat, const void* w, const float* bias, const float* tmpl, void* g, int B, void* stream);
+/* The L . x of GraphConv.forward (:110-115) for all hands at once: y [778][N] f16 = lap [778][ldl] f16 . x [778][N] f16,
+ * lap = adj / (rowsum(adj) + 1e-5) with columns 778 .. ldl-1 zero; ldl % 32 == 0, N % 8 == 0 (N = B * C). */
+int hm_sar_graph_mix(const void* lap, int ldl, const void* x, int N, void* y, void* stream);
+/* GraphConv.fc (:115) over M = 778 * B rows: y [M][N] = x [M][K] f16 . w [N][K]^T f16 + bias [N] f32; out_f32 == 0:
+ * LeakyReLU(0.1) (:148-149) and f16 out, out_f32 == 1: no activation, f32 out (the second layer's logits).  K % 32 == 0
+ * (zero-padded columns in both operands). */
+int hm_sar_linear(const void* x, int M, int K, const void* w, const float* bias, void* y, int N, int out_f32, void* stream);
+/* GBBMR.forward's tail (:163-176): logits_xy / logits_z are [799][B][1024] f32 whose rows 0 .. 777 hold the two branches'
+ * second-layer logits; rows 778 .. 798 are WRITTEN here by mesh2pose_hm / mesh2pose_dm (w [21][778], b [21]).  Then
+ * SoftHeatmap (:76-99): beta [799] (beta.weight), softmax over the 1024 cells, x = sum p * wx, y = sum p * wy (the
+ * checkpoint's [32][32] wx / wy buffers), z = sum p * heatmap_z, xy / 16 - 1 -> coords [B][799][3] f32.  Two launches. */
+int hm_sar_softargmax(float* logits_xy, float* logits_z, const float* m2p_w_xy, const float* m2p_b_xy, const float* m2p_w_z,
+                      const float* m2p_b_z, const float* beta, const float* wx, const float* wy, float* coords, int B,
+                      void* stream);
+/* One hand of hm_sar_postprocess. */
+typedef struct hm_sar_hand {
+  float bb2img[6];        /* 2x3 patch -> frame map (generate_patch_image's inv_trans), f32                          */
+  float depth_box;        /* cfg.depth_box (0.3)                                                                      */
+  int32_t flip;           /* 1: left hand, x -> img_w - x - 1 after the map (:445-446)                                */
+  int32_t img_w, img_h;   /* frame size                                                                               */
+  int32_t depth_w, depth_h; /* size of this hand's depth map                                                          */
+  int64_t depth_offset;   /* >= 0: root depth = grid_sample of depth + depth_offset (f32 metres) at row 778, else root */
+  double fx, fy, fu, fv;  /* camera K                                                                                 */
+} hm_sar_hand;
+/* post_processing (:428-480) with run's root depth (:533-551): coords [B][799][3] f32 (hm_sar_softargmax), hands [B]
+ * (device), root [B] f32 metres or NULL (0), depth: the depth maps hands[].depth_offset points into, or NULL.
+ * z = z * depth_box + root; uv = (uv + 0.5) * P; bb2img; flip; uvd2xyz (preprocessing.py:11-17) -> uvd, xyz [B][799][3]
+ * f32 (rows 778 .. are the joints).  With a depth map the root is the bilinear (zeros, align_corners=False) sample at
+ * convert2origin_pixel(row 778) / (W // 2, H // 2) - 1, which for a left hand is NOT un-flipped: the reference's rule. */
+int hm_sar_postprocess(const float* coords, const hm_sar_hand* hands, const float* root, const float* depth, float* uvd,
+                       float* xyz, int B, int P, void* stream);
 
 /* Optional per-launch timing (HIP events on the launch stream); kinds below. */
 enum { HM_K_GEMM = 0, HM_K_LAYERNORM = 1, HM_K_ATTENTION = 2, HM_K_IM2COL = 3, HM_K_LINEAR_F32 = 4,
