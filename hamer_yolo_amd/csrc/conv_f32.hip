@@ -19,6 +19,7 @@
 // (k-slot 1) hold k = 8g + 4 + e, e = 0..3 the MFMA's index in the group -- one 16-byte LDS read per operand and group, the
 // same mapping on both operands.
 #include <math.h>
+#include <stdio.h>
 #include "common.h"
 #include "hamer_hip_internal.h"
 
@@ -35,12 +36,18 @@ struct ConvF32Args {
   const float* bias;   // [Cout]
   float* Y;            // [M][ldy], already offset to the channel slice
   int H, Wd, Hout, Wout, Cin, cin_log2, ksz, stride, pad, taps, ldx, ldy, Kpad, nk, M, Cout, act;
+  const float* R;      // EPI_RELU only: optional [M][ldr] residual, added before the ReLU
+  int ldr;
 };
+
+// epilogues: EPI_YOLO is hm_conv2d_nhwc's (act 1: SiLU, act 0: none); EPI_RELU is hm_conv2d_f32_relu's (the ResNet-34 of the
+// RootNet backbone: + optional residual, then ReLU when act == 2).  Both apply to the same k-ordered sum.
+enum { EPI_YOLO = 0, EPI_RELU = 1 };
 
 template <int WM, int WN, int RB, int CB>
 constexpr int conv_f32_lds_bytes() { return 2 * (WM * RB * 32 + WN * CB * 32) * F32_LDK * 4; }
 
-template <int WM, int WN, int RB, int CB>
+template <int WM, int WN, int RB, int CB, int EPI>
 __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32Args a) {
   static_assert(WM * WN == 4, "4 waves");
   constexpr int BM = WM * RB * 32, BN = WN * CB * 32;
@@ -153,56 +160,101 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32Args a) {
         const int m = m0 + (wm * RB + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         if (m >= a.M) continue;
         float v = acc[i][j][r] + b;
-        if (a.act) v = v / (1.0f + expf(-v));        // SiLU as torch's CPU kernel writes it: x / (1 + exp(-x)), IEEE division
+        if constexpr (EPI == EPI_YOLO) {
+          if (a.act) v = v / (1.0f + expf(-v));      // SiLU as torch's CPU kernel writes it: x / (1 + exp(-x)), IEEE division
+        } else {
+          if (a.R) v += a.R[(size_t)m * a.ldr + co];  // BasicBlock: bn2(conv2(x)) + identity, then ReLU
+          if (a.act) v = v > 0.f ? v : 0.f;
+        }
         a.Y[(size_t)m * a.ldy + co] = v;
       }
   }
 }
 
-template <int WM, int WN, int RB, int CB>
+template <int WM, int WN, int RB, int CB, int EPI>
 int launch_conv_f32(const ConvF32Args& g, hipStream_t s) {
   constexpr int BM = WM * RB * 32, BN = WN * CB * 32, LDS = conv_f32_lds_bytes<WM, WN, RB, CB>();
-  auto kern = conv_f32_kernel<WM, WN, RB, CB>;
+  auto kern = conv_f32_kernel<WM, WN, RB, CB, EPI>;
   static HmLdsOnce lds_once;
   if (const int rc = lds_once.ensure((const void*)kern, LDS, "hm_conv2d_nhwc (fp32): cannot raise the dynamic LDS limit")) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)((g.M + BM - 1) / BM), (unsigned)((g.Cout + BN - 1) / BN)), dim3(256), LDS, s, g);
-  return hm_check_launch("hm_conv2d_nhwc (fp32)");
+  return hm_check_launch(EPI == EPI_YOLO ? "hm_conv2d_nhwc (fp32)" : "hm_conv2d_f32_relu");
+}
+
+// the tile changes which threads compute an output, never its arithmetic (see the numerics contract above)
+template <int EPI>
+int dispatch_conv_f32(const ConvF32Args& g, hipStream_t stream) {
+  if (g.Cout <= 32) return launch_conv_f32<4, 1, 2, 1, EPI>(g, stream);                  // 256 x 32: Conv 0 (32), the detect heads (24)
+  if (g.Cout <= 64) return launch_conv_f32<4, 1, 2, 2, EPI>(g, stream);                  // 256 x 64
+  const long tiles = (long)((g.M + 127) / 128) * ((g.Cout + 127) / 128);
+  if (tiles < hm_device_cu_count()) return launch_conv_f32<2, 2, 1, 1, EPI>(g, stream);  // 64 x 64: the small maps of one frame
+  return launch_conv_f32<2, 2, 2, 2, EPI>(g, stream);                                    // 128 x 128
+}
+
+// the checks both entry points share, in two parts (the entry point's own act / resid checks go between them, as
+// hm_conv2d_nhwc always ordered them); `what` names the entry point in the error string
+int conv_f32_fail(const char* what, const char* why) {
+  char msg[192];
+  snprintf(msg, sizeof msg, "%s: %s", what, why);
+  return hm_set_error(HM_ERR_ARG, msg);
+}
+
+int conv_f32_check_shape(const hm_conv_args& c, const char* what) {
+  if (!c.X || !c.W || !c.Y || !c.bias) return conv_f32_fail(what, "null operand");
+  if (c.N <= 0 || c.H <= 0 || c.W_in <= 0 || c.Cin <= 0 || c.Cout <= 0) return conv_f32_fail(what, "empty problem");
+  if ((c.ksize != 1 && c.ksize != 3 && c.ksize != 5 && c.ksize != 7) || (c.stride != 1 && c.stride != 2))
+    return conv_f32_fail(what, "kernel size 1, 3, 5 or 7, stride 1 or 2");
+  return HM_OK;
+}
+
+int conv_f32_args(const hm_conv_args& c, const char* what, ConvF32Args& g) {
+  int lg = 0;
+  while ((1 << lg) < c.Cin) ++lg;
+  if ((1 << lg) != c.Cin || c.Cin < 8) return conv_f32_fail(what, "Cin must be a power of two >= 8");
+  const int taps = c.ksize * c.ksize;
+  if (c.Kpad % 64 != 0 || c.Kpad < taps * c.Cin) return conv_f32_fail(what, "Kpad must be a multiple of 64 covering k*k*Cin");
+  if (c.ldx % 4 != 0 || c.ldx < c.Cin || c.ldy < c.Cout) return conv_f32_fail(what, "ldx % 4 == 0, ldx >= Cin, ldy >= Cout");
+  if ((((uintptr_t)c.X | (uintptr_t)c.W) & 15) || (((uintptr_t)c.Y | (uintptr_t)c.bias) & 3))
+    return conv_f32_fail(what, "X / W 16-byte aligned, Y / bias 4-byte aligned");
+  const int pad = c.ksize / 2;
+  const int Hout = (c.H + 2 * pad - c.ksize) / c.stride + 1, Wout = (c.W_in + 2 * pad - c.ksize) / c.stride + 1;
+  if ((size_t)c.N * Hout * Wout >= (1ull << 31) || (size_t)c.N * c.H * c.W_in >= (1ull << 31)) return conv_f32_fail(what, "more than 2^31 pixels");
+  g = ConvF32Args{};
+  g.X = (const float*)c.X; g.W = (const float*)c.W; g.bias = c.bias; g.Y = (float*)c.Y;
+  g.H = c.H; g.Wd = c.W_in; g.Hout = Hout; g.Wout = Wout; g.Cin = c.Cin; g.cin_log2 = lg; g.ksz = c.ksize; g.stride = c.stride;
+  g.pad = pad; g.taps = taps; g.ldx = c.ldx; g.ldy = c.ldy; g.Kpad = c.Kpad; g.M = c.N * Hout * Wout; g.Cout = c.Cout;
+  g.nk = (taps * c.Cin + F32_BK - 1) / F32_BK;       // stages up to k*k*Cin: the zero tail of Kpad adds nothing (Conv 0: 72 -> 96, not 128)
+  g.act = c.act;
+  return HM_OK;
 }
 
 }  // namespace
 
 int hm_conv2d_f32(const hm_conv_args* a, hipStream_t stream) {
   const hm_conv_args& c = *a;
-  if (!c.X || !c.W || !c.Y || !c.bias) return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): null operand");
-  if (c.N <= 0 || c.H <= 0 || c.W_in <= 0 || c.Cin <= 0 || c.Cout <= 0) return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): empty problem");
-  if ((c.ksize != 1 && c.ksize != 3 && c.ksize != 5 && c.ksize != 7) || (c.stride != 1 && c.stride != 2))
-    return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): kernel size 1, 3, 5 or 7, stride 1 or 2");
+  if (const int rc = conv_f32_check_shape(c, "hm_conv2d_nhwc (fp32)")) return rc;
   if (c.act < 0 || c.act > 1 || c.resid || (c.out_f32 && c.act))
     return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): act is 0 or 1 (SiLU), no resid / ReLU");
-  int lg = 0;
-  while ((1 << lg) < c.Cin) ++lg;
-  if ((1 << lg) != c.Cin || c.Cin < 8) return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): Cin must be a power of two >= 8");
-  const int taps = c.ksize * c.ksize;
-  if (c.Kpad % 64 != 0 || c.Kpad < taps * c.Cin) return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): Kpad must be a multiple of 64 covering k*k*Cin");
-  if (c.ldx % 4 != 0 || c.ldx < c.Cin || c.ldy < c.Cout)
-    return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): ldx % 4 == 0, ldx >= Cin, ldy >= Cout");
-  if ((((uintptr_t)c.X | (uintptr_t)c.W) & 15) || (((uintptr_t)c.Y | (uintptr_t)c.bias) & 3))
-    return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): X / W 16-byte aligned, Y / bias 4-byte aligned");
-  const int pad = c.ksize / 2;
-  const int Hout = (c.H + 2 * pad - c.ksize) / c.stride + 1, Wout = (c.W_in + 2 * pad - c.ksize) / c.stride + 1;
-  if ((size_t)c.N * Hout * Wout >= (1ull << 31) || (size_t)c.N * c.H * c.W_in >= (1ull << 31))
-    return hm_set_error(HM_ERR_ARG, "hm_conv2d_nhwc (fp32): more than 2^31 pixels");
-  ConvF32Args g{};
-  g.X = (const float*)c.X; g.W = (const float*)c.W; g.bias = c.bias; g.Y = (float*)c.Y;
-  g.H = c.H; g.Wd = c.W_in; g.Hout = Hout; g.Wout = Wout; g.Cin = c.Cin; g.cin_log2 = lg; g.ksz = c.ksize; g.stride = c.stride;
-  g.pad = pad; g.taps = taps; g.ldx = c.ldx; g.ldy = c.ldy; g.Kpad = c.Kpad; g.M = c.N * Hout * Wout; g.Cout = c.Cout;
-  g.nk = (taps * c.Cin + F32_BK - 1) / F32_BK;       // stages up to k*k*Cin: the zero tail of Kpad adds nothing (Conv 0: 72 -> 96, not 128)
-  g.act = c.act;
-  HmProfScope prof(HM_K_CONV, c.ksize * 10 + c.stride, g.M, g.Cout, taps * c.Cin, stream);
-  // the tile changes which threads compute an output, never its arithmetic (see the numerics contract above)
-  if (c.Cout <= 32) return launch_conv_f32<4, 1, 2, 1>(g, stream);                  // 256 x 32: Conv 0 (32), the detect heads (24)
-  if (c.Cout <= 64) return launch_conv_f32<4, 1, 2, 2>(g, stream);                  // 256 x 64
-  const long tiles = (long)((g.M + 127) / 128) * ((g.Cout + 127) / 128);
-  if (tiles < hm_device_cu_count()) return launch_conv_f32<2, 2, 1, 1>(g, stream);  // 64 x 64: the small maps of one frame
-  return launch_conv_f32<2, 2, 2, 2>(g, stream);                                    // 128 x 128
+  ConvF32Args g;
+  if (const int rc = conv_f32_args(c, "hm_conv2d_nhwc (fp32)", g)) return rc;
+  HmProfScope prof(HM_K_CONV, c.ksize * 10 + c.stride, g.M, g.Cout, g.taps * c.Cin, stream);
+  return dispatch_conv_f32<EPI_YOLO>(g, stream);
+}
+
+extern "C" int hm_conv2d_f32_relu(const hm_conv_args* a, void* stream_) {
+  if (!a) return hm_set_error(HM_ERR_ARG, "hm_conv2d_f32_relu: null args");
+  const hm_conv_args& c = *a;
+  if (c.dtype != HM_DTYPE_F32) return hm_set_error(HM_ERR_ARG, "hm_conv2d_f32_relu: dtype must be HM_DTYPE_F32");
+  if (const int rc = conv_f32_check_shape(c, "hm_conv2d_f32_relu")) return rc;
+  if ((c.act != 0 && c.act != 2) || c.out_f32) return hm_set_error(HM_ERR_ARG, "hm_conv2d_f32_relu: act is 0 or 2 (ReLU), out_f32 is 0");
+  if (c.resid && (c.ldr < c.Cout || ((uintptr_t)c.resid & 3)))
+    return hm_set_error(HM_ERR_ARG, "hm_conv2d_f32_relu: resid needs ldr >= Cout and 4-byte alignment");
+  ConvF32Args g;
+  if (const int rc = conv_f32_args(c, "hm_conv2d_f32_relu", g)) return rc;
+  g.R = (const float*)c.resid;
+  g.ldr = c.ldr;
+  g.act = c.act == 2;
+  hipStream_t stream = (hipStream_t)stream_;
+  HmProfScope prof(HM_K_CONV, c.ksize * 10 + c.stride, g.M, g.Cout, g.taps * c.Cin, stream);
+  return dispatch_conv_f32<EPI_RELU>(g, stream);
 }

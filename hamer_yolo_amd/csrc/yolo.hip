@@ -331,6 +331,28 @@ extern "C" int hm_gap_linear(const void* feat, int HW, int C, const float* w, fl
   return rc != HM_OK ? rc : hm_check_launch("hm_gap_linear");
 }
 
+// the fp32 forms of the two RootNet ops (the precise route of EstimateRGB): the same kernels instantiated for float.  The
+// pooling order is the one above -- per channel the HW positions in order, then the channels in the fixed order of the
+// 256-thread sweep and the 4-wave sum -- and depends on nothing but HW and C, so a hand's depth does not depend on B.
+extern "C" int hm_nchw3_to_nhwc8_f32(const float* x, float* y, int B, int H, int W, void* stream_) {
+  if (!x || !y || B <= 0 || H <= 0 || W <= 0 || (((uintptr_t)x & 3) | ((uintptr_t)y & 15)))
+    return hm_set_error(HM_ERR_ARG, "hm_nchw3_to_nhwc8_f32: bad arguments (y 16-byte aligned)");
+  hipStream_t s = (hipStream_t)stream_;
+  const size_t total = (size_t)B * H * W;
+  hipLaunchKernelGGL(nchw3_to_nhwc8_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, y, B, H * W);
+  return hm_check_launch("hm_nchw3_to_nhwc8_f32");
+}
+
+extern "C" int hm_gap_linear_f32(const float* feat, int HW, int C, const float* w, float bias, const float* k_value, float* depth,
+                                 int B, void* stream_) {
+  if (!feat || !w || !k_value || !depth || HW <= 0 || C <= 0 || B <= 0 || (((uintptr_t)feat | (uintptr_t)w | (uintptr_t)k_value |
+                                                                             (uintptr_t)depth) & 3))
+    return hm_set_error(HM_ERR_ARG, "hm_gap_linear_f32: bad arguments");
+  hipStream_t s = (hipStream_t)stream_;
+  hipLaunchKernelGGL(gap_linear_kernel<float>, dim3(B), dim3(256), 0, s, feat, HW, C, w, bias, k_value, depth);
+  return hm_check_launch("hm_gap_linear_f32");
+}
+
 extern "C" int hm_upsample2x_nhwc(const void* x, int ldx, void* y, int ldy, int N, int H, int W, int C, int dtype, void* stream_) {
   if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0) return hm_set_error(HM_ERR_ARG, "hm_upsample2x_nhwc: bad arguments");
   if (C % 8 || ldx % 8 || ldy % 8 || (((uintptr_t)x | (uintptr_t)y) & 15)) return hm_set_error(HM_ERR_ARG, "hm_upsample2x_nhwc: C, ld % 8 and 16-byte alignment");

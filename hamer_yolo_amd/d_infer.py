@@ -47,6 +47,8 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument('--obj', type=str, default=None, help="also reconstruct OBJ meshes into this folder")
     ap.add_argument('--precise-detector', action='store_true',
                     help="run YOLOv7 in fp32 (the reference's CPU branch) instead of fp16: its boxes, at about twice the detector time")
+    ap.add_argument('--precise-rootnet', action='store_true',
+                    help="run the RootNet backbone and depth head in fp32, as the reference does, instead of fp16 (DESIGN §9)")
     _render_args(ap)
     return ap
 
@@ -57,6 +59,9 @@ def main(argv=None):
     if args.precise_detector:
         from .config.yolo_config import yolo_opt
         yolo_opt.precise = True
+    if args.precise_rootnet:
+        from .rootnet.sar_config_stage_1 import rgb_opt
+        rgb_opt.precise = True
     k_real = load_intrinsics(args.intrinsics)
     hamer = hamer_inference(hamer_opt)
     process_batch_manopara(args.input, args.output, k_real, hamer=hamer)

@@ -34,6 +34,7 @@ EXPORTS = [
     "hm_tome_index_bytes", "hm_tome_attention", "hm_tome_merge", "hm_set_option", "hm_get_option", "hm_tome_merge_metric", "hm_conv_splitk_bytes", "hm_yolo_decode_batch", "hm_letterbox_batch",
     "hm_option_count", "hm_gemm_px_grid", "hm_absmax16", "hm_mesh_overlay_workspace_bytes", "hm_mesh_overlay",
     "hm_sar_saigb", "hm_sar_graph_mix", "hm_sar_linear", "hm_sar_softargmax", "hm_sar_postprocess",
+    "hm_conv2d_f32_relu", "hm_nchw3_to_nhwc8_f32", "hm_gap_linear_f32", "hm_sar_saigb_f32", "hm_sar_graph_mix_f32", "hm_sar_linear_f32",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -215,6 +216,12 @@ def load() -> C.CDLL:
     lib.hm_sar_linear.argtypes = [vp, i, i, vp, vp, vp, i, i, vp]
     lib.hm_sar_softargmax.argtypes = [vp] * 10 + [i, vp]
     lib.hm_sar_postprocess.argtypes = [vp, vp, vp, vp, vp, vp, i, i, vp]
+    lib.hm_conv2d_f32_relu.argtypes = [C.POINTER(ConvArgs), vp]
+    lib.hm_nchw3_to_nhwc8_f32.argtypes = [vp, vp, i, i, i, vp]
+    lib.hm_gap_linear_f32.argtypes = [vp, i, i, vp, C.c_float, vp, vp, i, vp]
+    lib.hm_sar_saigb_f32.argtypes = [vp, vp, vp, vp, vp, i, vp]
+    lib.hm_sar_graph_mix_f32.argtypes = [vp, i, vp, i, vp, vp]
+    lib.hm_sar_linear_f32.argtypes = [vp, i, i, vp, vp, vp, i, i, vp]
     lib.hm_prof_begin.argtypes = [i]
     lib.hm_prof_collect.argtypes = [C.POINTER(ProfRecord), i]
     lib.hm_prof_end.argtypes = []

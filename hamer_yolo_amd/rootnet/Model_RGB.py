@@ -3,7 +3,8 @@
 ``calculate_k``; and the reference's own estimator ``run(input)`` (:500-570): the SAR hand-mesh head (SAIGB + GBBMR +
 SoftHeatmap) on the same ResNet-34 features, root depth from ResRootNet or a depth image, and ``post_processing`` (:428-480).
 ``run_frames`` is the batched form: all hands of several frames through one backbone, one head, one RootNet and one
-post-process launch."""
+post-process launch.  ``EstimateRGB(cfg, precise=True)`` (or ``cfg.precise``) runs the backbone, the depth head and the SAR
+head in fp32, as the reference does, on the fp32-input MFMA: deterministic and batch-invariant."""
 from __future__ import annotations
 
 import numpy as np
@@ -51,9 +52,12 @@ def draw_2d_skeleton(image: np.ndarray, pose_uv: np.ndarray) -> np.ndarray:
 
 
 class EstimateRGB:
-    def __init__(self, cfg):
+    def __init__(self, cfg, precise=None):
+        """precise: None reads ``cfg.precise`` (default False).  True runs the fp32 route: the backbone, ResRootNet and the
+        SAR head in fp32 operands; the crop, the left-hand rule, the depth-image root and the post-process are shared."""
         self.cfg = cfg
         self.mode = 'estimate'
+        self.precise = bool(getattr(cfg, 'precise', False) if precise is None else precise)
         if getattr(cfg, 'backbone', 'resnet34') != 'resnet34':
             raise NotImplementedError(f"EstimateRGB: backbone {cfg.backbone!r} is not supported; only the resnet34 SAR "
                                       "checkpoint runs here (the ConvNeXt SAR is out of scope)")
@@ -70,9 +74,9 @@ class EstimateRGB:
         self.device = torch.device(cfg.device if torch.cuda.is_available() else 'cpu')
         if self.device.type != 'cuda':
             raise L.HipLibraryError("EstimateRGB runs on an MI355X only: the HIP hot path has no CPU fallback")
-        self.engine = RootNetEngine(net, root, device=self.device)
+        self.engine = RootNetEngine(net, root, device=self.device, dtype=torch.float32 if self.precise else torch.float16)
         self.rootnet = self.engine if root is not None else None
-        self.head = SarHeadEngine(net, device=self.device) if all(k in net for k in head_keys()) else None
+        self.head = SarHeadEngine(net, device=self.device, precise=self.precise) if all(k in net for k in head_keys()) else None
         self.mean = 255.0 * np.array([0.485, 0.456, 0.406])
         self.std = 255.0 * np.array([0.229, 0.224, 0.225])
 

@@ -1,5 +1,7 @@
 """RootNetEngine: ResNet-34 backbone + ResRootNet depth head on libhamer_hip (NHWC 16-bit implicit-GEMM convolutions with
-BatchNorm folded in, ReLU / residual-add epilogues, max-pool, fused global-average-pool + 1x1 conv)."""
+BatchNorm folded in, ReLU / residual-add epilogues, max-pool, fused global-average-pool + 1x1 conv).  dtype=torch.float32 is
+the precise route: the same network in fp32 operands on the fp32-input MFMA (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32,
+hm_gap_linear_f32), deterministic and batch-invariant."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,7 +23,8 @@ class RootNetEngine:
             raise L.HipLibraryError("RootNetEngine needs an MI355X (HIP device); there is no CPU fallback")
         self.lib = L.load()
         self.device, self.dtype = torch.device(device), dtype
-        self.dt = L.HM_DTYPE_BF16 if dtype == torch.bfloat16 else L.HM_DTYPE_F16
+        self.precise = dtype == torch.float32
+        self.dt = L.HM_DTYPE_F32 if self.precise else L.HM_DTYPE_BF16 if dtype == torch.bfloat16 else L.HM_DTYPE_F16
         self.zeros = torch.zeros(64, dtype=torch.uint8, device=self.device)
         self.w: Dict[str, tuple] = {}
 
@@ -58,14 +61,21 @@ class RootNetEngine:
         y = torch.empty(n, ho, wo, co, device=self.device, dtype=self.dtype)
         a = L.ConvArgs(L.ptr(x), L.ptr(wt), L.ptr(y), L.ptr(bs), L.ptr(self.zeros), n, h, w, cin, co, k, stride, x.shape[-1], co,
                        wt.shape[1], act, 0, self.dt, L.ptr(resid), co if resid is not None else 0)
-        L.check(self.lib.hm_conv2d_nhwc(C.byref(a), L.current_stream()), "hm_conv2d_nhwc")
+        if self.precise:
+            L.check(self.lib.hm_conv2d_f32_relu(C.byref(a), L.current_stream()), "hm_conv2d_f32_relu")
+        else:
+            L.check(self.lib.hm_conv2d_nhwc(C.byref(a), L.current_stream()), "hm_conv2d_nhwc")
         return y, ho, wo
 
     def features(self, img: torch.Tensor) -> torch.Tensor:
-        """img (B, 3, 256, 256) fp32 normalised RGB planes (the layout hm_crop_batch writes) -> (B, 8, 8, 512) NHWC."""
+        """img (B, 3, 256, 256) fp32 normalised RGB planes (the layout hm_crop_batch writes) -> (B, 8, 8, 512) NHWC in the
+        engine's dtype."""
         B, _, H, W = img.shape
         x = torch.empty(B, H, W, 8, device=self.device, dtype=self.dtype)
-        L.check(self.lib.hm_nchw3_to_nhwc8(L.ptr(img.contiguous()), L.ptr(x), B, H, W, self.dt, L.current_stream()), "hm_nchw3_to_nhwc8")
+        if self.precise:
+            L.check(self.lib.hm_nchw3_to_nhwc8_f32(L.ptr(img.contiguous()), L.ptr(x), B, H, W, L.current_stream()), "hm_nchw3_to_nhwc8_f32")
+        else:
+            L.check(self.lib.hm_nchw3_to_nhwc8(L.ptr(img.contiguous()), L.ptr(x), B, H, W, self.dt, L.current_stream()), "hm_nchw3_to_nhwc8")
         x, h, w = self._conv("stem", x, B, H, W, 2, 2)
         ho, wo = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
         y = torch.empty(B, ho, wo, 64, device=self.device, dtype=self.dtype)
@@ -90,6 +100,11 @@ class RootNetEngine:
             raise RuntimeError("RootNet is not loaded in the checkpoint!")
         B, h, w, c = f.shape
         depth = torch.empty(B, device=self.device, dtype=torch.float32)
+        if self.precise:
+            assert f.dtype == torch.float32 and f.is_contiguous()
+            L.check(self.lib.hm_gap_linear_f32(L.ptr(f), h * w, c, L.ptr(self.depth_w), self.depth_b, L.ptr(kv), L.ptr(depth), B,
+                                               L.current_stream()), "hm_gap_linear_f32")
+            return depth
         L.check(self.lib.hm_gap_linear(L.ptr(f), h * w, c, L.ptr(self.depth_w), self.depth_b, L.ptr(kv), L.ptr(depth), B, self.dt,
                                        L.current_stream()), "hm_gap_linear")
         return depth

@@ -3,7 +3,8 @@ on libhamer_hip, for all hands of a call at once, plus the post-processing of Es
 
 Load-time work: the ``head.*`` keys are mapped, the four Laplacians L = A / (rowsum(A) + 1e-5) are formed in fp32 as torch
 does, and the weights are padded (K to a multiple of 32 with zeros) and cast to f16.  Activations stay node-major across the
-batch ([778][B][C]); see csrc/sar.hip."""
+batch ([778][B][C]); see csrc/sar.hip.  precise=True is the fp32 route (csrc/sar_f32.hip): fp32 weights, an fp32 workspace
+and the ``_f32`` entry points, deterministic and batch-invariant."""
 from __future__ import annotations
 
 from typing import Dict, Optional
@@ -73,34 +74,40 @@ _F16_KEYS = ("saigb_w", "xy.lap0", "xy.w0", "xy.lap1", "xy.w1", "z.lap0", "z.w0"
 
 
 class SarHeadEngine:
-    def __init__(self, net_sd: Dict[str, torch.Tensor], device="cuda"):
+    def __init__(self, net_sd: Dict[str, torch.Tensor], device="cuda", precise: bool = False):
         if not torch.cuda.is_available():
             raise L.HipLibraryError("SarHeadEngine needs an MI355X (HIP device); there is no CPU fallback")
         self.lib = L.load()
         self.device = torch.device(device)
-        self.w = {k: v.to(self.device, torch.float16 if k in _F16_KEYS else torch.float32).contiguous()
+        self.precise = bool(precise)
+        self.act_dtype = torch.float32 if self.precise else torch.float16          # features, g, mix and h
+        self.w = {k: v.to(self.device, torch.float16 if k in _F16_KEYS and not self.precise else torch.float32).contiguous()
                   for k, v in host_weights(net_sd).items()}
         self._ws: Dict[int, Dict[str, torch.Tensor]] = {}
+        f = "_f32" if self.precise else ""
+        self._saigb, self._mix, self._linear = (getattr(self.lib, n + f) for n in ("hm_sar_saigb", "hm_sar_graph_mix", "hm_sar_linear"))
 
     def _workspace(self, B: int) -> Dict[str, torch.Tensor]:
         ws = self._ws.get(B)
         if ws is None:
             e = dict(device=self.device)
-            ws = {"g": torch.empty(NV, B, KG, dtype=torch.float16, **e),
-                  "mix": torch.empty(NV, B * CELLS, dtype=torch.float16, **e),      # L . x of both layers (B * 544 fits too)
-                  "h": torch.empty(NV * B, CELLS, dtype=torch.float16, **e),
+            ad = self.act_dtype
+            ws = {"g": torch.empty(NV, B, KG, dtype=ad, **e),
+                  "mix": torch.empty(NV, B * CELLS, dtype=ad, **e),                  # L . x of both layers (B * 544 fits too)
+                  "h": torch.empty(NV * B, CELLS, dtype=ad, **e),
                   "xy": torch.empty(NT, B, CELLS, dtype=torch.float32, **e),
                   "z": torch.empty(NT, B, CELLS, dtype=torch.float32, **e)}
             self._ws = {B: ws}                                                       # keep one batch size's buffers
         return ws
 
     def saigb(self, feat: torch.Tensor) -> torch.Tensor:
-        """feat (B, 8, 8, 512) f16 NHWC -> the init graph [778][B][544] f16 (a view of the workspace)."""
+        """feat (B, 8, 8, 512) NHWC, f16 (fp32 when precise) -> the init graph [778][B][544] in the same dtype (a view of the
+        workspace)."""
         B = feat.shape[0]
-        assert feat.shape[1:] == (8, 8, 512) and feat.dtype == torch.float16 and feat.is_contiguous()
+        assert feat.shape[1:] == (8, 8, 512) and feat.dtype == self.act_dtype and feat.is_contiguous()
         g = self._workspace(B)["g"]
-        L.check(self.lib.hm_sar_saigb(L.ptr(feat), L.ptr(self.w["saigb_w"]), L.ptr(self.w["saigb_b"]), L.ptr(self.w["template"]),
-                                      L.ptr(g), B, L.current_stream()), "hm_sar_saigb")
+        L.check(self._saigb(L.ptr(feat), L.ptr(self.w["saigb_w"]), L.ptr(self.w["saigb_b"]), L.ptr(self.w["template"]),
+                            L.ptr(g), B, L.current_stream()), "hm_sar_saigb")
         return g
 
     def branch(self, g: torch.Tensor, br: str, out: torch.Tensor) -> torch.Tensor:
@@ -108,11 +115,10 @@ class SarHeadEngine:
         B = g.shape[1]
         ws, w, s = self._workspace(B), self.w, L.current_stream()
         mix, h = ws["mix"], ws["h"]
-        L.check(self.lib.hm_sar_graph_mix(L.ptr(w[br + ".lap0"]), LDL, L.ptr(g), B * KG, L.ptr(mix), s), "hm_sar_graph_mix")
-        L.check(self.lib.hm_sar_linear(L.ptr(mix), NV * B, KG, L.ptr(w[br + ".w0"]), L.ptr(w[br + ".b0"]), L.ptr(h), CELLS, 0, s),
-                "hm_sar_linear")
-        L.check(self.lib.hm_sar_graph_mix(L.ptr(w[br + ".lap1"]), LDL, L.ptr(h), B * CELLS, L.ptr(mix), s), "hm_sar_graph_mix")
-        L.check(self.lib.hm_sar_linear(L.ptr(mix), NV * B, CELLS, L.ptr(w[br + ".w1"]), L.ptr(w[br + ".b1"]), L.ptr(out), CELLS, 1, s),
+        L.check(self._mix(L.ptr(w[br + ".lap0"]), LDL, L.ptr(g), B * KG, L.ptr(mix), s), "hm_sar_graph_mix")
+        L.check(self._linear(L.ptr(mix), NV * B, KG, L.ptr(w[br + ".w0"]), L.ptr(w[br + ".b0"]), L.ptr(h), CELLS, 0, s), "hm_sar_linear")
+        L.check(self._mix(L.ptr(w[br + ".lap1"]), LDL, L.ptr(h), B * CELLS, L.ptr(mix), s), "hm_sar_graph_mix")
+        L.check(self._linear(L.ptr(mix), NV * B, CELLS, L.ptr(w[br + ".w1"]), L.ptr(w[br + ".b1"]), L.ptr(out), CELLS, 1, s),
                 "hm_sar_linear")
         return out
 
@@ -126,7 +132,8 @@ class SarHeadEngine:
         return coords
 
     def forward(self, feat: torch.Tensor) -> torch.Tensor:
-        """SARhead.forward (:213-222): feat (B, 8, 8, 512) f16 NHWC (RootNetEngine.features) -> coords (B, 799, 3) f32:
+        """SARhead.forward (:213-222): feat (B, 8, 8, 512) NHWC (RootNetEngine.features; f16, fp32 when precise) -> coords
+        (B, 799, 3) f32:
         normalised xy, relative z; rows 778 .. 798 are the joints."""
         B = feat.shape[0]
         g = self.saigb(feat)

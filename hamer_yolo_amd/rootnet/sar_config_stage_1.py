@@ -14,4 +14,5 @@ class rgb_opt:
     num_joints = 21
     depth_box = 0.3
     device = 'cuda'
+    precise = False                 # True: the fp32 route of the backbone, RootNet and the SAR head (d_infer --precise-rootnet)
     checkpoint = 'synthetic:0'      # the reference hard-codes /home/pt/fbs/model/rootnet/SAR-resnet34-Root.pth

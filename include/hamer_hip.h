@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
+#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
 
 enum { HM_DTYPE_BF16 = 0, HM_DTYPE_F16 = 1,
        HM_DTYPE_F32 = 2 /* the YOLOv7 detector path only (same value as HM_OUT_F32): see its section below */ };
@@ -525,6 +525,36 @@ typedef struct hm_sar_hand {
  * convert2origin_pixel(row 778) / (W // 2, H // 2) - 1, which for a left hand is NOT un-flipped: the reference's rule. */
 int hm_sar_postprocess(const float* coords, const hm_sar_hand* hands, const float* root, const float* depth, float* uvd,
                        float* xyz, int B, int P, void* stream);
+
+
+/* ---- The precise (fp32) route of the RootNet backbone, the depth head and the SAR head (EstimateRGB(cfg, precise=True)):
+ * the reference runs that network in fp32 (rootnet/Model_RGB.py:318-340).  Every product runs on the fp32-input MFMA and every
+ * output is bias + ONE sum over K in a fixed order: no split-K, no K groups, no batch-dependent reduction, so the route is
+ * deterministic and batch-invariant (a hand's numbers are the same bits alone and inside any batch).  These are additive
+ * entry points: hm_conv2d_nhwc keeps rejecting fp32 with ReLU or a residual, and hm_nchw3_to_nhwc8 / hm_gap_linear keep
+ * rejecting HM_DTYPE_F32.  hm_maxpool_nhwc (HM_DTYPE_F32), hm_sar_softargmax and hm_sar_postprocess (already fp32) serve both
+ * routes. */
+
+/* The ResNet-34 convolution in fp32 (conv_f32.hip's kernel with a ReLU / residual epilogue): dtype must be HM_DTYPE_F32, act 0
+ * or 2 (ReLU), out_f32 0; X, W, Y, bias fp32 with the layouts of hm_conv_args; optional resid [N][Hout][Wout][ldr] fp32 added
+ * before the ReLU (BasicBlock identity; ldr >= Cout).  Cin a power of two >= 8, X / W 16-byte aligned, ldx % 4 == 0; zeros and
+ * splitk_ws are not used.  Within ~1e-6 * sum|x * w| of exact. */
+int hm_conv2d_f32_relu(const hm_conv_args* args, void* stream);
+/* (B,3,H,W) f32 planes -> NHWC f32 with 8 channels (3 real, 5 zero); y 16-byte aligned. */
+int hm_nchw3_to_nhwc8_f32(const float* x, float* y, int B, int H, int W, void* stream);
+/* ResRootNet.forward_coord on fp32 features [B][HW][C]: per channel the HW positions summed in order, / HW, dot with w [C]
+ * in a fixed order, + bias, * k_value[b] -> depth [B] f32.  The order depends on HW and C only. */
+int hm_gap_linear_f32(const float* feat, int HW, int C, const float* w, float bias, const float* k_value, float* depth, int B,
+                      void* stream);
+/* hm_sar_saigb in fp32: feat [B][8][8][512], w [6224][512] (16-byte aligned), bias [6224], tmpl [778][3] -> g [778][B][544]. */
+int hm_sar_saigb_f32(const float* feat, const float* w, const float* bias, const float* tmpl, float* g, int B, void* stream);
+/* hm_sar_graph_mix in fp32: y [778][N] = lap [778][ldl] . x [778][N]; ldl >= 778, ldl % 4 == 0, columns 778 .. ldl-1 of lap
+ * zero; N % 4 == 0; lap / x 16-byte aligned.  Rows of x are never read past 778. */
+int hm_sar_graph_mix_f32(const float* lap, int ldl, const float* x, int N, float* y, void* stream);
+/* hm_sar_linear in fp32: y [M][N] = x [M][K] . w [N][K]^T + bias [N]; logits == 0: LeakyReLU(0.1), logits == 1: no
+ * activation (the second layer's logits, rows 0 .. 777 of hm_sar_softargmax's [799][B][1024] buffers).  K % 32 == 0
+ * (zero-padded columns in both operands); x / w 16-byte aligned. */
+int hm_sar_linear_f32(const float* x, int M, int K, const float* w, const float* bias, float* y, int N, int logits, void* stream);
 
 /* Optional per-launch timing (HIP events on the launch stream); kinds below. */
 enum { HM_K_GEMM = 0, HM_K_LAYERNORM = 1, HM_K_ATTENTION = 2, HM_K_IM2COL = 3, HM_K_LINEAR_F32 = 4,

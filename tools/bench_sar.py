@@ -2,7 +2,8 @@
 """Time the SAR hand-mesh head (SarHeadEngine.forward: SAIGB, both GBBMR branches, mesh2pose + soft-argmax) and the
 end-to-end estimator on prepared patches (ResNet-34 features + head + ResRootNet + post-process, what run_frames does after
 the crops) at B = 1 / 64 / 256 hands, synthetic weights.  Prints one JSON line per batch size with device milliseconds
-(median of --iters CUDA-event timings after --warmup) and the head's TFLOP/s."""
+(median of --iters CUDA-event timings after --warmup) and the head's TFLOP/s.  --precise times the fp32 route
+(EstimateRGB(cfg, precise=True)) instead and adds "route" and the backbone's TFLOP/s to each line."""
 import argparse
 import json
 import os
@@ -25,6 +26,18 @@ def head_flop_per_hand():
     return saigb + 2 * branch + 2 * 2 * 21 * NV * 1024
 
 
+def backbone_flop_per_hand():
+    """The ResNet-34 convolutions on a 256 x 256 patch (the 7x7 stem on the 8-channel image as the kernel runs it)."""
+    from hamer_yolo_amd.rootnet import arch
+    fl = 2 * 128 * 128 * 64 * 7 * 7 * 8
+    hw = 64
+    for _, cin, cout, s, ds in arch.blocks():
+        ho = hw // s
+        fl += 2 * ho * ho * cout * 9 * cin + 2 * ho * ho * cout * 9 * cout + (2 * ho * ho * cout * cin if ds else 0)
+        hw = ho
+    return fl
+
+
 def timed(fn, warmup, iters):
     for _ in range(warmup):
         fn()
@@ -44,11 +57,12 @@ def main():
     ap.add_argument("--batches", default="1,64,256")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--precise", action="store_true", help="time the fp32 route (backbone, RootNet and head in fp32)")
     a = ap.parse_args()
     dev = "cuda:0"
     net, root = synth.rootnet_state_dict(0)
-    bb = RootNetEngine(net, root, device=dev)
-    head = SarHeadEngine(synth.sar_head_state_dict(0), device=dev)
+    bb = RootNetEngine(net, root, device=dev, dtype=torch.float32 if a.precise else torch.float16)
+    head = SarHeadEngine(synth.sar_head_state_dict(0), device=dev, precise=a.precise)
     K = np.array([[906.96, 0, 960], [0, 906.79, 540], [0, 0, 1]])
     for B in [int(x) for x in a.batches.split(",")]:
         img = torch.randn(B, 3, 256, 256, device=dev)
@@ -63,9 +77,13 @@ def main():
         t_head = timed(lambda: head.forward(feat), a.warmup, a.iters)
         t_bb = timed(lambda: bb.features(img), a.warmup, a.iters)
         t_e2e = timed(e2e, a.warmup, a.iters)
-        print(json.dumps({"B": B, "head_ms": round(t_head, 4), "head_tflops": round(head_flop_per_hand() * B / t_head / 1e9, 1),
-                          "backbone_ms": round(t_bb, 4), "end_to_end_ms": round(t_e2e, 4),
-                          "head_gflop_per_hand": round(head_flop_per_hand() / 1e9, 2)}), flush=True)
+        rec = {"B": B, "head_ms": round(t_head, 4), "head_tflops": round(head_flop_per_hand() * B / t_head / 1e9, 1),
+               "backbone_ms": round(t_bb, 4), "end_to_end_ms": round(t_e2e, 4),
+               "head_gflop_per_hand": round(head_flop_per_hand() / 1e9, 2)}
+        if a.precise:
+            rec = {"route": "precise", **rec, "backbone_tflops": round(backbone_flop_per_hand() * B / t_bb / 1e9, 1),
+                   "backbone_gflop_per_hand": round(backbone_flop_per_hand() / 1e9, 2)}
+        print(json.dumps(rec), flush=True)
 
 
 if __name__ == "__main__":
