@@ -374,21 +374,22 @@ __device__ __forceinline__ void epilogue(const KArgs& g, f32x4_t (&acc)[NI][MI],
 // the groups kg > 0 hand their accumulators to group 0 through LDS (added in the order kg = 1, 2, ..: deterministic).
 // KDUAL (WK = 1): the SAME summation order in one group of waves -- even K tiles into one accumulator set, odd ones into a
 // second, added at the end -- so that a layer may run on either form, by launch size, with bit-identical results.
-template <class T, int EPI, int WM, int WN, int MI, int NI, int STAGES, bool CONV, int BK = 64, int SCHED = 0, int WK = 1, bool KDUAL = false, bool KSER = false>
+// MID_LOADS: the next tile's loads are issued between the two 32-deep sub-steps of a K-step (else in front of both), and the
+// MFMA runs are raised with s_setprio.
+template <class T, int EPI, int WM, int WN, int MI, int NI, int STAGES, bool CONV, bool MID_LOADS = false, int WK = 1, bool KDUAL = false, bool KSER = false>
 __global__ __launch_bounds__(64 * WM * WN * WK, WK > 1 ? 1 : 2) void gemm_tn_kernel(const KArgs g) {
   constexpr int NWG = WM * WN;                        // waves of one K group
   constexpr int NW = NWG * WK;
   constexpr int BM = WM * MI * 16, BN = WN * NI * 16;
-  constexpr int ROWB = BK * 2;                        // bytes per tile row in LDS (128 or 64)
+  constexpr int BK = 64;
+  constexpr int ROWB = BK * 2;                        // bytes per tile row in LDS
   constexpr int CH = BK / 8;                          // 16-byte chunks per row
   constexpr int RPI = 1024 / ROWB;                    // rows covered by one 1-KiB LDS-DMA instruction
   constexpr int XI = BM / NWG / RPI, WI = BN / NWG / RPI;   // staging instructions per wave and K-tile
-  static_assert(BK == 64 || BK == 32, "BK is 64 or 32");
-  static_assert(!CONV || BK == 64, "the implicit-GEMM loader is written for BK = 64");
   static_assert(BM % (NWG * RPI) == 0 && BN % (NWG * RPI) == 0, "tile rows must split into whole DMA pieces per wave");
-  static_assert(WK == 1 || (CONV && SCHED == 0), "K groups: written for the convolution flavour");
-  static_assert(!KDUAL || (WK == 1 && CONV && SCHED == 0), "the two-accumulator form is the one-group twin of WK = 2");
-  static_assert(!KSER || (WK == 1 && CONV && SCHED == 0 && EPI != HM_EPI_F32), "serial K ranges: the one-workgroup twin of split-K");
+  static_assert(WK == 1 || (CONV && !MID_LOADS), "K groups: written for the convolution flavour");
+  static_assert(!KDUAL || (WK == 1 && CONV && !MID_LOADS), "the two-accumulator form is the one-group twin of WK = 2");
+  static_assert(!KSER || (WK == 1 && CONV && !MID_LOADS && EPI != HM_EPI_F32), "serial K ranges: the one-workgroup twin of split-K");
   constexpr int XTILE_BYTES = BM * BK * 2, WTILE_BYTES = BN * BK * 2;
   constexpr int STAGE_BYTES = XTILE_BYTES + WTILE_BYTES;
   constexpr int LOADS = XI + WI;
@@ -411,16 +412,15 @@ __global__ __launch_bounds__(64 * WM * WN * WK, WK > 1 ? 1 : 2) void gemm_tn_ker
   const elem* __restrict__ W = (const elem*)g.W;
 
   // staging geometry: wave w loads X rows [XI*RPI*w, +XI*RPI) and W rows [WI*RPI*w, +WI*RPI); lane -> (row =
-  // lane / CH, physical 16-B chunk = lane % CH); logical chunk = physical ^ key(row) with key = row & 7 for
-  // 128-B rows and (row >> 2) & 3 for 64-B rows (4 rows share a 256-B bank row)
+  // lane / CH, physical 16-B chunk = lane % CH); logical chunk = physical ^ (row & 7)
   const int srow = lane / CH;
-  const int chunk = (lane % CH) ^ (BK == 64 ? (srow & 7) : ((srow >> 2) & 3));
+  const int chunk = (lane % CH) ^ (srow & 7);
   const elem* xsrc[XI];
   int pix_y[XI], pix_x[XI];
   const elem* wsrc[WI];
 #pragma unroll
   for (int i = 0; i < XI; ++i) {
-    int gm = (SCHED == 97 ? 0 : m0) + wave * XI * RPI + i * RPI + srow;     // (97: experiment, every tile reads panel 0)
+    int gm = m0 + wave * XI * RPI + i * RPI + srow;
     gm = gm < g.M ? gm : g.M - 1;                          // edge rows: valid memory, never stored
     if (CONV) {
       const int hw = g.Hout * g.Wout;
@@ -436,7 +436,7 @@ __global__ __launch_bounds__(64 * WM * WN * WK, WK > 1 ? 1 : 2) void gemm_tn_ker
   }
 #pragma unroll
   for (int i = 0; i < WI; ++i) {
-    int gn = (SCHED == 97 ? 0 : n0) + wave * WI * RPI + i * RPI + srow;
+    int gn = n0 + wave * WI * RPI + i * RPI + srow;
     gn = gn < g.N ? gn : g.N - 1;
     wsrc[i] = W + (size_t)gn * g.ldw + chunk * 8;
   }
@@ -472,7 +472,6 @@ __global__ __launch_bounds__(64 * WM * WN * WK, WK > 1 ? 1 : 2) void gemm_tn_ker
     s_kx = s_tap - s_ky * g.ksz;
   }
   auto stage = [&](int buf, int kt) {
-    if (SCHED == 93) return;                            // ablation: no global loads at all
     char* lx = smem + (kg * STAGES + buf) * STAGE_BYTES + wave * XI * 1024;
     char* lw = smem + (kg * STAGES + buf) * STAGE_BYTES + XTILE_BYTES + wave * WI * 1024;
     if (WK > 1) kt = kt * WK + kg;
@@ -515,10 +514,9 @@ __global__ __launch_bounds__(64 * WM * WN * WK, WK > 1 ? 1 : 2) void gemm_tn_ker
     for (int b = 0; b < MI; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   // fragment reads: row = tile_row + (lane&15); 16-B chunk = ks*4 + (lane>>4), swizzled with the staging key
-  const int frow = lane & 15, fsw = BK == 64 ? (lane & 7) : ((lane >> 2) & 3), fch = lane >> 4;
+  const int frow = lane & 15, fsw = lane & 7, fch = lane >> 4;
   // one K sub-step (32 deep): fragment reads + NI x MI MFMAs
   auto substep = [&](int buf, int ks, f32x4_t (&acc)[NI][MI]) {
-    if (SCHED == 92) return;                            // ablation: LDS-DMA fill only
     const char* lx = smem + (kg * STAGES + buf) * STAGE_BYTES;
     const char* lw = lx + XTILE_BYTES;
     const int coff = ((ks * 4 + fch) ^ fsw) * 16;
@@ -528,32 +526,12 @@ __global__ __launch_bounds__(64 * WM * WN * WK, WK > 1 ? 1 : 2) void gemm_tn_ker
     __builtin_amdgcn_sched_barrier(0);                 // X fragments first (round 4): the first MFMAs need W0 and all of X
 #pragma unroll
     for (int i = 0; i < NI; ++i) wf[i] = *(const vec8*)(lw + (wc * 16 * NI + i * 16 + frow) * ROWB + coff);
-    if (SCHED >= 1) __builtin_amdgcn_s_setprio(1);
-#ifdef HM_ABLATIONS
-    if constexpr (SCHED == 98) {
-      // timing ablation (WRONG results): the same fragment reads feeding HALF as many, twice as long MFMAs (32x32x16 instead of
-      // 16x16x32): is the K loop bound by vector-instruction ISSUE (an MFMA holds the issue port 8 cycles whatever its shape)?
-      typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-      static_assert(NI == 8 && MI == 4, "written for the 64 x 128 wave tile");
-      f32x16_t* a32 = (f32x16_t*)&acc[0][0];                // 8 accumulators of 16 registers over the same 128 registers
-#pragma unroll
-      for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-          for (int kk = 0; kk < 2; ++kk) {
-            if constexpr (std::is_same<T, TF16>::value) a32[nb * 2 + mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[nb * 2 + kk], xf[mb * 2 + kk], a32[nb * 2 + mb], 0, 0, 0);
-            else a32[nb * 2 + mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[nb * 2 + kk], xf[mb * 2 + kk], a32[nb * 2 + mb], 0, 0, 0);
-          }
-      __builtin_amdgcn_s_setprio(0);
-      return;
-    }
-#endif
+    if (MID_LOADS) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = T::mfma(wf[ni], xf[mi], acc[ni][mi]);
-    if (SCHED >= 1) __builtin_amdgcn_s_setprio(0);
+    if (MID_LOADS) __builtin_amdgcn_s_setprio(0);
   };
 
   // ---- K loop: ring of STAGES buffers, STAGES-1 tiles of LDS-DMA in flight across the barrier
@@ -587,13 +565,11 @@ __global__ __launch_bounds__(64 * WM * WN * WK, WK > 1 ? 1 : 2) void gemm_tn_ker
   int rd = 0, wrb = STAGES - 1;                        // ring slots: read tile kt, write tile kt+STAGES-1
   auto kstep = [&](int kt, f32x4_t (&acc)[NI][MI]) {
     // tile kt must have landed: in steady state the STAGES-2 newer tiles may still be in flight
-    if (SCHED != 94 && SCHED != 95) {                  // (ablations 94 / 95: nobody waits for the copies; 95: no barrier either)
-      if (kt + STAGES - 2 < nk) wait_vmcnt<LOADS * (STAGES - 2)>();
-      else wait_vmcnt<0>();
-    }
-    if (SCHED != 95) __builtin_amdgcn_s_barrier();     // everyone's tile kt landed; everyone is done reading slot wrb
+    if (kt + STAGES - 2 < nk) wait_vmcnt<LOADS * (STAGES - 2)>();
+    else wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();                      // everyone's tile kt landed; everyone is done reading slot wrb
     const bool more = kt + STAGES - 1 < nk;
-    if (SCHED <= 1) {                                  // loads first, then the whole tile
+    if (!MID_LOADS) {                                  // loads first, then the whole tile
       if (more) stage(wrb, kt + STAGES - 1);
 #pragma unroll
       for (int ks = 0; ks < BK / 32; ++ks) substep(rd, ks, acc);
@@ -689,13 +665,6 @@ __global__ __launch_bounds__(64 * WM * WN * WK, WK > 1 ? 1 : 2) void gemm_tn_ker
       for (int a = 0; a < NI; ++a)
 #pragma unroll
         for (int b = 0; b < MI; ++b) acc[a][b] += red[((((q - 1) * NWG + wave) * NI + a) * MI + b) * 64 + lane];
-  }
-  if (SCHED == 96 || SCHED == 98) {                     // ablation: no epilogue (keep the accumulators alive)
-#pragma unroll
-    for (int a = 0; a < NI; ++a)
-#pragma unroll
-      for (int b = 0; b < MI; ++b) asm volatile("" :: "v"(acc[a][b]));
-    return;
   }
   epilogue<T, EPI, MI, NI, true, SKB>(g, acc, m0 + wr * 16 * MI, n0 + wc * 16 * NI, lane, smem + wave * epi_stage_bytes(MI, NI, SKB),
                            rowstat + wr * 16 * MI, colvec + wc * 16 * NI, colvec + BN + wc * 16 * NI, split);
@@ -1165,119 +1134,6 @@ int launch_rin(const KArgs& g, hipStream_t s) {
   return hm_check_launch("hm_gemm");
 }
 
-#ifdef HM_ABLATIONS   // experiments live in the tools-only build (python -m hamer_yolo_amd.build --ablations), not in the product
-// ---------------------------------------------------------------------------------------------------------------
-// EXPERIMENT (variant 28): 256x160 tile with BOTH operands two K-steps ahead.  The 256x256 K loop runs at the latency of
-// its copies: W is requested one step before it is needed because a third 32 KB W slot does not fit beside three X slots
-// (160 KB).  A 256x160 tile (waves 4x2, each 64x80 = 4x5 MFMA tiles) fits three slots of each operand (96 + 60 KB), so
-// every copy has two full steps to land; it pays 27 % more operand bytes per flop.  Uses the generic epilogue.
-template <class T, int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_d2_kernel(const KArgs g) {
-  constexpr int WN = 2, MI = 4, NI = 5, NW = 8, BM = 256, BN = 160, ROWB = 128;
-  constexpr int XT = BM * ROWB, WT = BN * ROWB;                         // 32 KB, 20 KB
-  constexpr int XRING = 0, WRING = 3 * XT;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using vec8 = typename T::vec8;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
-  int tm, tn;
-  tile_coords(xcd_remap(blockIdx.x, gridDim.x), tiles_m, tiles_n, g.group_m, tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int wr = wave / WN, wc = wave % WN;
-  const char* X = (const char*)g.X;
-  const char* W = (const char*)g.W;
-  const int srow = lane >> 3, swz = (lane & 7) ^ (srow & 7);
-  const int nwp = wave < 4 ? 3 : 2;                                     // W pieces of this wave: 20 pieces over 8 waves
-  unsigned xoff[4], woff[3];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    int gm = m0 + wave * 32 + i * 8 + srow;
-    gm = gm < g.M ? gm : g.M - 1;
-    xoff[i] = (unsigned)gm * (unsigned)(g.ldx * 2) + swz * 16;
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    int gn = n0 + (wave + 8 * i) * 8 + srow;                            // piece p = wave + 8 i
-    gn = gn < g.N ? gn : g.N - 1;
-    woff[i] = (unsigned)gn * (unsigned)(g.ldw * 2) + swz * 16;
-  }
-  float bias_reg = 0.f;
-  if (g.bias) bias_reg = g.bias[min(n0 + (tid % BN), g.N - 1)];         // the oldest vector-memory operation: every wait below covers it
-  auto dma = [&](int slot, int kt) {
-    const char* xb = X + (size_t)kt * ROWB;
-    const char* wb = W + (size_t)kt * ROWB;
-    char* lx = smem + XRING + slot * XT + wave * 4 * 1024;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) glds16_hidden_s(xb, xoff[i], lx + i * 1024);
-    char* lw = smem + WRING + slot * WT;
-    glds16_hidden_s(wb, woff[0], lw + wave * 1024);
-    glds16_hidden_s(wb, woff[1], lw + (wave + 8) * 1024);
-    if (wave < 4) glds16_hidden_s(wb, woff[2], lw + (wave + 16) * 1024);
-  };
-  f32x4_t acc[NI][MI];
-#pragma unroll
-  for (int a = 0; a < NI; ++a)
-#pragma unroll
-    for (int b = 0; b < MI; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  const int frow = lane & 15, fsw = lane & 7, fch = lane >> 4;
-  auto substep = [&](int slot, int ks) {
-    const char* lx = smem + XRING + slot * XT;
-    const char* lw = smem + WRING + slot * WT;
-    const int coff = ((ks * 4 + fch) ^ fsw) * 16;
-    vec8 wf[NI], xf[MI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i) xf[i] = *(const vec8*)(lx + (wr * 16 * MI + i * 16 + frow) * ROWB + coff);
-    __builtin_amdgcn_sched_barrier(0);                 // X fragments first (round 4): the first MFMAs need W0 and all of X
-#pragma unroll
-    for (int i = 0; i < NI; ++i) wf[i] = *(const vec8*)(lw + (wc * 16 * NI + i * 16 + frow) * ROWB + coff);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = T::mfma(wf[ni], xf[mi], acc[ni][mi]);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  auto wait_step = [&](bool more) {                                     // all but the next step's copies (4 X + nwp W) have landed
-    if (!more) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (nwp == 3) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  };
-  const int nk = g.K / 64;
-  dma(0, 0);
-  if (nk > 1) dma(1, 1);
-  int slot = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    wait_step(kt + 1 < nk);
-    __builtin_amdgcn_s_barrier();                      // step kt complete in LDS; everyone is done reading step kt-1's slot
-    substep(slot, 0);
-    if (kt + 2 < nk) dma(slot == 0 ? 2 : slot - 1, kt + 2);            // (kt + 2) % 3 = the slot step kt-1 read
-    substep(slot, 1);
-    slot = slot == 2 ? 0 : slot + 1;
-  }
-  __builtin_amdgcn_s_barrier();
-  constexpr int EPI_BYTES = NW * epi_stage_bytes(MI, NI);
-  float2* rowstat = (float2*)(smem + EPI_BYTES);       // unused by these epilogues
-  float* colvec = (float*)(rowstat + BM);
-  if (tid < BN) colvec[tid] = bias_reg;
-  __builtin_amdgcn_s_barrier();
-  epilogue<T, EPI, MI, NI>(g, acc, m0 + wr * 16 * MI, n0 + wc * 16 * NI, lane, smem + wave * epi_stage_bytes(MI, NI),
-                           rowstat + wr * 16 * MI, colvec + wc * 16 * NI, colvec + BN + wc * 16 * NI, 0);
-}
-
-template <class T, int EPI>
-int launch_d2(const KArgs& g, hipStream_t s) {
-  constexpr int LDS = 3 * 256 * 128 + 3 * 160 * 128;                    // 159,744 B
-  auto kern = gemm_d2_kernel<T, EPI>;
-  static HmLdsOnce lds_once;
-  if (const int rc = lds_once.ensure((const void*)kern, LDS, "gemm: cannot raise the dynamic LDS limit")) return rc;
-  const int tiles = ((g.M + 255) / 256) * ((g.N + 159) / 160);
-  hipLaunchKernelGGL(kern, dim3(tiles), dim3(512), LDS, s, g);
-  return hm_check_launch("hm_gemm");
-}
-
-#endif  // HM_ABLATIONS (variant 28)
-
 // ---------------------------------------------------------------------------------------------------------------
 // Persistent form of gemm_x3_kernel for the 16-bit store epilogues (qkv, fc1, to_kv: 3-5 tiles per CU at B = 64).
 // Launched tile by tile, every tile pays its own start-up in series with everything else on its CU -- address set-up,
@@ -1297,23 +1153,14 @@ int launch_d2(const KArgs& g, hipStream_t s) {
 //   guarantees M, N multiples of 256), issued after the copies W(t+1), X(t+2) of the last step; the first step of the next
 //   tile therefore waits vmcnt(16 + 4): everything but those stores and X(t+2).  An extra vector-memory operation
 //   anywhere (a spill, the next tile's bias request) only makes a counted wait stricter, never looser.
-// DMAW (experiments library, variant 34): waves 0..3 issue ALL copies (their own rows and those of the wave that shares their
-// SIMD, wave + 4), waves 4..7 none -- does a SIMD whose second wave never stalls in copy issue keep its MFMA pipe fuller?
-// STAMP (experiments library, variant 35; a diagnostic build: in the product no stamp executes): wave 0 of every workgroup
-// records s_memtime (shader cycles) and s_memrealtime (100 MHz) around the kernel and around every tile's K loop into
-// g.ln_stats as [workgroup][6] uint64: {cycles, realtime ticks} of the whole kernel, {cycles, ticks, K-steps} of its K loops.
-// LEAN (round 4, the default; variant 36 of the experiments library compares it with the old form = LEAN false): the copies
-// through glds16_lean_s (LDS destinations as scalar byte offsets, M0 not saved / restored): -1.4 % per ViT block.
-// XFIRST (round 4, the default; variant 37 of the experiments library = the old order): the four X fragments of a sub-step are
-// read before the eight W fragments, so the first MFMAs (W0 x X0..3) issue behind five reads instead of nine and the remaining
-// W reads retire under them: -1.6 % per ViT block (profiles/r04_gemm_xfirst_ab.log).  Same MFMA order: same bytes.
-// R1EARLY (variant 38): the twelve fragment reads of the step's SECOND sub-step are issued in front of the step's copies instead of
-// behind them, so their latency passes under the copies' issue and the second run of MFMAs starts at once.
-// TWEAK (experiments): 1 = read order X0 W0 X1 X2 X3 W1.. (first MFMA behind two reads), 2 = no s_setprio around the MFMA runs.
-template <class T, int EPI, bool DIRECT = true, bool DMAW = false, bool STAMP = false, bool LEAN = true, bool XFIRST = true, bool R1EARLY = false, int TWEAK = 0>
+//   Round 4: the copies go through glds16_lean_s (LDS destinations as scalar byte offsets, M0 not saved / restored): -1.4 %
+//   per ViT block.  The four X fragments of a sub-step are read before the eight W fragments, so the first MFMAs (W0 x X0..3)
+//   issue behind five reads instead of nine and the remaining W reads retire under them: -1.6 % per ViT block
+//   (profiles/r04_gemm_xfirst_ab.log).  The MFMA runs are raised with s_setprio.  DESIGN.md section 4 has the alternatives
+//   measured against these.
+template <class T, int EPI, bool DIRECT = true>
 __global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) {
   static_assert(EPI == HM_EPI_STORE || EPI == HM_EPI_GELU || EPI == HM_EPI_SILU, "16-bit store epilogues only");
-  static_assert(!(DMAW && LEAN), "the loader-wave experiment was written against the round-3 copy issue");
   constexpr int WN = 2, MI = 4, NI = 8, ROWB = 128;
   constexpr int TILE_BYTES = 256 * ROWB;                               // 32 KB
   constexpr int XRING = 0, WRING = 3 * TILE_BYTES;
@@ -1331,8 +1178,6 @@ __global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) {
   const int run_lo = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq, run_len = tq + (xcd < tr ? 1 : 0);
   const int my = li < run_len ? (run_len - li + per - 1) / per : 0;
   if (my == 0) return;
-  unsigned long long st_c0 = 0, st_r0 = 0, st_kc = 0, st_kr = 0, st_kn = 0;
-  if constexpr (STAMP) { st_c0 = __builtin_amdgcn_s_memtime(); st_r0 = __builtin_amdgcn_s_memrealtime(); }
   const int nk = g.K / 64, S = my * nk;
   const int wr = wave / WN, wc = wave % WN;
   const char* X = (const char*)g.X;
@@ -1351,40 +1196,15 @@ __global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) {
   };
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   auto dma_x = [&](int slot, const char* base) {
-    if constexpr (DMAW) { if (wave >= 4) return; }
-    char* l = smem + XRING + slot * TILE_BYTES + wave * XI * 1024;
-    if constexpr (LEAN) {
-      const unsigned d = __builtin_amdgcn_readfirstlane(lds_base + XRING + slot * TILE_BYTES + wave * XI * 1024);
+    const unsigned d = __builtin_amdgcn_readfirstlane(XRING + slot * TILE_BYTES + wave * XI * 1024 + lds_base);
 #pragma unroll
-      for (int i = 0; i < XI; ++i) glds16_lean_s(base, xoff[i], d + i * 1024);
-      return;
-    }
-#pragma unroll
-    for (int i = 0; i < XI; ++i) glds16_hidden_s(base, xoff[i], l + i * 1024);
-    if constexpr (DMAW) {                                 // the rows of wave + 4: 4 * XI * 8 rows further on, same lane offsets
-      const char* b2 = base + (size_t)(4 * XI * 8) * g.ldx * 2;
-#pragma unroll
-      for (int i = 0; i < XI; ++i) glds16_hidden_s(b2, xoff[i], l + 4 * XI * 1024 + i * 1024);
-    }
+    for (int i = 0; i < XI; ++i) glds16_lean_s(base, xoff[i], d + i * 1024);
   };
   auto dma_w = [&](int slot, const char* base) {
-    if constexpr (DMAW) { if (wave >= 4) return; }
-    char* l = smem + WRING + slot * TILE_BYTES + wave * WI * 1024;
-    if constexpr (LEAN) {
-      const unsigned d = __builtin_amdgcn_readfirstlane(lds_base + WRING + slot * TILE_BYTES + wave * WI * 1024);
+    const unsigned d = __builtin_amdgcn_readfirstlane(WRING + slot * TILE_BYTES + wave * WI * 1024 + lds_base);
 #pragma unroll
-      for (int i = 0; i < WI; ++i) glds16_lean_s(base, woff[i], d + i * 1024);
-      return;
-    }
-#pragma unroll
-    for (int i = 0; i < WI; ++i) glds16_hidden_s(base, woff[i], l + i * 1024);
-    if constexpr (DMAW) {
-      const char* b2 = base + (size_t)(4 * WI * 8) * g.ldw * 2;
-#pragma unroll
-      for (int i = 0; i < WI; ++i) glds16_hidden_s(b2, woff[i], l + 4 * WI * 1024 + i * 1024);
-    }
+    for (int i = 0; i < WI; ++i) glds16_lean_s(base, woff[i], d + i * 1024);
   };
-  const bool dbl = DMAW && wave < 4;                       // this wave's copy groups are 8 pieces, not 4: the counted waits double
   // cursors over the concatenated step sequence: X runs two steps ahead of the MFMAs, W one
   int xti = 0, xkt = 0, wti = 0, wkt = 0, m0, n0;
   origin(0, m0, n0);
@@ -1410,47 +1230,11 @@ __global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) {
     const char* lw = smem + WRING + wslot * TILE_BYTES;
     const int coff = ((ks * 4 + fch) ^ fsw) * 16;
     vec8 wf[NI], xf[MI];
-    if constexpr (TWEAK == 1) {
-      xf[0] = *(const vec8*)(lx + (wr * 16 * MI + frow) * ROWB + coff);
-      __builtin_amdgcn_sched_barrier(0);
-      wf[0] = *(const vec8*)(lw + (wc * 16 * NI + frow) * ROWB + coff);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 1; i < MI; ++i) xf[i] = *(const vec8*)(lx + (wr * 16 * MI + i * 16 + frow) * ROWB + coff);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 1; i < NI; ++i) wf[i] = *(const vec8*)(lw + (wc * 16 * NI + i * 16 + frow) * ROWB + coff);
-    } else {
-    if constexpr (XFIRST) {
-#pragma unroll
-      for (int i = 0; i < MI; ++i) xf[i] = *(const vec8*)(lx + (wr * 16 * MI + i * 16 + frow) * ROWB + coff);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int i = 0; i < NI; ++i) wf[i] = *(const vec8*)(lw + (wc * 16 * NI + i * 16 + frow) * ROWB + coff);
-    if constexpr (!XFIRST) {
-#pragma unroll
-      for (int i = 0; i < MI; ++i) xf[i] = *(const vec8*)(lx + (wr * 16 * MI + i * 16 + frow) * ROWB + coff);
-    }
-    }
-    if constexpr (TWEAK != 2) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = T::mfma(wf[ni], xf[mi], acc[ni][mi]);
-    if constexpr (TWEAK != 2) __builtin_amdgcn_s_setprio(0);
-  };
-  auto frag_reads = [&](int xslot, int wslot, int ks, vec8 (&wf)[NI], vec8 (&xf)[MI]) {
-    const char* lx = smem + XRING + xslot * TILE_BYTES;
-    const char* lw = smem + WRING + wslot * TILE_BYTES;
-    const int coff = ((ks * 4 + fch) ^ fsw) * 16;
 #pragma unroll
     for (int i = 0; i < MI; ++i) xf[i] = *(const vec8*)(lx + (wr * 16 * MI + i * 16 + frow) * ROWB + coff);
-    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);                 // X fragments first
 #pragma unroll
     for (int i = 0; i < NI; ++i) wf[i] = *(const vec8*)(lw + (wc * 16 * NI + i * 16 + frow) * ROWB + coff);
-  };
-  auto frag_mfmas = [&](const vec8 (&wf)[NI], const vec8 (&xf)[MI]) {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni)
@@ -1463,8 +1247,7 @@ __global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) {
   dma_x(0, xbase); next_x();
   dma_w(0, wbase); next_w();
   dma_x(1, xbase + (size_t)xkt * ROWB); next_x();
-  if (dbl) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
 
   int gs = 0, xs = 0;                                  // global step, its X slot (gs % 3); W slot = gs & 1
   for (int ti = 0; ti < my; ++ti) {
@@ -1486,46 +1269,26 @@ __global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) {
 #pragma unroll
       for (int b = 0; b < MI; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     int xs_last = 0, ws_last = 0;
-    unsigned long long st_a = 0, st_b = 0;
-    if constexpr (STAMP) { st_a = __builtin_amdgcn_s_memtime(); st_b = __builtin_amdgcn_s_memrealtime(); }
     for (int kt = 0; kt < nk; ++kt, ++gs) {
       if (gs > 0) {
-        if (kt == 0) { if (dbl) asm volatile("s_waitcnt vmcnt(26)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(22)" ::: "memory"); }   // 16 epilogue stores + X(gs+1) + the 2 bias loads may stay in flight
-        else if (gs + 1 < S) { if (dbl) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }   // X(gs+1)
+        if (kt == 0) asm volatile("s_waitcnt vmcnt(22)" ::: "memory");   // 16 epilogue stores + X(gs+1) + the 2 bias loads may stay in flight
+        else if (gs + 1 < S) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // X(gs+1)
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       __builtin_amdgcn_s_barrier();                    // step gs complete in LDS; everyone is done with step gs-1's slots (and epilogue)
       const int ws = gs & 1, xs2 = xs == 0 ? 2 : xs - 1;
-      if constexpr (R1EARLY) {
-        vec8 wf1[NI], xf1[MI];
-        substep(xs, ws, 0);
-        frag_reads(xs, ws, 1, wf1, xf1);
-        if (gs + 1 < S) { dma_w(ws ^ 1, wbase + (size_t)wkt * ROWB); next_w(); }
-        if (gs + 2 < S) { dma_x(xs2, xbase + (size_t)xkt * ROWB); next_x(); }
-        frag_mfmas(wf1, xf1);
-      } else {
       substep(xs, ws, 0);
       if (gs + 1 < S) { dma_w(ws ^ 1, wbase + (size_t)wkt * ROWB); next_w(); }   // W first, then X: the counted waits rely on this order
       if (gs + 2 < S) { dma_x(xs2, xbase + (size_t)xkt * ROWB); next_x(); }
       substep(xs, ws, 1);
-      }
       xs_last = xs; ws_last = ws;
       xs = xs == 2 ? 0 : xs + 1;
-    }
-    if constexpr (STAMP) {
-      st_kc += __builtin_amdgcn_s_memtime() - st_a; st_kr += __builtin_amdgcn_s_memrealtime() - st_b; st_kn += nk;
-      if (ti + 1 == my && tid == 0) {                  // (the last tile's epilogue is not inside the kernel figure: stamped before it)
-        unsigned long long* o = (unsigned long long*)g.ln_stats + (size_t)blockIdx.x * 6;
-        o[0] = __builtin_amdgcn_s_memtime() - st_c0; o[1] = __builtin_amdgcn_s_memrealtime() - st_r0;
-        o[2] = st_kc; o[3] = st_kr; o[4] = st_kn; o[5] = my;
-      }
     }
     __builtin_amdgcn_s_barrier();                      // the last step's two slots are free: epilogue staging
     // The bias pair landed long ago (the wait of step kt == 1 retired it; >= 16 copies were issued behind it).  This statement
     // is its fence: at most 12 operations are in flight here (X(gs+1), W(gs+1), X(gs+2)), so it never stalls, and it names the
     // two registers as read-write operands -- no use, copy or spill of them can be scheduled above it.
-    if constexpr (DMAW) asm volatile("s_waitcnt vmcnt(24)" : "+v"(bias_lo), "+v"(bias_hi) :: "memory");
-    else asm volatile("s_waitcnt vmcnt(12)" : "+v"(bias_lo), "+v"(bias_hi) :: "memory");
+    asm volatile("s_waitcnt vmcnt(12)" : "+v"(bias_lo), "+v"(bias_hi) :: "memory");
 
     // ---- epilogue: 64 x 128 per wave = 4 column groups of 32 x 2 half-strips of 32 rows, each through 4 KB of LDS (all
     // eight waves inside the last step's X slot; the wave's 128 bias values wait in 512 B of the last step's W slot).
@@ -1612,339 +1375,6 @@ __global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) {
   }
 }
 
-#ifdef HM_ABLATIONS
-// ---------------------------------------------------------------------------------------------------------------
-// Round 4 EXPERIMENT (experiments library only, -DHM_ABLATIONS; tests opt-in): gemm_px_kernel with a SOFTWARE-PIPELINED K loop
-// (variant 27, gemm_pp_kernel; 33 = the same with the copies of waves 4..7 issued four groups after those of waves 0..3).
-// Bit-identical to variant 26 and NOT faster: interleaved A/B on one box (profiles/r04_gemm_pipelined_ab.log), store epilogue,
-// B = 64: qkv 122.0 us (26) / 123.2 (27) / 132.4 (33), fc1 144.1 / 147.7 / 154.2, fc2 130.9 / 135.4 / 140.0, kv 172.6 / 178.6 /
-// 184.4 -- the reasoning below (which the loop's ISA confirms: no MFMA waits for a fragment any more) predicted a third off the
-// K loop; the measurement says the fragment reads were never what the loop waited for.  With rounds 1-3 (ring depth, tile
-// shapes, wave counts, stagger, no-wait ablations) every structure lands on ~1.5 us per K-step on random operands: the guide's
-// own 256 x 256 template rate, and the rate at which the chip holds its clock down under MFMA + LDS-DMA load (DVFS give-back).
-// What the px / x3 loops do per K-step and wave, as hipcc emits them: [barrier] 12 ds_read_b128, lgkmcnt(3..0), 32 MFMAs,
-// 8 copies, 12 ds_read_b128, wait, 32 MFMAs.  All eight waves leave the barrier together, so all of them read while both
-// MFMA pipes of every SIMD idle, then all of them multiply while the LDS idles: 2 x (96 reads x 4 cycles + latency) + 2 x 1024
-// MFMA cycles per SIMD = ~3050 cycles per step where the MFMAs alone need 2048 (v_mfma 16x16x32: 16 cycles, 64 per wave, two
-// waves per SIMD) -- the 1.5 us per step that every tile structure of rounds 1-3 landed on.  Here the fragment reads never
-// wait in front of the MFMAs that use them:
-//   * a K-step is 16 GROUPS of 4 MFMAs (ks = g >> 3, ni = g & 7: W fragment (ks, ni) against the four X fragments of ks);
-//   * fragment reads are issued from inline asm FIVE groups ahead of their use (W: an 8-entry register ring, slot = ni; X: two
-//     sets of four, one per ks) and waited for by COUNT (LDS operations retire in order; the counts are derived below);
-//   * the step's barrier moves from its top to group 12: by then every read of the step has been issued and is retired by one
-//     lgkmcnt(0), so after the barrier the step's LDS slots are free -- the copies W(t+2), X(t+3) go out there, two pieces per
-//     group over groups 12..15, and the first fragments of step t+1 (whose copies the same wait + barrier have completed) are
-//     requested under the last 16 MFMAs of step t.  W therefore runs TWO steps ahead as well (px: one), in the same two slots.
-//   * last step of a tile: no reads and no copies behind the barrier; after the epilogue (which stages through this wave's own
-//     4 KB of the step's X slot and keeps its bias in its own 4 KB of the W slot -- exactly the regions this wave's next copies
-//     overwrite) the copies, the next tile's bias request and its first nine reads are issued in the order the steady state
-//     uses, so every group's wait count is the same in every step.
-// Read stream of a step (L_g = reads issued in front of group g) and the count each group waits with (reads issued after the
-// last one it needs, through L_g):
-//   L0 W5 | L1 W6 | L2 W7 X1a | L3 W8 X1b | L4 W9 X1c | L5 W10 X1d | L6 W11 | L7 W12 | L8 W13 | L9 W14 | L10 W15 | L11 - |
-//   [lgkmcnt(0) vmcnt barrier] L12 nW0 nW1 nX0a | L13 nW2 nX0b nX0c | L14 nW3 nX0d | L15 nW4
-//   g0 2 (needs nX0d) | g1 9 | g2 9 | g3 8 | g4 8 | g5 9 | g6 9 | g7 9 | g8 3 (needs X1d) | g9 7 | g10 6 | g11 4 | g12 3 | g13 6 | g14 8 | g15 9
-// vmcnt: copies retire in issue order: W then X, always.  At group 12 of step t everything but X(t+2) must have landed:
-// vmcnt(4); in the first step of a tile the tile's two bias loads are younger than X(t+2): vmcnt(6); vmcnt(0) once no X(t+2)
-// exists.  The epilogue's 16 stores are older than the copies issued behind it and retire with them.
-constexpr int pp_wait_count(int g) {
-  constexpr int c[16] = {2, 9, 9, 8, 8, 9, 9, 9, 3, 7, 6, 4, 3, 6, 8, 9};
-  return c[g];
-}
-
-template <class T, int EPI, bool DIRECT = true, bool STAG = false>   // STAG: waves 4..7 issue a step's copies four groups later than waves 0..3 (groups 0..3 of the next step)
-__global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const KArgs g) {
-  static_assert(EPI == HM_EPI_STORE || EPI == HM_EPI_GELU, "16-bit store epilogues only");
-  constexpr int WN = 2, MI = 4, NI = 8, ROWB = 128;
-  constexpr int TILE_BYTES = 256 * ROWB;                               // 32 KB
-  constexpr int XRING = 0, WRING = 3 * TILE_BYTES;
-  constexpr int XI = 4, WI = 4;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using vec8 = typename T::vec8;
-  using elem = typename T::elem;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tiles_n = g.N >> 8, tiles_m = g.M >> 8, tiles = tiles_m * tiles_n;
-  const int G = gridDim.x, xcd = blockIdx.x & 7, li = blockIdx.x >> 3, per = G >> 3;
-  const int tq = tiles >> 3, tr = tiles & 7;
-  const int run_lo = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq, run_len = tq + (xcd < tr ? 1 : 0);
-  const int my = li < run_len ? (run_len - li + per - 1) / per : 0;
-  if (my == 0) return;
-  const int nk = g.K / 64, S = my * nk;
-  const int wr = wave / WN, wc = wave % WN;
-  const char* X = (const char*)g.X;
-  const char* W = (const char*)g.W;
-
-  const int srow = lane >> 3, swz = (lane & 7) ^ (srow & 7);
-  // lane part of a copy's source address (piece 0 of this wave); the piece index and the tile origin ride in the scalar base
-  const unsigned xoff0 = (unsigned)(wave * XI * 8 + srow) * (unsigned)(g.ldx * 2) + swz * 16;
-  const unsigned woff0 = (unsigned)(wave * WI * 8 + srow) * (unsigned)(g.ldw * 2) + swz * 16;
-  const size_t xpiece = (size_t)8 * g.ldx * 2, wpiece = (size_t)8 * g.ldw * 2;
-  auto origin = [&](int ti, int& m0, int& n0) {
-    int tm, tn;
-    tile_coords(run_lo + li + ti * per, tiles_m, tiles_n, g.group_m, tm, tn);
-    m0 = tm << 8; n0 = tn << 8;
-  };
-  // cursors over the concatenated step sequence: W runs two steps ahead of the MFMAs, X three (one copy cursor each)
-  int xti = 0, xkt = 0, wti = 0, wkt = 0, m0, n0;
-  origin(0, m0, n0);
-  const char* xbase = X + (size_t)m0 * g.ldx * 2;
-  const char* wbase = W + (size_t)n0 * g.ldw * 2;
-  auto next_x = [&]() {
-    if (++xkt == nk) {
-      xkt = 0;
-      if (++xti < my) { int a, b; origin(xti, a, b); xbase = X + (size_t)a * g.ldx * 2; }
-    }
-  };
-  auto next_w = [&]() {
-    if (++wkt == nk) {
-      wkt = 0;
-      if (++wti < my) { int a, b; origin(wti, a, b); wbase = W + (size_t)b * g.ldw * 2; }
-    }
-  };
-  auto piece_x = [&](int slot, int i) {
-    glds16_hidden_s(xbase + (size_t)xkt * ROWB + i * xpiece, xoff0, smem + XRING + slot * TILE_BYTES + wave * XI * 1024 + i * 1024);
-  };
-  auto piece_w = [&](int slot, int i) {
-    glds16_hidden_s(wbase + (size_t)wkt * ROWB + i * wpiece, woff0, smem + WRING + slot * TILE_BYTES + wave * WI * 1024 + i * 1024);
-  };
-
-  // fragment read addresses: X (ks, mi) = X slot + lx[ks] + mi * 2048, W (ks, ni) = W slot + lw[ks] + ni * 2048 (immediates)
-  const int frow = lane & 15, fsw = lane & 7, fch = lane >> 4;
-  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  unsigned lx[2], lw[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    lx[ks] = lds0 + XRING + (unsigned)((wr * 16 * MI + frow) * ROWB + (((ks * 4 + fch) ^ fsw) << 4));
-    lw[ks] = lds0 + WRING + (unsigned)((wc * 16 * NI + frow) * ROWB + (((ks * 4 + fch) ^ fsw) << 4));
-  }
-
-  f32x4_t acc[NI][MI];
-  vec8 wf[NI], xf[2][MI];
-#define PP_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-  // the nine reads that open a step, in the order the steady state issues them behind its barrier (nW0 nW1 nX0a | nW2 nX0b nX0c
-  // | nW3 nX0d | nW4): part 0..3 = what groups 12..15 of the previous step carry
-  auto open_reads = [&](auto part, unsigned ax0, unsigned aw0) {
-    constexpr int P = decltype(part)::value;
-    if constexpr (P == 0) { PP_RD(wf[0], aw0, 0); PP_RD(wf[1], aw0, 2048); PP_RD(xf[0][0], ax0, 0); }
-    if constexpr (P == 1) { PP_RD(wf[2], aw0, 4096); PP_RD(xf[0][1], ax0, 2048); PP_RD(xf[0][2], ax0, 4096); }
-    if constexpr (P == 2) { PP_RD(wf[3], aw0, 6144); PP_RD(xf[0][3], ax0, 6144); }
-    if constexpr (P == 3) { PP_RD(wf[4], aw0, 8192); }
-  };
-
-  // prologue: X(0), W(0), X(1) -> wait for the first two -> barrier -> W(1), X(2) -> bias request -> the first nine reads
-  int gs = 0, xs = 0;                                  // global step, its X slot (gs % 3); W slot = gs & 1
-#pragma unroll
-  for (int i = 0; i < XI; ++i) piece_x(0, i);
-  next_x();
-#pragma unroll
-  for (int i = 0; i < WI; ++i) piece_w(0, i);
-  next_w();
-#pragma unroll
-  for (int i = 0; i < XI; ++i) piece_x(1, i);
-  next_x();
-  asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  if (1 < S) {
-#pragma unroll
-    for (int i = 0; i < WI; ++i) piece_w(1, i);
-    next_w();
-  }
-  if (2 < S) {
-#pragma unroll
-    for (int i = 0; i < XI; ++i) piece_x(2, i);
-    next_x();
-  }
-
-  for (int ti = 0; ti < my; ++ti) {
-    if (ti > 0) origin(ti, m0, n0);
-    // this wave's 128 bias values, two per lane (see gemm_px_kernel): always issued, from asm, fenced in front of the epilogue
-    float bias_lo, bias_hi;
-    {
-      const float* bsrc = g.bias ? g.bias + n0 + wc * 128 : (const float*)g.W;
-      asm volatile("global_load_dword %0, %2, %3\n\tglobal_load_dword %1, %2, %3 offset:256"
-                   : "=&v"(bias_lo), "=&v"(bias_hi) : "v"(lane * 4), "s"(bsrc) : "memory");
-    }
-    {
-      const unsigned ax0 = lx[0] + (unsigned)(xs * TILE_BYTES), aw0 = lw[0] + (unsigned)((gs & 1) * TILE_BYTES);
-      open_reads(std::integral_constant<int, 0>{}, ax0, aw0); open_reads(std::integral_constant<int, 1>{}, ax0, aw0);
-      open_reads(std::integral_constant<int, 2>{}, ax0, aw0); open_reads(std::integral_constant<int, 3>{}, ax0, aw0);
-    }
-#pragma unroll
-    for (int a = 0; a < NI; ++a)
-#pragma unroll
-      for (int b = 0; b < MI; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    int xs_last = 0, ws_last = 0;
-    // one K-step; `last` (the tile's last step) is a compile-time property: behind its barrier there are no reads and no copies,
-    // and a runtime branch around asm statements that define fragment registers costs register copies in every group
-    auto step = [&](auto last_c, const int kt) {
-      constexpr bool last = decltype(last_c)::value;
-      const int ws = gs & 1;
-      const unsigned ax1 = lx[1] + (unsigned)(xs * TILE_BYTES);
-      const unsigned aw0 = lw[0] + (unsigned)(ws * TILE_BYTES), aw1 = lw[1] + (unsigned)(ws * TILE_BYTES);
-      const int xsn = xs == 2 ? 0 : xs + 1;
-      const unsigned nax0 = lx[0] + (unsigned)(xsn * TILE_BYTES), naw0 = lw[0] + (unsigned)((ws ^ 1) * TILE_BYTES);
-      auto group = [&](auto gc) {
-        constexpr int GI = decltype(gc)::value, ks = GI >> 3, ni = GI & 7;
-        // ---- reads (and, behind the barrier, copies) issued in front of this group
-        if constexpr (GI <= 10) {                                     // W fragment five groups on (same step)
-          constexpr int j = GI + 5, jks = j >> 3, jni = j & 7;
-          if constexpr (jks == 0) PP_RD(wf[jni], aw0, jni * 2048); else PP_RD(wf[jni], aw1, jni * 2048);
-        }
-        if constexpr (GI >= 2 && GI <= 5) PP_RD(xf[1][GI - 2], ax1, (GI - 2) * 2048);     // X fragments of ks = 1
-        if constexpr (GI == 12) {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         // every fragment read of this step has returned
-          if (gs + 1 < S) {
-            if (gs + 2 >= S) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (kt == 0) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // X(gs+2) and the tile's bias pair may stay in flight
-            else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                   // X(gs+2)
-          }
-          __builtin_amdgcn_s_barrier();      // step gs+1 complete in LDS; nobody reads step gs's slots any more
-        }
-        if constexpr (GI >= 12) {
-          if constexpr (!last) {
-            // copies into the slots this step just gave up: W(gs+2) -> its W slot, X(gs+3) -> its X slot; two pieces per group
-            if (!STAG || wave < 4) {
-              if constexpr (GI == 12 || GI == 13) {
-                if (gs + 2 < S) { piece_w(ws, 2 * (GI - 12)); piece_w(ws, 2 * (GI - 12) + 1); if constexpr (GI == 13) next_w(); }
-              } else {
-                if (gs + 3 < S) { piece_x(xs, 2 * (GI - 14)); piece_x(xs, 2 * (GI - 14) + 1); if constexpr (GI == 15) next_x(); }
-              }
-            }
-            open_reads(std::integral_constant<int, GI - 12>{}, nax0, naw0);     // the first fragments of step gs + 1
-          }
-        }
-        if constexpr (STAG && GI <= 3) {
-          // waves 4..7: the copies of the step before this one (its barrier has passed), unless that step was a tile's last
-          // (kt == 0: everyone issued those behind the epilogue).  Same issue order per wave, so the counted waits do not change.
-          if (wave >= 4 && kt > 0) {
-            const int wprev = ws ^ 1, xprev = xs == 0 ? 2 : xs - 1;
-            if constexpr (GI <= 1) {
-              if (gs + 1 < S) { piece_w(wprev, 2 * GI); piece_w(wprev, 2 * GI + 1); if constexpr (GI == 1) next_w(); }
-            } else {
-              if (gs + 2 < S) { piece_x(xprev, 2 * (GI - 2)); piece_x(xprev, 2 * (GI - 2) + 1); if constexpr (GI == 3) next_x(); }
-            }
-          }
-        }
-        // ---- wait for this group's fragments by count, naming them so that no MFMA below can move above the wait
-        {
-          vec8 &w = wf[ni], &x0 = xf[ks][0], &x1 = xf[ks][1], &x2 = xf[ks][2], &x3 = xf[ks][3];
-          if constexpr (ni == 0) {                                    // the group that opens a sub-step also releases its X set
-            asm volatile("s_waitcnt lgkmcnt(%5)" : "+v"(w), "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3) : "n"(pp_wait_count(GI)));
-          } else if constexpr (GI >= 12 && last) {
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(w));
-          } else {
-            asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(w) : "n"(pp_wait_count(GI)));
-          }
-        }
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = T::mfma(wf[ni], xf[ks][mi], acc[ni][mi]);
-      };
-      group(std::integral_constant<int, 0>{}); group(std::integral_constant<int, 1>{}); group(std::integral_constant<int, 2>{});
-      group(std::integral_constant<int, 3>{}); group(std::integral_constant<int, 4>{}); group(std::integral_constant<int, 5>{});
-      group(std::integral_constant<int, 6>{}); group(std::integral_constant<int, 7>{}); group(std::integral_constant<int, 8>{});
-      group(std::integral_constant<int, 9>{}); group(std::integral_constant<int, 10>{}); group(std::integral_constant<int, 11>{});
-      group(std::integral_constant<int, 12>{}); group(std::integral_constant<int, 13>{}); group(std::integral_constant<int, 14>{});
-      group(std::integral_constant<int, 15>{});
-      xs_last = xs; ws_last = ws;
-      xs = xsn;
-      ++gs;
-    };
-    for (int kt = 0; kt + 1 < nk; ++kt) step(std::false_type{}, kt);
-    step(std::true_type{}, nk - 1);
-    // (no barrier here: the one at group 12 of the last step already separates every wave's last reads of these slots from the
-    // staging below.)  Fence of the bias pair, as in gemm_px_kernel: at most 8 copies are in flight, so it never stalls.
-    asm volatile("s_waitcnt vmcnt(12)" : "+v"(bias_lo), "+v"(bias_hi) :: "memory");
-
-    // ---- epilogue (gemm_px_kernel's, with the bias in THIS wave's 4 KB of the last step's W slot)
-    // (the epilogue's lane constants are re-derived from an opaque copy of the lane id: hoisted out of the tile loop they would
-    //  live through the K loop, whose 192 accumulator + fragment registers leave no room -- hipcc spilled two of them)
-    int elane = lane;
-    asm volatile("" : "+v"(elane));
-    float* cb = (float*)(smem + WRING + ws_last * TILE_BYTES + wave * 4096);
-    cb[elane] = g.bias ? bias_lo : 0.f; cb[64 + elane] = g.bias ? bias_hi : 0.f;
-    char* wl = smem + XRING + xs_last * TILE_BYTES + wave * 4096;
-    const int arow = elane & 15, apiece = elane >> 4, row0 = elane >> 2, j = elane & 3;
-    const int mb = m0 + wr * 64, nb = n0 + wc * 128;
-    if constexpr (DIRECT) {
-      const int g4 = elane >> 4;
-      typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-      typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-      f32x4_t bv[NI];
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) bv[ni] = *(const f32x4_t*)(cb + ni * 16 + 4 * g4);
-      elem* crow = (elem*)g.C + (size_t)(mb + arow) * g.ldc + nb + (g4 & 1) * 16 + (g4 >> 1) * 8;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int np = 0; np < NI / 2; ++np) {
-          unsigned pk[2][2];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const f32x4_t a = acc[2 * np + h][mi], bb = bv[2 * np + h];
-            float v0 = __fadd_rn(a[0], bb[0]), v1 = __fadd_rn(a[1], bb[1]), v2 = __fadd_rn(a[2], bb[2]), v3 = __fadd_rn(a[3], bb[3]);
-            if constexpr (EPI == HM_EPI_GELU) {
-              const f32x2_t g0 = gelu_fast2(f32x2_t{v0, v1}), g1 = gelu_fast2(f32x2_t{v2, v3});
-              v0 = g0[0] * g.out_scale; v1 = g0[1] * g.out_scale; v2 = g1[0] * g.out_scale; v3 = g1[1] * g.out_scale;
-            }
-            typename T::vec4 o;
-            o[0] = (elem)v0; o[1] = (elem)v1; o[2] = (elem)v2; o[3] = (elem)v3;
-            const u32x2 w = __builtin_bit_cast(u32x2, o);
-            pk[h][0] = w[0]; pk[h][1] = w[1];
-          }
-          const u32x2 s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
-          const u32x2 s1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
-          *(u32x4*)(crow + (size_t)(mi * 16) * g.ldc + np * 32) = u32x4{s0[0], s1[0], s0[1], s1[1]};
-        }
-    } else {
-#pragma unroll
-      for (int cg = 0; cg < 4; ++cg) {
-        const f32x4_t b0 = *(const f32x4_t*)(cb + cg * 32 + 8 * j), b1 = *(const f32x4_t*)(cb + cg * 32 + 8 * j + 4);
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-#pragma unroll
-          for (int nl = 0; nl < 2; ++nl)
-#pragma unroll
-            for (int mm = 0; mm < 2; ++mm) {
-              const int row = mm * 16 + arow;
-              *(f32x4_t*)(wl + row * 128 + (((nl * 4 + apiece) ^ (row & 7)) << 4)) = acc[cg * 2 + nl][half * 2 + mm];
-            }
-#pragma unroll
-          for (int it = 0; it < 2; ++it) {
-            const int row = it * 16 + row0, sw = row & 7;
-            const f32x4_t v0 = *(const f32x4_t*)(wl + row * 128 + (((2 * j) ^ sw) << 4));
-            const f32x4_t v1 = *(const f32x4_t*)(wl + row * 128 + (((2 * j + 1) ^ sw) << 4));
-            vec8 o;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              float a = __fadd_rn(v0[q], b0[q]), b = __fadd_rn(v1[q], b1[q]);
-              if constexpr (EPI == HM_EPI_GELU) { const f32x2_t gq = gelu_fast2(f32x2_t{a, b}); a = gq[0] * g.out_scale; b = gq[1] * g.out_scale; }
-              o[q] = (elem)a; o[4 + q] = (elem)b;
-            }
-            *(vec8*)((elem*)g.C + (size_t)(mb + half * 32 + row) * g.ldc + nb + cg * 32 + 8 * j) = o;
-          }
-        }
-      }
-    }
-    // the copies the last step held back: W(gs+1) .. wait: gs already counts the next step.  W(gs + 1), X(gs + 2) in the numbering
-    // of the step that just ended + 1: the slots of the tile's last step (ws_last, xs_last), whose staging this wave has finished
-    // (its LDS reads returned before the stores that carry their data were issued)
-    if (gs + 1 < S) {
-#pragma unroll
-      for (int i = 0; i < WI; ++i) piece_w(ws_last, i);
-      next_w();
-    }
-    if (gs + 2 < S) {
-#pragma unroll
-      for (int i = 0; i < XI; ++i) piece_x(xs_last, i);
-      next_x();
-    }
-  }
-#undef PP_RD
-}
-
-#endif  // HM_ABLATIONS (variants 27 / 33)
-
 // Default persistent grid: one workgroup per CU on all but ONE CU of every XCD (248 of 256; see launch_px), unless all 256 save
 // a whole round of tiles (1020 tiles = fc1 at 68 hands: 4 rounds instead of 5).
 int px_default_grid(int tiles, int cus) {
@@ -1976,7 +1406,7 @@ int px_grid_for(int tiles, int cus) {
 }
 extern "C" int hm_gemm_px_grid(int tiles, int cus) { return px_grid_for(tiles, cus > 0 ? cus : 256); }
 
-template <class T, int EPI, int PIPE = 0>      // PIPE: 1 = the software-pipelined K loop (gemm_pp_kernel), 2 = with the copy stagger between the wave halves
+template <class T, int EPI>
 int launch_px(const KArgs& g, hipStream_t s) {
   constexpr int LDS = 5 * 256 * 128;
   // Epilogue form.  Both are bit-identical; measured in one process (profiles/r03_gemm_px_epilogue_ab.log): the lane-swap form
@@ -1984,26 +1414,9 @@ int launch_px(const KArgs& g, hipStream_t s) {
   // and 3 % slower for the plain store (qkv 119.8 vs 116.4, kv 177.2 vs 170.9) -- so each epilogue takes its faster form.
   // HM_OPT_PX_LDS_EPILOGUE: 0 = that choice, 1 = always through LDS, 2 = always lane swaps.
   const int form = hm_option(HM_OPT_PX_LDS_EPILOGUE);
-  const bool staged = form == 1 || (form == 0 && ((PIPE == 1 || PIPE == 2) || (EPI != HM_EPI_GELU && EPI != HM_EPI_SILU)));
-  if (PIPE == 4 && !g.ln_stats) return hm_set_error(HM_ERR_ARG, "hm_gemm: variant 35 (stamps) needs a device buffer of 6 x 8 bytes per workgroup in ln_stats");   // (pipelined kernel: the lane-swap GELU form does not fit the register file)
-#ifdef HM_ABLATIONS
-  void (*kern)(const KArgs) = nullptr;
-  if constexpr (PIPE == 0) kern = staged ? gemm_px_kernel<T, EPI, false> : gemm_px_kernel<T, EPI, true>;     // (the only form a SiLU epilogue exists in)
-  else kern = PIPE == 9 ? (staged ? gemm_px_kernel<T, EPI, false, false, false, true, true, false, 2> : gemm_px_kernel<T, EPI, true, false, false, true, true, false, 2>)
-            : PIPE == 8 ? (staged ? gemm_px_kernel<T, EPI, false, false, false, true, true, false, 1> : gemm_px_kernel<T, EPI, true, false, false, true, true, false, 1>)
-            : PIPE == 7 ? (staged ? gemm_px_kernel<T, EPI, false, false, false, true, true, true> : gemm_px_kernel<T, EPI, true, false, false, true, true, true>)
-            : PIPE == 6 ? (staged ? gemm_px_kernel<T, EPI, false, false, false, true, false> : gemm_px_kernel<T, EPI, true, false, false, true, false>)
-            : PIPE == 5 ? (staged ? gemm_px_kernel<T, EPI, false, false, false, false> : gemm_px_kernel<T, EPI, true, false, false, false>)
-            : PIPE == 4 ? (staged ? gemm_px_kernel<T, EPI, false, false, true> : gemm_px_kernel<T, EPI, true, false, true>)
-            : PIPE == 3 ? (staged ? gemm_px_kernel<T, EPI, false, true, false, false, false> : gemm_px_kernel<T, EPI, true, true, false, false, false>)   // (as measured: round 3's copy issue and read order)
-            : PIPE == 2 ? (staged ? gemm_pp_kernel<T, EPI, false, true> : gemm_pp_kernel<T, EPI, true, true>)
-            : PIPE ? (staged ? gemm_pp_kernel<T, EPI, false> : gemm_pp_kernel<T, EPI, true>)
-                   : (staged ? gemm_px_kernel<T, EPI, false> : gemm_px_kernel<T, EPI, true>);
-#else
-  static_assert(PIPE == 0, "the pipelined K loop is an experiment (-DHM_ABLATIONS)");
+  const bool staged = form == 1 || (form == 0 && EPI != HM_EPI_GELU && EPI != HM_EPI_SILU);
   auto kern = staged ? gemm_px_kernel<T, EPI, false> : gemm_px_kernel<T, EPI, true>;
-#endif
-  static HmLdsOnce lds_once[2];      // (per instantiation of this launcher: one pair per (T, EPI, PIPE))
+  static HmLdsOnce lds_once[2];      // (per instantiation of this launcher: one pair per (T, EPI))
   if (const int rc = lds_once[staged ? 1 : 0].ensure((const void*)kern, LDS, "gemm: cannot raise the dynamic LDS limit")) return rc;
   const int tiles = (g.M >> 8) * (g.N >> 8);
   int cus = hm_device_cu_count();
@@ -2018,152 +1431,6 @@ bool px_ok(const KArgs& g) {
   return g.M % 256 == 0 && g.N % 256 == 0 && g.K >= 128 && (g.ldc & 7) == 0 && (g.M >> 8) * (g.N >> 8) >= 8 &&
          256ull * g.ldx * 2 < (1ull << 32) && 256ull * g.ldw * 2 < (1ull << 32) && (((uintptr_t)g.C) & 15) == 0;
 }
-
-#ifdef HM_ABLATIONS
-// ---------------------------------------------------------------------------------------------------------------
-// Variant 29: the 256x256x64 tile on FOUR waves (one per SIMD), each owning a 128x128 quadrant = 8x8 MFMA tiles.
-// Per K-step and CU that is 64 ds_read_b128 instead of the 96 of the 8-wave kernels (2/3 of the LDS traffic per flop) and
-// a wave may use the whole 512-entry register file: 256 accumulator registers, and TWO sets of operand fragments, so the
-// fragments of the next half-step are read while the MFMAs of the current one run -- inside one wave, without relying on
-// a second wave of the SIMD being out of phase.  One barrier per K-step, in its middle:
-//     first half : MFMAs on F0 = fragments (t, k 0..31)   | read F1 = (t, k 32..63)
-//     lgkmcnt(0), vmcnt(8), barrier                        -> every wave is done with step t's slots; step t+1 has landed
-//     second half: MFMAs on F1                             | copy W(t+2), X(t+3) into the freed slots | read F0 = (t+1, k 0..31)
-// Ring as in gemm_x3_kernel (X: 3 slots, two steps ahead; W: 2 slots).  Copies, reads and MFMAs are laid out in 16 groups
-// per half-step (1 copy, 1 read, 4 MFMAs) fenced by sched_barrier, so the issue order is the one written here.
-template <class T, int EPI, int ABL = 0>     // ABL (HM_ABLATIONS builds only): 1 = no copies in the loop, 2 = copies and waits only
-__global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const KArgs g) {
-  constexpr int MI = 8, NI = 8, BM = 256, BN = 256, BK = 64, ROWB = 128;
-  constexpr int TILE_BYTES = 256 * ROWB;
-  constexpr int XRING = 0, WRING = 3 * TILE_BYTES;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using vec8 = typename T::vec8;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
-  int tm, tn;
-  tile_coords(xcd_remap(blockIdx.x, gridDim.x), tiles_m, tiles_n, g.group_m, tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int wr = wave >> 1, wc = wave & 1;
-  const char* X = (const char*)g.X;
-  const char* W = (const char*)g.W;
-
-  // copies: wave w moves rows [64 w, 64 w + 64) of both tiles, 8 pieces of 8 rows x 128 B each
-  const int srow = lane >> 3, swz = (lane & 7) ^ (srow & 7);
-  unsigned xoff[8], woff[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    int gm = m0 + wave * 64 + i * 8 + srow;
-    gm = gm < g.M ? gm : g.M - 1;
-    xoff[i] = (unsigned)gm * (unsigned)(g.ldx * 2) + swz * 16;
-    int gn = n0 + wave * 64 + i * 8 + srow;
-    gn = gn < g.N ? gn : g.N - 1;
-    woff[i] = (unsigned)gn * (unsigned)(g.ldw * 2) + swz * 16;
-  }
-  auto dma_x1 = [&](int slot, int kt, int i) { glds16_hidden_s(X + (size_t)kt * ROWB, xoff[i], smem + XRING + slot * TILE_BYTES + (wave * 8 + i) * 1024); };
-  auto dma_w1 = [&](int slot, int kt, int i) { glds16_hidden_s(W + (size_t)kt * ROWB, woff[i], smem + WRING + slot * TILE_BYTES + (wave * 8 + i) * 1024); };
-
-  f32x4_t acc[NI][MI];
-#pragma unroll
-  for (int a = 0; a < NI; ++a)
-#pragma unroll
-    for (int b = 0; b < MI; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  const int frow = lane & 15, fsw = lane & 7, fch = lane >> 4;
-  const int fx = (wr * 128 + frow) * ROWB, fw = (wc * 128 + frow) * ROWB;
-  const int c0 = (fch ^ fsw) * 16, c1 = ((4 + fch) ^ fsw) * 16;
-  vec8 wf0[NI], xf0[MI], wf1[NI], xf1[MI];
-  // fragment j of a half-step: j < 8 -> X rows 16 j.., else W rows 16 (j - 8)..
-  auto rd = [&](const char* lx, const char* lw, int coff, int j, vec8 (&wf)[NI], vec8 (&xf)[MI]) {
-    if constexpr (ABL == 2) return;
-    if (j < 8) xf[j] = *(const vec8*)(lx + fx + j * 16 * ROWB + coff);
-    else wf[j - 8] = *(const vec8*)(lw + fw + (j - 8) * 16 * ROWB + coff);
-  };
-  auto mma4 = [&](int j, const vec8 (&wf)[NI], const vec8 (&xf)[MI]) {      // group j of 16: W fragment j / 2, X fragments 4 (j & 1) .. + 3
-    if constexpr (ABL == 2) return;
-    const int ni = j >> 1, mb = (j & 1) * 4;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[ni][mb + q] = T::mfma(wf[ni], xf[mb + q], acc[ni][mb + q]);
-  };
-
-  const int nk = g.K / BK;                              // host: nk >= 3
-  // prologue: X(0) W(0) X(1) W(1) X(2)
-#pragma unroll
-  for (int i = 0; i < 8; ++i) dma_x1(0, 0, i);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) dma_w1(0, 0, i);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) dma_x1(1, 1, i);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) dma_w1(1, 1, i);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) dma_x1(2, 2, i);
-  asm volatile("s_waitcnt vmcnt(24)" ::: "memory");    // X(0), W(0)
-  __builtin_amdgcn_s_barrier();
-#pragma unroll
-  for (int j = 0; j < 16; ++j) rd(smem + XRING, smem + WRING, c0, j, wf0, xf0);
-
-  int xs = 0;                                          // X slot of step t (t % 3); W slot t & 1
-  // one K-step; CW / CX: copies of W(t+2) / X(t+3) exist, MORE: a step t+1 exists (compile-time: the steady-state body has no branch)
-  auto step = [&](auto CW, auto CX, auto MORE, int t) {
-    const char* lx = smem + XRING + xs * TILE_BYTES;
-    const char* lw = smem + WRING + (t & 1) * TILE_BYTES;
-    // ---- first half
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      rd(lx, lw, c1, j, wf1, xf1);
-      mma4(j, wf0, xf0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // F1 is in registers (this wave is done with step t's slots); all but X(t+2) of this wave's copies have landed
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if constexpr (decltype(CW)::value && ABL != 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- second half
-    const int xn = xs == 2 ? 0 : xs + 1;               // slot of step t + 1
-    const char* lx1 = smem + XRING + xn * TILE_BYTES;
-    const char* lw1 = smem + WRING + ((t + 1) & 1) * TILE_BYTES;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      if (j < 8) { if constexpr (decltype(CW)::value && ABL != 1) dma_w1(t & 1, t + 2, j); }            // W first, then X: the counted wait relies on this order
-      else { if constexpr (decltype(CX)::value && ABL != 1) dma_x1(xs, t + 3, j - 8); }
-      if constexpr (decltype(MORE)::value) rd(lx1, lw1, c0, j, wf0, xf0);
-      mma4(j, wf1, xf1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    xs = xn;
-  };
-  using Yes = std::true_type;
-  using No = std::false_type;
-  for (int t = 0; t < nk - 3; ++t) step(Yes{}, Yes{}, Yes{}, t);
-  step(Yes{}, No{}, Yes{}, nk - 3);
-  step(No{}, No{}, Yes{}, nk - 2);
-  step(No{}, No{}, No{}, nk - 1);
-
-  __builtin_amdgcn_s_barrier();                        // the ring is free: per-column vectors, then epilogue staging
-  constexpr int EPI_BYTES = 4 * epi_stage_bytes(MI, NI);
-  float2* rowstat = (float2*)(smem + EPI_BYTES);       // unused by these epilogues
-  float* colvec = (float*)(rowstat + BM);
-  colvec[tid] = g.bias ? g.bias[min(n0 + tid, g.N - 1)] : 0.f;
-  __builtin_amdgcn_s_barrier();
-  epilogue<T, EPI, MI, NI>(g, acc, m0 + wr * 128, n0 + wc * 128, lane, smem + wave * epi_stage_bytes(MI, NI),
-                           rowstat + wr * 128, colvec + wc * 128, colvec + BN + wc * 128, 0);
-}
-
-template <class T, int EPI, int ABL = 0>
-int launch_w4(const KArgs& g, hipStream_t s) {
-  constexpr int LDS = 5 * 256 * 128;
-  static_assert(LDS >= 4 * epi_stage_bytes(8, 8) + 256 * 8 + 2 * 256 * 4, "epilogue staging + vectors fit");
-  auto kern = gemm_w4_kernel<T, EPI, ABL>;
-  static HmLdsOnce lds_once;
-  if (const int rc = lds_once.ensure((const void*)kern, LDS, "gemm: cannot raise the dynamic LDS limit")) return rc;
-  const int tiles = ((g.M + 255) / 256) * ((g.N + 255) / 256);
-  hipLaunchKernelGGL(kern, dim3(tiles), dim3(256), LDS, s, g);
-  return hm_check_launch("hm_gemm");
-}
-
-#endif  // HM_ABLATIONS (variant 29)
 
 // ---------------------------------------------------------------------------------------------------------------
 // Persistent form of gemm_fp8_kernel (the gemm_px_kernel idea on the fp8 MFMA) for the qkv (bf16 out) and fc1 (GELU ->
@@ -2481,15 +1748,15 @@ __global__ __launch_bounds__(256) void ln_finalize_kernel(const float2* __restri
   fin[m] = float2{mean, 1.0f / sqrtf(fmaxf(b * invD - mean * mean, 0.f) + eps)};
 }
 
-template <class T, int EPI, int WM, int WN, int MI, int NI, int STAGES, bool CONV, int BK = 64, int SCHED = 0, int WK = 1, bool KDUAL = false, bool KSER = false>
+template <class T, int EPI, int WM, int WN, int MI, int NI, int STAGES, bool CONV, bool MID_LOADS = false, int WK = 1, bool KDUAL = false, bool KSER = false>
 int launch_cfg(const KArgs& g, hipStream_t s, const char* what) {
-  constexpr int BM = WM * MI * 16, BN = WN * NI * 16;
+  constexpr int BM = WM * MI * 16, BN = WN * NI * 16, BK = 64;
   constexpr int RING = WK * STAGES * (BM + BN) * BK * 2, EPIB = WM * WN * epi_stage_bytes(MI, NI, WM * WN > 8 ? 8 : 16);
   constexpr int LDS = (RING > EPIB ? RING : EPIB) + BM * 8 + BN * 8;     // + row statistics + column vectors
   static_assert(LDS <= 160 * 1024, "fits the CU's LDS");
   if ((WK > 1 || KDUAL) && (g.K / BK / (EPI == HM_EPI_F32 ? g.ksplit : (KSER ? g.kser : 1))) % 2 != 0) return hm_set_error(HM_ERR_ARG, "gemm: K tiles do not split over the K groups");
   if (KSER && (g.kser < 1 || (g.K / BK) % g.kser != 0)) return hm_set_error(HM_ERR_ARG, "gemm: K tiles do not split over the serial ranges");
-  auto kern = gemm_tn_kernel<T, EPI, WM, WN, MI, NI, STAGES, CONV, BK, SCHED, WK, KDUAL, KSER>;
+  auto kern = gemm_tn_kernel<T, EPI, WM, WN, MI, NI, STAGES, CONV, MID_LOADS, WK, KDUAL, KSER>;
   static HmLdsOnce lds_once;
   if (const int rc = lds_once.ensure((const void*)kern, LDS, "gemm: cannot raise the dynamic LDS limit")) return rc;
   const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN) * (EPI == HM_EPI_F32 ? g.ksplit : 1);
@@ -2502,7 +1769,7 @@ int launch_cfg(const KArgs& g, hipStream_t s, const char* what) {
 int g_group_m = 8;
 int g_variant = -2;    // -2: read HM_GEMM_VARIANT on first use; -1: per-shape default
 
-// what the 32-bit lane offsets of the asm-issued copies (gemm_x3_kernel and the experiments built like it) require
+// what the 32-bit lane offsets of the asm-issued copies (gemm_x3_kernel, gemm_x3r_kernel) require
 bool off32_ok(const KArgs& g) { return (size_t)g.M * g.ldx * 2 < (1ull << 32) && (size_t)g.N * g.ldw * 2 < (1ull << 32); }
 
 template <class T, int EPI>
@@ -2510,7 +1777,7 @@ int launch_gemm(const KArgs& g, int variant, hipStream_t s) {
   switch (variant) {
     // ---- the product's tiles: what pick_variant() can choose
     case 0: return launch_cfg<T, EPI, 2, 2, 4, 4, 2, false>(g, s, "hm_gemm");          // 128x128, 4 waves, 2 stages (64 KB, 2 blocks/CU)
-    case 10: return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 2>(g, s, "hm_gemm");  // 256x256, waves 4x2 (64x128 each), 2 stages, s_setprio, loads between the sub-steps
+    case 10: return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, true>(g, s, "hm_gemm");  // 256x256, waves 4x2 (64x128 each), 2 stages, s_setprio, loads between the sub-steps
     case 26:                                                                           // persistent 256x256 (gemm_px_kernel), else as 24
       if constexpr (EPI == HM_EPI_STORE || EPI == HM_EPI_GELU) {
         if (px_ok(g)) return launch_px<T, EPI>(g, s);
@@ -2523,67 +1790,7 @@ int launch_gemm(const KArgs& g, int variant, hipStream_t s) {
       if constexpr (EPI == HM_EPI_STORE || EPI == HM_EPI_GELU || EPI == HM_EPI_RESID_F32) {
         if (off32_ok(g)) return launch_rs<T, EPI>(g, s);
       }
-      return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 2>(g, s, "hm_gemm");
-#ifdef HM_ABLATIONS
-    // ---- experiments (correct results, measured and not adopted: DESIGN.md section 4); tools and opt-in tests only
-    case 35:                                                                           // gemm_px_kernel with clock stamps (diagnostic)
-      if constexpr (EPI == HM_EPI_STORE || EPI == HM_EPI_GELU) {
-        if (px_ok(g)) return launch_px<T, EPI, 4>(g, s);
-      }
-      return hm_set_error(HM_ERR_ARG, "hm_gemm: variant 35 exists for the persistent kernel's shapes only");
-    case 27: case 33: case 34: case 36: case 37: case 38: case 39: case 40:                                                         // persistent 256x256, software-pipelined K loop (gemm_pp_kernel; 33: + copy stagger); 34: gemm_px_kernel with all copies issued by waves 0..3; else as 24
-      if constexpr (EPI == HM_EPI_STORE || EPI == HM_EPI_GELU) {
-        if (px_ok(g)) return variant == 40 ? launch_px<T, EPI, 9>(g, s) : variant == 39 ? launch_px<T, EPI, 8>(g, s) : variant == 38 ? launch_px<T, EPI, 7>(g, s) : variant == 37 ? launch_px<T, EPI, 6>(g, s) : variant == 36 ? launch_px<T, EPI, 5>(g, s) : variant == 34 ? launch_px<T, EPI, 3>(g, s) : (variant == 33 ? launch_px<T, EPI, 2>(g, s) : launch_px<T, EPI, 1>(g, s));   // (36: gemm_px_kernel with round 3's copy issue -- pointer casts, M0 saved and restored)
-      }
-      if constexpr (EPI == HM_EPI_RESID_F32) {
-        if (off32_ok(g) && rin_ok(g)) return launch_rin<T>(g, s);
-      }
-      if constexpr (EPI == HM_EPI_STORE || EPI == HM_EPI_GELU || EPI == HM_EPI_RESID_F32) {
-        if (off32_ok(g)) return launch_rs<T, EPI>(g, s);
-      }
-      return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 2>(g, s, "hm_gemm");
-    case 1: return launch_cfg<T, EPI, 4, 2, 4, 4, 3, false>(g, s, "hm_gemm");   // 256x128, 8 waves, 3 stages (144 KB)
-    case 2: return launch_cfg<T, EPI, 2, 4, 8, 4, 2, false>(g, s, "hm_gemm");   // 256x256, 8 waves, 2 stages (128 KB)
-    case 3: return launch_cfg<T, EPI, 4, 2, 4, 4, 2, false>(g, s, "hm_gemm");   // 256x128, 8 waves, 2 stages (96 KB)
-    case 4: return launch_cfg<T, EPI, 2, 2, 4, 4, 3, false>(g, s, "hm_gemm");   // 128x128, 4 waves, 3 stages (96 KB, 1 block/CU)
-    case 5: return launch_cfg<T, EPI, 2, 2, 8, 4, 3, false>(g, s, "hm_gemm");   // 256x128, 4 waves (128x64 each), 3 stages (144 KB)
-    case 6: return launch_cfg<T, EPI, 2, 4, 8, 4, 4, false, 32>(g, s, "hm_gemm");   // 256x256x32, 8 waves, 4 stages (128 KB)
-    case 7: return launch_cfg<T, EPI, 2, 4, 8, 4, 3, false, 32>(g, s, "hm_gemm");   // 256x256x32, 8 waves, 3 stages (96 KB)
-    case 8: return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false>(g, s, "hm_gemm");       // 256x256, waves 4x2 (64x128 each), 2 stages
-    case 9: return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 1>(g, s, "hm_gemm");   // + s_setprio around the MFMA cluster
-    case 11: return launch_cfg<T, EPI, 4, 2, 4, 8, 4, false, 32, 1>(g, s, "hm_gemm");  // 256x256x32, 4 stages, setprio
-    case 12: return launch_cfg<T, EPI, 4, 4, 4, 4, 2, false, 64, 2>(g, s, "hm_gemm");  // 256x256 on SIXTEEN waves of 64x64 (4 per SIMD, <= 128 VGPRs), 2 stages
-    case 21: return launch_cfg<T, EPI, 4, 2, 4, 4, 2, false, 32, 1>(g, s, "hm_gemm");  // 256x128x32, 8 waves, 2 stages (48 KB): 2 blocks/CU
-    case 22: return launch_cfg<T, EPI, 4, 2, 4, 4, 3, false, 32, 1>(g, s, "hm_gemm");  // 256x128x32, 8 waves, 3 stages (72 KB): 2 blocks/CU
-    case 23: return launch_cfg<T, EPI, 2, 2, 4, 4, 2, false, 32, 1>(g, s, "hm_gemm");  // 128x128x32, 4 waves, 2 stages (32 KB): 4 blocks/CU
-    case 25: return launch_cfg<T, EPI, 4, 2, 4, 10, 2, false, 64, 2>(g, s, "hm_gemm"); // 256x320, waves 4x2 (64x160 each), 2 stages (144 KB)
-    case 28:                                                                           // 256x160, both operands two steps ahead
-      if constexpr (EPI == HM_EPI_STORE || EPI == HM_EPI_GELU || EPI == HM_EPI_RESID_F32) {
-        if (off32_ok(g) && g.K >= 192) return launch_d2<T, EPI>(g, s);
-      }
-      return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 2>(g, s, "hm_gemm");
-    case 29:                                                                           // 256x256 on four waves of 128x128 (gemm_w4_kernel)
-      if constexpr (EPI == HM_EPI_STORE || EPI == HM_EPI_GELU || EPI == HM_EPI_RESID_F32) {
-        if (off32_ok(g) && g.K >= 192) return launch_w4<T, EPI>(g, s);
-      }
-      return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 2>(g, s, "hm_gemm");
-    // ---- timing ablations with WRONG results (tools/bench_gemm_ab.py only).  The w4 forms carry the guards of case 29:
-    // gemm_w4_kernel's prologue issues K-steps 0..2 unconditionally and its lane offsets are 32-bit.
-    case 30: case 31:
-      if constexpr (EPI == HM_EPI_STORE) {
-        if (!off32_ok(g) || g.K < 192) return hm_set_error(HM_ERR_ARG, "hm_gemm: ablations 30 / 31 need K >= 192 and operands below 4 GB");
-        return variant == 30 ? launch_w4<T, EPI, 1>(g, s) : launch_w4<T, EPI, 2>(g, s);     // w4 without copies / copies only
-      } else {
-        return hm_set_error(HM_ERR_ARG, "hm_gemm: ablations 30 / 31 exist for the store epilogue only");
-      }
-    case 16: return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 94>(g, s, "hm_gemm"); // everything, but no wave waits for its copies
-    case 17: return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 95>(g, s, "hm_gemm"); // ... and no barrier
-    case 14: return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 92>(g, s, "hm_gemm"); // LDS-DMA + waits + barriers only
-    case 15: return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 93>(g, s, "hm_gemm"); // ds_read + MFMA + barriers, no loads
-    case 20: return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 96>(g, s, "hm_gemm"); // no epilogue
-    case 18: return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 97>(g, s, "hm_gemm"); // every tile loads operand panel 0 (pure L2 hits)
-    case 32: return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 98>(g, s, "hm_gemm"); // K loop on 32x32x16 MFMAs (half the MFMA issues), no epilogue
-#endif
+      return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, true>(g, s, "hm_gemm");
     default: return hm_set_error(HM_ERR_ARG, "hm_gemm: unknown tile variant");
   }
 }
@@ -2592,24 +1799,18 @@ int launch_gemm(const KArgs& g, int variant, hipStream_t s) {
 template <class T, int EPI>
 int launch_gemm_ln(const KArgs& g, int variant, hipStream_t s) {
   if (variant == 0) return launch_cfg<T, EPI, 2, 2, 4, 4, 2, false>(g, s, "hm_gemm");
-  return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, 64, 2>(g, s, "hm_gemm");
+  return launch_cfg<T, EPI, 4, 2, 4, 8, 2, false, true>(g, s, "hm_gemm");
 }
 
 // Default tile choice (measured on MI355X, interleaved A/B on the ViT-H shapes, random data): the 256x256 tile halves
 // the LDS-DMA bytes per flop of the 128x128 one (the K loop is bound by the global->LDS fill, not by the MFMA pipe) and
 // wins by 15 % at M = 12288 -- as long as its tiles fill the CUs; small and mid-sized problems keep the 128x128 tile
 // (less padding and round waste, 2 workgroups per CU).
-bool variant_ok(int v) {
-  if (v == -1 || v == 0 || v == 10 || v == 24 || v == 26) return true;
-#ifdef HM_ABLATIONS
-  if ((v >= 1 && v <= 12) || (v >= 14 && v <= 18) || v == 20 || (v >= 21 && v <= 23) || v == 25 || (v >= 27 && v <= 40)) return true;
-#endif
-  return false;
-}
+bool variant_ok(int v) { return v == -1 || v == 0 || v == 10 || v == 24 || v == 26; }
 
 int pick_variant(const KArgs& g, int epilogue) {
   if (g_variant == -2) {
-    const char* e = getenv("HM_GEMM_VARIANT");     // tuning runs only; an unknown or ablation id is ignored, never obeyed
+    const char* e = getenv("HM_GEMM_VARIANT");     // tuning runs only; an unknown id is ignored, never obeyed
     const int v = e ? atoi(e) : -1;
     g_variant = variant_ok(v) ? v : -1;
   }
@@ -2763,7 +1964,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_direct_kernel(const KArgs g) {
           const f32x4_t a = acc[p][2 * np + h], bb = bv[2 * np + h];
           typename T::vec4 o;
           f32x4_t v4 = add4(a, bb);
-          if (ACT == 1 || ACT == 3) v4 = silu4(v4);
+          if (ACT == 1) v4 = silu4(v4);
 #pragma unroll
           for (int q = 0; q < 4; ++q) o[q] = (elem)(ACT == 2 ? fmaxf(v4[q], 0.f) : v4[q]);
           const u32x2 w = __builtin_bit_cast(u32x2, o);
@@ -2771,7 +1972,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_direct_kernel(const KArgs g) {
         }
         const u32x2 s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
         const u32x2 s1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
-        if (ox < g.Wout && (ACT != 3 || g.kser == 0x7fff))          // (ACT 3: bound diagnosis of the experiments library, nothing is stored)
+        if (ox < g.Wout)
           *(u32x4*)(yrow + (size_t)ox * g.ldc + (2 * np + (g4 & 1)) * 16 + (g4 >> 1) * 8) = u32x4{s0[0], s1[0], s0[1], s1[1]};
       }
     }
@@ -3121,7 +2322,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s2c32_kernel(const KArgs g) {
     typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
     typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     const int ox = tx * TW + li;
-    whole = ACT != 3 && (ty + 1) * TH <= g.Hout && (tx + 1) * TW <= g.Wout;
+    whole = (ty + 1) * TH <= g.Hout && (tx + 1) * TW <= g.Wout;
     char* ytile = (char*)g.C + ((((size_t)n * g.Hout + ty * TH + 4 * pg) * g.Wout + tx * TW) * g.ldc + 32 * chh) * 2;
     f32x4_t bv[2];
 #pragma unroll
@@ -3135,7 +2336,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s2c32_kernel(const KArgs g) {
         const f32x4_t a = acc[mi][h], bb = bv[h];
         typename T::vec4 o;
         f32x4_t v4 = add4(a, bb);
-        if (ACT == 1 || ACT == 3) v4 = silu4(v4);
+        if (ACT == 1) v4 = silu4(v4);
 #pragma unroll
         for (int q = 0; q < 4; ++q) o[q] = (elem)(ACT == 2 ? fmaxf(v4[q], 0.f) : v4[q]);
         const u32x2 w = __builtin_bit_cast(u32x2, o);
@@ -3143,7 +2344,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_s2c32_kernel(const KArgs g) {
       }
       const u32x2 s0 = __builtin_amdgcn_permlane16_swap(pk[0][0], pk[1][0], false, false);
       const u32x2 s1 = __builtin_amdgcn_permlane16_swap(pk[0][1], pk[1][1], false, false);
-      if ((whole || (ox < g.Wout && oy < g.Hout)) && (ACT != 3 || g.kser == 0x7fff)) {
+      if (whole || (ox < g.Wout && oy < g.Hout)) {
         const u32x4 o = u32x4{s0[0], s1[0], s0[1], s1[1]};
         const char* yrow = ytile + (size_t)mi * g.Wout * g.ldc * 2;
         asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" :: "v"(yoff), "v"(o), "s"(yrow) : "memory");   // (s_nop: see asm_store_note)
@@ -3844,14 +3045,6 @@ int try_conv_direct(const KArgs& g, int epilogue, hipStream_t s, bool& taken) {
   if (g.ksz != 3 || g.ldw < ((9 << g.cin_log2) + 31) / 32 * 32) return HM_OK;
   const int cin = 1 << g.cin_log2;
   taken = true;
-#ifdef HM_ABLATIONS
-  // bound diagnosis of the two stem layers (WRONG results): HM_OPT_CONV_DIRECT = 4: no activation, 5: SiLU computed, nothing stored
-  if (hm_option(HM_OPT_CONV_DIRECT) == 4 || hm_option(HM_OPT_CONV_DIRECT) == 5) {
-    const bool nostore = hm_option(HM_OPT_CONV_DIRECT) == 5;
-    if (cin == 8 && g.N == 32 && g.stride == 1) return nostore ? launch_conv_direct<T, 8, 32, 1, 3>(g, s) : launch_conv_direct<T, 8, 32, 1, 0>(g, s);
-    if (cin == 32 && g.N == 64 && g.stride == 2 && g.pad == 1) return nostore ? launch_conv_s2c32<T, 3>(g, s) : launch_conv_s2c32<T, 0>(g, s);
-  }
-#endif
   // 3x3 stride 1, 64 -> 64, when every one of the 512 persistent workgroups gets at least two 8 x 16 tiles (its weight slice is
   // loaded into registers once per workgroup): 16 frames, 192 x 320: 138 -> 79 us; 96 x 160 (3.75 tiles each): 40.4 -> 30.5 us;
   // 48 x 80 (480 tiles, not taken): 16.8 -> 18.2 us.  The two kernels agree to the bit, so the choice may depend on the batch.
@@ -3940,17 +3133,17 @@ int launch_conv_tile(const KArgs& g, int t, hipStream_t s, bool deep = false) {
   if (deep) {
     if constexpr (EPI == HM_EPI_STORE || EPI == HM_EPI_SILU || EPI == HM_EPI_RELU || EPI == HM_EPI_F32) {
       switch (t) {
-        case CT_128x32_P2: return launch_cfg<T, EPI, 2, 2, 4, 1, 3, true, 64, 0, 1, true>(g, s, "hm_conv2d_nhwc");
-        case CT_128x64_P2: return launch_cfg<T, EPI, 2, 2, 4, 2, 3, true, 64, 0, 1, true>(g, s, "hm_conv2d_nhwc");
+        case CT_128x32_P2: return launch_cfg<T, EPI, 2, 2, 4, 1, 3, true, false, 1, true>(g, s, "hm_conv2d_nhwc");
+        case CT_128x64_P2: return launch_cfg<T, EPI, 2, 2, 4, 2, 3, true, false, 1, true>(g, s, "hm_conv2d_nhwc");
         default: break;
       }
     }
     if constexpr (EPI == HM_EPI_STORE || EPI == HM_EPI_SILU || EPI == HM_EPI_RELU) {
       switch (t) {
-        case CT_128x32_S: return launch_cfg<T, EPI, 2, 2, 4, 1, 3, true, 64, 0, 1, false, true>(g, s, "hm_conv2d_nhwc");
-        case CT_128x64_S: return launch_cfg<T, EPI, 2, 2, 4, 2, 3, true, 64, 0, 1, false, true>(g, s, "hm_conv2d_nhwc");
-        case CT_128x32_SP2: return launch_cfg<T, EPI, 2, 2, 4, 1, 3, true, 64, 0, 1, true, true>(g, s, "hm_conv2d_nhwc");
-        case CT_128x64_SP2: return launch_cfg<T, EPI, 2, 2, 4, 2, 3, true, 64, 0, 1, true, true>(g, s, "hm_conv2d_nhwc");
+        case CT_128x32_S: return launch_cfg<T, EPI, 2, 2, 4, 1, 3, true, false, 1, false, true>(g, s, "hm_conv2d_nhwc");
+        case CT_128x64_S: return launch_cfg<T, EPI, 2, 2, 4, 2, 3, true, false, 1, false, true>(g, s, "hm_conv2d_nhwc");
+        case CT_128x32_SP2: return launch_cfg<T, EPI, 2, 2, 4, 1, 3, true, false, 1, true, true>(g, s, "hm_conv2d_nhwc");
+        case CT_128x64_SP2: return launch_cfg<T, EPI, 2, 2, 4, 2, 3, true, false, 1, true, true>(g, s, "hm_conv2d_nhwc");
         default: break;
       }
     }
@@ -3959,28 +3152,28 @@ int launch_conv_tile(const KArgs& g, int t, hipStream_t s, bool deep = false) {
     case CT_128x128: return launch_cfg<T, EPI, 2, 2, 4, 4, 2, true>(g, s, "hm_conv2d_nhwc");
     case CT_128x64: return launch_cfg<T, EPI, 2, 2, 4, 2, 2, true>(g, s, "hm_conv2d_nhwc");
     case CT_128x32: return launch_cfg<T, EPI, 2, 2, 4, 1, 2, true>(g, s, "hm_conv2d_nhwc");
-    case CT_256x128: return launch_cfg<T, EPI, 4, 2, 4, 4, 2, true, 64, 2>(g, s, "hm_conv2d_nhwc");
-    case CT_256x256: return launch_cfg<T, EPI, 4, 2, 4, 8, 2, true, 64, 2>(g, s, "hm_conv2d_nhwc");
-    case CT_256x64: return launch_cfg<T, EPI, 4, 2, 4, 2, 2, true, 64, 2>(g, s, "hm_conv2d_nhwc");
+    case CT_256x128: return launch_cfg<T, EPI, 4, 2, 4, 4, 2, true, true>(g, s, "hm_conv2d_nhwc");
+    case CT_256x256: return launch_cfg<T, EPI, 4, 2, 4, 8, 2, true, true>(g, s, "hm_conv2d_nhwc");
+    case CT_256x64: return launch_cfg<T, EPI, 4, 2, 4, 2, 2, true, true>(g, s, "hm_conv2d_nhwc");
     case CT_128x32_D: return launch_cfg<T, EPI, 2, 2, 4, 1, 4, true>(g, s, "hm_conv2d_nhwc");      // 4 x 20 KB
     case CT_128x64_D: return launch_cfg<T, EPI, 2, 2, 4, 2, 4, true>(g, s, "hm_conv2d_nhwc");      // 4 x 24 KB
     case CT_128x128_D: return launch_cfg<T, EPI, 2, 2, 4, 4, 3, true>(g, s, "hm_conv2d_nhwc");     // 3 x 32 KB
-    case CT_128x32_K2: return launch_cfg<T, EPI, 2, 2, 4, 1, 3, true, 64, 0, 2>(g, s, "hm_conv2d_nhwc");     // 2 x 3 x 20 KB
-    case CT_128x64_K2: return launch_cfg<T, EPI, 2, 2, 4, 2, 3, true, 64, 0, 2>(g, s, "hm_conv2d_nhwc");     // 2 x 3 x 24 KB
-    case CT_128x128_K2: return launch_cfg<T, EPI, 2, 2, 4, 4, 2, true, 64, 0, 2>(g, s, "hm_conv2d_nhwc");    // 2 x 2 x 32 KB
-    case CT_128x32_P2: return launch_cfg<T, EPI, 2, 2, 4, 1, 2, true, 64, 0, 1, true>(g, s, "hm_conv2d_nhwc");
-    case CT_128x64_P2: return launch_cfg<T, EPI, 2, 2, 4, 2, 2, true, 64, 0, 1, true>(g, s, "hm_conv2d_nhwc");
-    case CT_128x128_P2: return launch_cfg<T, EPI, 2, 2, 4, 4, 2, true, 64, 0, 1, true>(g, s, "hm_conv2d_nhwc");
+    case CT_128x32_K2: return launch_cfg<T, EPI, 2, 2, 4, 1, 3, true, false, 2>(g, s, "hm_conv2d_nhwc");     // 2 x 3 x 20 KB
+    case CT_128x64_K2: return launch_cfg<T, EPI, 2, 2, 4, 2, 3, true, false, 2>(g, s, "hm_conv2d_nhwc");     // 2 x 3 x 24 KB
+    case CT_128x128_K2: return launch_cfg<T, EPI, 2, 2, 4, 4, 2, true, false, 2>(g, s, "hm_conv2d_nhwc");    // 2 x 2 x 32 KB
+    case CT_128x32_P2: return launch_cfg<T, EPI, 2, 2, 4, 1, 2, true, false, 1, true>(g, s, "hm_conv2d_nhwc");
+    case CT_128x64_P2: return launch_cfg<T, EPI, 2, 2, 4, 2, 2, true, false, 1, true>(g, s, "hm_conv2d_nhwc");
+    case CT_128x128_P2: return launch_cfg<T, EPI, 2, 2, 4, 4, 2, true, false, 1, true>(g, s, "hm_conv2d_nhwc");
     default: break;
   }
   if constexpr (EPI == HM_EPI_STORE || EPI == HM_EPI_SILU || EPI == HM_EPI_RELU) {
     switch (t) {
-      case CT_128x32_S: return launch_cfg<T, EPI, 2, 2, 4, 1, 2, true, 64, 0, 1, false, true>(g, s, "hm_conv2d_nhwc");
-      case CT_128x64_S: return launch_cfg<T, EPI, 2, 2, 4, 2, 2, true, 64, 0, 1, false, true>(g, s, "hm_conv2d_nhwc");
-      case CT_128x128_S: return launch_cfg<T, EPI, 2, 2, 4, 4, 2, true, 64, 0, 1, false, true>(g, s, "hm_conv2d_nhwc");
-      case CT_128x32_SP2: return launch_cfg<T, EPI, 2, 2, 4, 1, 2, true, 64, 0, 1, true, true>(g, s, "hm_conv2d_nhwc");
-      case CT_128x64_SP2: return launch_cfg<T, EPI, 2, 2, 4, 2, 2, true, 64, 0, 1, true, true>(g, s, "hm_conv2d_nhwc");
-      case CT_128x128_SP2: return launch_cfg<T, EPI, 2, 2, 4, 4, 2, true, 64, 0, 1, true, true>(g, s, "hm_conv2d_nhwc");
+      case CT_128x32_S: return launch_cfg<T, EPI, 2, 2, 4, 1, 2, true, false, 1, false, true>(g, s, "hm_conv2d_nhwc");
+      case CT_128x64_S: return launch_cfg<T, EPI, 2, 2, 4, 2, 2, true, false, 1, false, true>(g, s, "hm_conv2d_nhwc");
+      case CT_128x128_S: return launch_cfg<T, EPI, 2, 2, 4, 4, 2, true, false, 1, false, true>(g, s, "hm_conv2d_nhwc");
+      case CT_128x32_SP2: return launch_cfg<T, EPI, 2, 2, 4, 1, 2, true, false, 1, true, true>(g, s, "hm_conv2d_nhwc");
+      case CT_128x64_SP2: return launch_cfg<T, EPI, 2, 2, 4, 2, 2, true, false, 1, true, true>(g, s, "hm_conv2d_nhwc");
+      case CT_128x128_SP2: return launch_cfg<T, EPI, 2, 2, 4, 4, 2, true, false, 1, true, true>(g, s, "hm_conv2d_nhwc");
       default: break;
     }
   }
@@ -4129,7 +3322,7 @@ extern "C" int hm_gemm_set_group_m(int gm) {
 }
 
 extern "C" int hm_gemm_set_variant(int v) {
-  if (!variant_ok(v)) return hm_set_error(HM_ERR_ARG, "hm_gemm_set_variant: -1 (default) or a shipped tile variant: 0, 10, 24, 26 (experiments and ablations: libhamer_hip_abl.so)");
+  if (!variant_ok(v)) return hm_set_error(HM_ERR_ARG, "hm_gemm_set_variant: -1 (default) or a shipped tile variant: 0, 10, 24, 26");
   g_variant = v;
   return HM_OK;
 }
@@ -4168,9 +3361,6 @@ extern "C" int hm_gemm(const hm_gemm_args* a, void* stream_) {
     k.ksplit = g.k_split;
   }
   if (ln_out) { k.ln_gamma = g.ln_gamma; k.ln_xg = g.ln_xg; k.ln_stats = g.ln_stats; k.ln_P = g.N / 64; }
-#ifdef HM_ABLATIONS
-  if (g_variant == 35) k.ln_stats = g.ln_stats;      // (diagnostic build: the stamp buffer of gemm_px_kernel<..., STAMP>)
-#endif
   if (ln_in) {
     k.ln_stats = g.ln_stats; k.ln_colsum = g.ln_colsum;
   }

@@ -2,7 +2,7 @@
 """Interleaved A/B of GEMM tile variants on the ViT-H shapes (random data): ROUNDS rounds, every round runs
 every variant REPS times per shape; reports the median over all launches of a variant (200 / 201: the default tile with
 the fp32 residual fetched in the epilogue / inside the K loop; >= 100 otherwise: default tile with group_m = v - 100).  One process, one
-device, variants interleaved so clock drift hits them equally.  Env: VARIANTS=8,9,10 ROUNDS=6 REPS=5"""
+device, variants interleaved so clock drift hits them equally.  Env: VARIANTS=0,10,24,26 ROUNDS=6 REPS=5"""
 import os
 import sys
 
@@ -12,10 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hamer_yolo_amd import lib as L
 from hamer_yolo_amd import ops
 
-if os.environ.get("ABLATION_LIB"):     # python -m hamer_yolo_amd.build --ablations: variants that skip work (wrong results, timing only)
-    L.LIB_PATH = L.LIB_PATH.replace(".so", "_abl.so")
-
-variants = [int(v) for v in os.environ.get("VARIANTS", "0,8").split(",")]      # v >= 100: default variant with group_m = v - 100
+variants = [int(v) for v in os.environ.get("VARIANTS", "0,26").split(",")]      # v >= 100: default variant with group_m = v - 100
 rounds, reps = int(os.environ.get("ROUNDS", 6)), int(os.environ.get("REPS", 5))
 M = int(os.environ.get("BATCH", 64)) * 192
 DT = torch.float16 if os.environ.get("DTYPE", "fp16") == "fp16" else torch.bfloat16

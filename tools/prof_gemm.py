@@ -15,7 +15,7 @@ banner()
 
 M, N, K = int(os.environ.get("GM", 12288)), int(os.environ.get("GN", 1280)), int(os.environ.get("GK", 5120))
 epi = int(os.environ.get("EPI", L.HM_EPI_STORE))
-L.check(L.load().hm_gemm_set_variant(int(os.environ.get("VARIANT", 8))))
+L.check(L.load().hm_gemm_set_variant(int(os.environ.get("VARIANT", 26))))
 torch.manual_seed(0)
 x = torch.randn(M, K, device="cuda").bfloat16()
 w = (torch.randn(N, K, device="cuda") * 0.02).bfloat16()

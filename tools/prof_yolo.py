@@ -6,8 +6,6 @@ Usage: python tools/prof_yolo.py [frames=16] [reps=3]      (rocprofv3 --kernel-t
 import os, sys, collections, torch
 sys.path.insert(0, ".")
 from hamer_yolo_amd import synth, lib as L
-if os.environ.get("ABLATION_LIB"):     # experiments library (python -m hamer_yolo_amd.build --ablations): CONV_DIRECT=4 / 5 = the two stem layers
-    L.LIB_PATH = L.LIB_PATH.replace(".so", "_abl.so")   # without their activation / without their stores (WRONG results, bound diagnosis only)
 from hamer_yolo_amd.yolo.engine import YoloEngine
 import os as _os, sys as _sys
 _sys.path.insert(0, _os.path.join(_os.path.dirname(_os.path.abspath(__file__))))

@@ -5,7 +5,7 @@ import os
 import sys
 import time
 
-KEYS = ("VARIANTS", "ROUNDS", "REPS", "BATCH", "DTYPE", "SHAPES", "EPI_STORE", "PAD", "YARDSTICK", "ABLATION_LIB", "VARIANT")
+KEYS = ("VARIANTS", "ROUNDS", "REPS", "BATCH", "DTYPE", "SHAPES", "EPI_STORE", "PAD", "YARDSTICK", "VARIANT")
 
 
 def banner(extra: str = "") -> None:
