@@ -13,6 +13,7 @@ class Config:
     model_cfg = os.path.join(root_dir, "hamer/_DATA/hamer_ckpts/model_config.yaml")
     onnx_path = os.path.join(root_dir, "hamer/_DATA/hamer_ckpts/onnx/hamer_inferpy.onnx")
     use_onnx = False      # the ONNX path is out of scope (BASELINE.json north_star): True raises
+    precise = False       # True: the fp32 HaMeR route (the reference's fp32 arithmetic; --precise-hamer)
 
 
 hamer_opt = Config()

@@ -17,18 +17,14 @@
 // ds_read_b128, and the 32 rows one MFMA operand read touches start in different banks.
 // Within a stage the K order is: for each group g of 8 k, lanes 0-31 (k-slot 0 of the MFMA) hold k = 8g + e and lanes 32-63
 // (k-slot 1) hold k = 8g + 4 + e, e = 0..3 the MFMA's index in the group -- one 16-byte LDS read per operand and group, the
-// same mapping on both operands.
+// same mapping on both operands.  (That MFMA side of a stage lives in mfma_f32_tile.h, shared with gemm_f32.hip.)
 #include <math.h>
 #include <stdio.h>
 #include "common.h"
 #include "hamer_hip_internal.h"
+#include "mfma_f32_tile.h"      // F32_BK, F32_LDK and the MFMA side of the stage loop, shared with gemm_f32.hip
 
 namespace {
-
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-
-constexpr int F32_BK = 32;             // K per stage
-constexpr int F32_LDK = F32_BK + 4;    // LDS row stride in floats
 
 struct ConvF32Args {
   const float* X;      // [N][H][Wd][ldx], already offset to the first input channel
@@ -111,15 +107,10 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32Args a) {
   };
 
   f32x16_t acc[RB][CB];
-#pragma unroll
-  for (int i = 0; i < RB; ++i)
-#pragma unroll
-    for (int j = 0; j < CB; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  f32_tile_zero(acc);
 
-  const int arow = (wm * RB * 32 + (lane & 31)) * F32_LDK + 4 * (lane >> 5);
-  const int brow_l = (BM + wn * CB * 32 + (lane & 31)) * F32_LDK + 4 * (lane >> 5);
+  const int arow = f32_tile_lane_offset(wm * RB * 32, lane);
+  const int brow_l = f32_tile_lane_offset(BM + wn * CB * 32, lane);
   const int nk = a.nk;
   fetch(0);
   stash(0);
@@ -127,21 +118,7 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32Args a) {
   for (int st = 0; st < nk; ++st) {
     const int cur = st & 1;
     if (st + 1 < nk) fetch((st + 1) * F32_BK);
-    const float* s = smem + cur * STAGE;
-#pragma unroll
-    for (int g = 0; g < F32_BK / 8; ++g) {
-      f32x4_t av[RB], bv[CB];
-#pragma unroll
-      for (int i = 0; i < RB; ++i) av[i] = *(const f32x4_t*)(s + arow + i * 32 * F32_LDK + 8 * g);
-#pragma unroll
-      for (int j = 0; j < CB; ++j) bv[j] = *(const f32x4_t*)(s + brow_l + j * 32 * F32_LDK + 8 * g);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int i = 0; i < RB; ++i)
-#pragma unroll
-          for (int j = 0; j < CB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i][e], bv[j][e], acc[i][j], 0, 0, 0);
-    }
+    f32_tile_stage<RB, CB>(smem + cur * STAGE, arow, brow_l, acc);
     if (st + 1 < nk) stash(cur ^ 1);
     __syncthreads();
   }
@@ -157,7 +134,7 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF32Args a) {
     for (int i = 0; i < RB; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int m = m0 + (wm * RB + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int m = m0 + (wm * RB + i) * 32 + f32_tile_row(r, lane);
         if (m >= a.M) continue;
         float v = acc[i][j][r] + b;
         if constexpr (EPI == EPI_YOLO) {

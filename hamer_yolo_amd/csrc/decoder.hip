@@ -108,7 +108,9 @@ __global__ __launch_bounds__(64) void cross_attention_kernel(const float* __rest
   for (int i = 0; i < CA_MAXT / 64; ++i) {
     const int t = lane + 64 * i;
     if (t < tokens) {
-      const float p = __expf(sc[i] - mx);
+      float p;
+      if constexpr (sizeof(E) == 4) p = expf(sc[i] - mx);      // the precise route: the accurate exponential
+      else p = __expf(sc[i] - mx);
       ps[t] = p;
       sum += p;
     }
@@ -163,6 +165,7 @@ extern "C" int hm_cross_attention(const float* q, const void* kv, int ldkv, int 
     return hm_set_error(HM_ERR_ARG, "hm_cross_attention: dim_head must be 64 and tokens <= 256");
   if (ldkv % 8 != 0 || k_off % 8 != 0 || v_off % 8 != 0 || ((uintptr_t)kv & 15))
     return hm_set_error(HM_ERR_ARG, "hm_cross_attention: kv rows must be 16-byte aligned");
+  if (dtype == HM_DTYPE_F32 && ((uintptr_t)kv & 31)) return hm_set_error(HM_ERR_ARG, "hm_cross_attention: fp32 kv rows must be 32-byte aligned");
   dim3 grid(B * heads), block(64);
   hipStream_t s = (hipStream_t)stream_;
   HmProfScope prof(HM_K_CROSS_ATTN, 0, B, tokens, heads, s);
@@ -170,6 +173,8 @@ extern "C" int hm_cross_attention(const float* q, const void* kv, int ldkv, int 
     hipLaunchKernelGGL(cross_attention_kernel<__bf16>, grid, block, 0, s, q, (const __bf16*)kv, ldkv, k_off, v_off, out, B, tokens, heads, scale);
   else if (dtype == HM_DTYPE_F16)
     hipLaunchKernelGGL(cross_attention_kernel<_Float16>, grid, block, 0, s, q, (const _Float16*)kv, ldkv, k_off, v_off, out, B, tokens, heads, scale);
+  else if (dtype == HM_DTYPE_F32)      // the precise route: fp32 k / v from hm_gemm_f32
+    hipLaunchKernelGGL(cross_attention_kernel<float>, grid, block, 0, s, q, (const float*)kv, ldkv, k_off, v_off, out, B, tokens, heads, scale);
   else
     return hm_set_error(HM_ERR_ARG, "hm_cross_attention: bad dtype");
   return hm_check_launch("hm_cross_attention");

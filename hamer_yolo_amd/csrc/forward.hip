@@ -34,15 +34,16 @@ Layout make_layout(const hm_hamer_weights& w, int B) {
   const size_t M = (size_t)B * gh * gw, D = w.embed_dim;
   const size_t inner = (size_t)w.dec_heads * w.dec_dim_head;
   const size_t dmax = (size_t)(w.dec_dim > w.dec_mlp ? w.dec_dim : w.dec_mlp);
+  const size_t es = w.dtype == HM_DTYPE_F32 ? 4 : 2;       // bytes per GEMM operand element (the precise route: fp32 throughout)
   Layout L;
   size_t o = 0;
-  L.patches = o; o += align256(M * 3 * w.patch * w.patch * 2);
+  L.patches = o; o += align256(M * 3 * w.patch * w.patch * es);
   L.x = o; o += align256(M * D * 4);
-  L.h = o; o += align256(M * D * 2);
-  L.qkv = o; o += align256(M * 3 * D * 2);
-  L.att = o; o += align256(M * D * 2);
-  L.mlp = o; o += align256(M * (size_t)w.mlp_dim * 2);
-  L.kv = o; o += align256(M * (size_t)w.dec_depth * 2 * inner * 2);
+  L.h = o; o += align256(M * D * es);
+  L.qkv = o; o += align256(M * 3 * D * es);
+  L.att = o; o += align256(M * D * es);
+  L.mlp = o; o += align256(M * (size_t)w.mlp_dim * es);
+  L.kv = o; o += align256(M * (size_t)w.dec_depth * 2 * inner * es);
   L.xd = o; o += align256((size_t)B * w.dec_dim * 4);
   L.hd = o; o += align256((size_t)B * w.dec_dim * 4);
   L.t1 = o; o += align256((size_t)B * (inner > dmax ? inner : dmax) * 4);
@@ -56,6 +57,7 @@ Layout make_layout(const hm_hamer_weights& w, int B) {
   // split-K of the two N = D GEMMs of a block when their 128x128 tiles would leave most CUs idle (a few hands)
   L.ksplit_proj = pick_split_k((int)M, (int)D, (int)D);
   L.ksplit_fc2 = pick_split_k((int)M, (int)D, w.mlp_dim);
+  if (w.dtype == HM_DTYPE_F32) L.ksplit_proj = L.ksplit_fc2 = 1;     // one sum over K in one order at every batch size
   const int smax = L.ksplit_proj > L.ksplit_fc2 ? L.ksplit_proj : L.ksplit_fc2;
   L.partials = o; o += smax > 1 ? align256((size_t)smax * M * D * 4) : 0;
   L.x2 = L.tsize = L.tmetric = L.tindex = 0;
@@ -80,6 +82,29 @@ int check_weights(const hm_hamer_weights* w) {
       !w->kv_w || !w->head_w || !w->head_b)
     return hm_set_error(HM_ERR_ARG, "hm_hamer_forward: incomplete weights");
   if (w->embed_dim % w->heads != 0) return hm_set_error(HM_ERR_ARG, "hm_hamer_forward: embed_dim % heads != 0");
+  if (w->dtype != HM_DTYPE_BF16 && w->dtype != HM_DTYPE_F16 && w->dtype != HM_DTYPE_F32) return hm_set_error(HM_ERR_ARG, "hm_hamer_forward: bad dtype");
+  return HM_OK;
+}
+
+// HM_DTYPE_F32: nothing of the 16-bit route's load-time rewriting may ride along (hamer_hip.h, hm_hamer_forward)
+int check_weights_f32(const hm_hamer_weights* w) {
+  if (w->tome_r) return hm_set_error(HM_ERR_ARG, "hm_hamer_forward (fp32): token merging (tome_r) is not part of the precise route");
+  if (w->range_stats) return hm_set_error(HM_ERR_ARG, "hm_hamer_forward (fp32): range_stats is for the dense 16-bit path");
+  for (int i = 0; i < w->depth; ++i) {
+    const hm_vit_block& b = w->blocks[i];
+    if (!b.ln1_g || !b.ln1_b || !b.ln2_g || !b.ln2_b || !b.qkv_w || !b.proj_w || !b.fc1_w || !b.fc2_w || !b.qkv_b || !b.proj_b || !b.fc1_b || !b.fc2_b)
+      return hm_set_error(HM_ERR_ARG, "hm_hamer_forward (fp32): incomplete block weights");
+    if (b.qkv_w8 || b.fc1_w8 || b.fc2_w8 || b.qkv_ws || b.fc1_ws || b.fc2_ws || b.proj_w8 || b.proj_ws)
+      return hm_set_error(HM_ERR_ARG, "hm_hamer_forward (fp32): fp8 weights are not part of the precise route");
+    if (b.qkv_colsum || b.qkv_bias_ln || b.fc1_colsum || b.fc1_bias_ln)
+      return hm_set_error(HM_ERR_ARG, "hm_hamer_forward (fp32): deferred-LayerNorm operands (*_colsum, *_bias_ln) are not part of the precise route");
+    if (b.kmean_w || b.kmean_b) return hm_set_error(HM_ERR_ARG, "hm_hamer_forward (fp32): the token-merging metric is not part of the precise route");
+    if ((b.attn_scale_mul != 0.f && b.attn_scale_mul != 1.f) || (b.gelu_out_scale != 0.f && b.gelu_out_scale != 1.f))
+      return hm_set_error(HM_ERR_ARG, "hm_hamer_forward (fp32): the range prescale is not part of the precise route");
+  }
+  for (int i = 0; i < w->dec_depth; ++i)
+    if (w->layers[i].ca_scale_mul != 0.f && w->layers[i].ca_scale_mul != 1.f)
+      return hm_set_error(HM_ERR_ARG, "hm_hamer_forward (fp32): the range prescale is not part of the precise route");
   return HM_OK;
 }
 
@@ -98,6 +123,7 @@ extern "C" int hm_hamer_forward(const hm_hamer_weights* w, const float* img, int
   if (!img || !out || !workspace || B <= 0) return hm_set_error(HM_ERR_ARG, "hm_hamer_forward: bad arguments");
   if (!out->pose6d || !out->betas || !out->cam || !out->rotmats || !out->verts || !out->joints || !out->cam_t || !out->kp2d)
     return hm_set_error(HM_ERR_ARG, "hm_hamer_forward: incomplete outputs");
+  if (w->dtype == HM_DTYPE_F32) HM_TRY(check_weights_f32(w));
   const Layout L = make_layout(*w, B);
   if (workspace_bytes < L.total) return hm_set_error(HM_ERR_ARG, "hm_hamer_forward: workspace too small");
   if ((uintptr_t)workspace & 255) return hm_set_error(HM_ERR_ARG, "hm_hamer_forward: workspace must be 256-byte aligned");
@@ -175,7 +201,30 @@ extern "C" int hm_hamer_forward(const hm_hamer_weights* w, const float* img, int
   const float scale = 1.0f / sqrtf((float)(D / w->heads));
   void* tok = out->tokens ? out->tokens : h;
   int ctx_tokens = tokens;                              // tokens per crop the decoder attends over
-  if (w->tome_r) {
+  if (dt == HM_DTYPE_F32) {
+    // the precise route (HamerEngine(dtype=torch.float32)): the reference's fp32 arithmetic, kernel for kernel -- LayerNorm,
+    // hm_gemm_f32 (bias + one k-ordered sum, the residual behind it), hm_vit_attention_f32.  No deferred LayerNorm, no split-K,
+    // no prescale: the same launches and the same order of operations at every batch size.
+    auto gemm32 = [&](const void* X, int K, const void* W, int N, void* C, const float* bias, int epi, const float* resid, int rmod) {
+      hm_gemm_args g{};
+      g.X = X; g.W = W; g.C = C; g.bias = bias; g.resid = resid;
+      g.M = M; g.N = N; g.K = K; g.ldx = K; g.ldw = K; g.ldc = N; g.ldr = N; g.resid_mod = rmod;
+      g.epilogue = epi; g.dtype = HM_DTYPE_F32;
+      return hm_gemm_f32(&g, stream);
+    };
+    HM_TRY(gemm32(ws + L.patches, kpe, w->patch_w, D, x, w->patch_b, HM_EPI_RESID_F32, w->pos, tokens));
+    for (int i = 0; i < w->depth; ++i) {
+      const hm_vit_block& b = w->blocks[i];
+      HM_TRY(hm_layernorm(x, b.ln1_g, b.ln1_b, h, HM_OUT_F32, M, D, w->vit_eps, stream));
+      HM_TRY(gemm32(h, D, b.qkv_w, 3 * D, qkv, b.qkv_b, HM_EPI_F32, nullptr, 0));
+      HM_TRY(hm_vit_attention_f32((const float*)qkv, (float*)att, B, tokens, w->heads, D / w->heads, scale, stream));
+      HM_TRY(gemm32(att, D, b.proj_w, D, x, b.proj_b, HM_EPI_RESID_F32, x, 0));
+      HM_TRY(hm_layernorm(x, b.ln2_g, b.ln2_b, h, HM_OUT_F32, M, D, w->vit_eps, stream));
+      HM_TRY(gemm32(h, D, b.fc1_w, w->mlp_dim, mlp, b.fc1_b, HM_EPI_GELU, nullptr, 0));
+      HM_TRY(gemm32(mlp, w->mlp_dim, b.fc2_w, D, x, b.fc2_b, HM_EPI_RESID_F32, x, 0));
+    }
+    HM_TRY(hm_layernorm(x, w->last_g, w->last_b, tok, HM_OUT_F32, M, D, w->vit_eps, stream));
+  } else if (w->tome_r) {
     // token-merging variant (selective_vit_adapter.py ToMeBlock.forward :210-235): the token count T shrinks after the
     // attention of every block, the same for every crop, so all buffers stay compact [B * T][.] and only M changes
     if (fp8 || D / w->heads != 80) return hm_set_error(HM_ERR_ARG, "hm_hamer_forward: token merging needs the 16-bit path and head_dim 80");
@@ -292,8 +341,9 @@ extern "C" int hm_hamer_forward(const hm_hamer_weights* w, const float* img, int
   {
     hm_gemm_args g{};                                   // to_kv of all decoder layers over the B * ctx_tokens context rows
     g.X = tok; g.W = w->kv_w; g.C = kv; g.M = B * ctx_tokens; g.N = ldkv; g.K = D; g.ldx = D; g.ldw = D; g.ldc = ldkv;
-    g.epilogue = HM_EPI_STORE; g.dtype = dt;
-    HM_TRY(hm_gemm(&g, stream));
+    g.epilogue = dt == HM_DTYPE_F32 ? HM_EPI_F32 : HM_EPI_STORE; g.dtype = dt;
+    if (dt == HM_DTYPE_F32) HM_TRY(hm_gemm_f32(&g, stream));
+    else HM_TRY(hm_gemm(&g, stream));
     for (int i = 0; i < w->dec_depth; ++i) {
       HM_TRY(probe(kv, ldkv, B * ctx_tokens, i * 2 * inner, inner, 6 * w->depth + 1 + 2 * i));
       HM_TRY(probe(kv, ldkv, B * ctx_tokens, i * 2 * inner + inner, inner, 6 * w->depth + 2 + 2 * i));

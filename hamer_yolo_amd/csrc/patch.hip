@@ -121,6 +121,8 @@ extern "C" int hm_patch_im2col(const float* img, void* patches, int B, int img_h
     hipLaunchKernelGGL(im2col_kernel<__bf16>, grid, block, 0, s, img, (__bf16*)patches, B, img_h, img_w_full, x0, win_w, patch, pad, gh, gw);
   else if (dtype == HM_DTYPE_F16)
     hipLaunchKernelGGL(im2col_kernel<_Float16>, grid, block, 0, s, img, (_Float16*)patches, B, img_h, img_w_full, x0, win_w, patch, pad, gh, gw);
+  else if (dtype == HM_DTYPE_F32)      // the precise route: the patches as the fp32 GEMM operand, a plain copy of the pixels
+    hipLaunchKernelGGL(im2col_kernel<float>, grid, block, 0, s, img, (float*)patches, B, img_h, img_w_full, x0, win_w, patch, pad, gh, gw);
   else
     return hm_set_error(HM_ERR_ARG, "hm_patch_im2col: bad dtype");
   return hm_check_launch("hm_patch_im2col");

@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from .infer import *  # noqa: F401,F403
-from .infer import (FRAMES_PER_STEP, _default_models, _detection_list, _imread_bgr, _list_images, _record_from, _render_args, hamer_inference,  # noqa: F401
+from .infer import (FRAMES_PER_STEP, _default_models, _detection_list, _imread_bgr, _list_images, _precise_hamer_args, _record_from, _render_args, apply_precise_args, hamer_inference,  # noqa: F401
                     hamer_opt, hand_record, iter_folder_results, load_intrinsics, reconstruct_and_save_obj_with_wrapper)
 from .rootnet.Model_RGB import get_model  # noqa: F401
 
@@ -49,6 +49,7 @@ def _parser() -> argparse.ArgumentParser:
                     help="run YOLOv7 in fp32 (the reference's CPU branch) instead of fp16: its boxes, at about twice the detector time")
     ap.add_argument('--precise-rootnet', action='store_true',
                     help="run the RootNet backbone and depth head in fp32, as the reference does, instead of fp16 (DESIGN §9)")
+    _precise_hamer_args(ap)
     _render_args(ap)
     return ap
 
@@ -56,12 +57,7 @@ def _parser() -> argparse.ArgumentParser:
 def main(argv=None):
     """``python -m hamer_yolo_amd.d_infer --input <RGB_dir> --output <out_dir> --intrinsics <cam_K.txt>``."""
     args = _parser().parse_args(argv)
-    if args.precise_detector:
-        from .config.yolo_config import yolo_opt
-        yolo_opt.precise = True
-    if args.precise_rootnet:
-        from .rootnet.sar_config_stage_1 import rgb_opt
-        rgb_opt.precise = True
+    apply_precise_args(args)
     k_real = load_intrinsics(args.intrinsics)
     hamer = hamer_inference(hamer_opt)
     process_batch_manopara(args.input, args.output, k_real, hamer=hamer)

@@ -6,6 +6,10 @@ on the ViT-H geometry, rounding to fp16 (11 bits) by 1.7e-4 (tools/precision_stu
 MFMA rate -- so the default operand type is fp16; ``dtype=torch.bfloat16`` stays selectable for checkpoints whose
 activations need the wider exponent.
 
+``dtype=torch.float32`` is the opt-in precise route: the weights stay fp32, the forward runs the
+fp32-input MFMA kernels (hm_gemm_f32, hm_vit_attention_f32), nothing below that rewrites weights applies (no LayerNorm
+folding, no prescale, no folded self-attention matrix), and a hand's outputs are the same bytes in any batch.
+
 Load time (host, once): GEMM matrices are converted to the 16-bit operand type and laid out
 [N][K] as nn.Linear stores them; the positional embedding is folded to ``pos[1:] + pos[0]``
 (vit.py:327); the six decoder ``to_kv`` matrices are stacked into one [6*1024][1280] GEMM
@@ -79,6 +83,21 @@ class HamerEngine:
         and its to_out -- so that every 16-bit activation of a checkpoint that overflows fp16 lands inside it while the operands
         keep their 11 significant bits.  Exact arithmetic: powers of two commute with rounding (no value underflows on the way),
         so the forward computes the same function.  ``want_tokens`` then returns last_norm's output times 2^-prescale['last']."""
+        # the precise route (dtype=torch.float32; DESIGN.md section 2c): fp32 weights as the checkpoint holds them, no LayerNorm
+        # folding, no prescale, no split-K plan -- and none of the 16-bit route's variants.  Checked before any device work.
+        self.precise = dtype == torch.float32
+        if self.precise:
+            if token_merge:
+                raise ValueError("HamerEngine(dtype=torch.float32): token merging is not part of the precise fp32 route "
+                                 "(token_merge needs the 16-bit route)")
+            if fp8 or (fp8 is None and os.environ.get("HAMER_FP8", "0") == "1"):
+                raise ValueError("HamerEngine(dtype=torch.float32): fp8 weights are not part of the precise fp32 route "
+                                 "(fp8 needs dtype=torch.bfloat16)")
+            if fold_ln:
+                raise ValueError("HamerEngine(dtype=torch.float32): deferred LayerNorm (fold_ln) is not part of the precise fp32 route")
+            if not prescale_is_identity(prescale):
+                raise ValueError("HamerEngine(dtype=torch.float32): the range prescale is for fp16 operands, not the precise fp32 route")
+            fold_ln, fp8 = False, False
         if not torch.cuda.is_available():
             raise L.HipLibraryError("HamerEngine needs an MI355X (HIP device); there is no CPU fallback")
         self.lib = L.load()
@@ -203,8 +222,10 @@ class HamerEngine:
             l.sa_v_w = L.ptr(f32(sd[p + "0.fn.to_qkv.weight"][2 * inner:3 * inner]))
             l.sa_out_w, l.sa_out_b = L.ptr(f32(sd[p + "0.fn.to_out.0.weight"])), L.ptr(f32(sd[p + "0.fn.to_out.0.bias"]))
             # one token: softmax == 1, so self-attention is to_out(to_v(.)) -- folded into one [dim][dim] matrix in fp64
-            l.sa_w = L.ptr(f32((sd[p + "0.fn.to_out.0.weight"].to(self.device, torch.float64)
-                                @ sd[p + "0.fn.to_qkv.weight"][2 * inner:3 * inner].to(self.device, torch.float64)).float()))
+            # (the precise route keeps the reference's two linears: hm_hamer_forward takes them when sa_w is NULL)
+            if not self.precise:
+                l.sa_w = L.ptr(f32((sd[p + "0.fn.to_out.0.weight"].to(self.device, torch.float64)
+                                    @ sd[p + "0.fn.to_qkv.weight"][2 * inner:3 * inner].to(self.device, torch.float64)).float()))
             l.ca_q_w = L.ptr(f32(sd[p + "1.fn.to_q.weight"]))
             ekk, ekv = pre["dec"][i] if pre is not None else (0, 0)
             l.ca_out_w, l.ca_out_b = L.ptr(f32(scaled(sd[p + "1.fn.to_out.0.weight"], ekv))), L.ptr(f32(sd[p + "1.fn.to_out.0.bias"]))
@@ -247,7 +268,7 @@ class HamerEngine:
         w.head_w, w.head_b = L.ptr(f32(head_w)), L.ptr(f32(head_b))
         w.mano = mano_model_struct(self.mano)
         w.focal_length, w.image_size = float(self.cfg.focal_length), float(self.cfg.image_size)
-        w.dtype = L.HM_DTYPE_BF16 if dtype == torch.bfloat16 else L.HM_DTYPE_F16
+        w.dtype = L.HM_DTYPE_F32 if self.precise else L.HM_DTYPE_BF16 if dtype == torch.bfloat16 else L.HM_DTYPE_F16
         # token merging (HAMER_INFER(token_merge=True), hamer.py:481-483): True = the reference's schedule r = (8, -1);
         # an int, an (r, inflection) pair or a per-block list are parsed as selective_vit_adapter.py:132-157 does
         self.tome_r = None

@@ -64,6 +64,9 @@ def engine_config(cfg, state_dict: Dict[str, torch.Tensor]) -> synth.HamerConfig
 class HAMER:
     def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], mano: MANO, dtype=torch.float16,
                  hamer_cfg: Optional[synth.HamerConfig] = None, token_merge=False):
+        # dtype=torch.float32 is the precise route: fp32 weights and activations on the fp32-input MFMA
+        if dtype == torch.float32 and token_merge:
+            raise ValueError("HAMER(dtype=torch.float32): token merging is not part of the precise fp32 route")
         self.cfg = cfg
         self.mano = mano
         self.dtype = dtype
@@ -84,6 +87,7 @@ class HAMER:
         if self._engine is None or self.device != device:
             self._engine = HamerEngine(self._sd, self.mano.params, self._hc, device=device, dtype=self.dtype,
                                        token_merge=self.token_merge or None)
+            # (the precise fp32 route has fp32's range: no check)
             # fp16 operands (the type that meets the 1e-3 bar) have a 65504 ceiling and no overflow detection: check once,
             # at load, that this checkpoint's activations fit; if not, take the wider exponent and say so
             if self.dtype == torch.float16 and self.check_fp16_range and not self._engine.calibration_is_finite():
@@ -146,7 +150,8 @@ class HAMER:
         # a chunk of frames yields whatever number of hands the detector found.  From 24 hands on (where those tiles are
         # chosen) the batch is padded with copies of its last crop and the extra rows are dropped again: every hand is its own
         # problem, so the real hands' results are what a batch of that size gives them.
-        Bp = (B + 3) // 4 * 4 if B >= 24 else B
+        # (The precise route has one tile loop for every M and masks partial tiles: nothing to pad.)
+        Bp = (B + 3) // 4 * 4 if B >= 24 and self.dtype != torch.float32 else B
         if Bp != B:
             x = torch.cat([x, x[-1:].expand(Bp - B, -1, -1, -1)], 0)
         o = self._engine.forward(x, workspace=self._workspace(Bp))

@@ -71,13 +71,15 @@ def matrix_to_axis_angle(rot_mats) -> np.ndarray:
 
 
 class hamer_inference():
-    def __init__(self, cfg=hamer_opt):
-        """infer.py:118-146.  ``cfg.{ckpt_path, model_cfg, use_onnx, onnx_path}``."""
+    def __init__(self, cfg=hamer_opt, precise=None):
+        """infer.py:118-146.  ``cfg.{ckpt_path, model_cfg, use_onnx, onnx_path}``.  precise: None reads
+        ``getattr(cfg, "precise", False)``; True loads HaMeR on the fp32 route (load_hamer(precise=True))."""
+        self.precise = bool(getattr(cfg, "precise", False) if precise is None else precise)
         self.use_onnx = bool(getattr(cfg, "use_onnx", False))
         if self.use_onnx:
             raise NotImplementedError("the ONNX Runtime path of the reference is out of scope (no ONNX export path)")
         self.device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
-        model, model_cfg_obj = load_hamer(cfg.ckpt_path)
+        model, model_cfg_obj = load_hamer(cfg.ckpt_path, precise=self.precise)
         self.model = model.to(self.device)      # raises on a machine without an MI355X: no CPU fallback
         self.model.eval()
         self.cfg = model_cfg_obj
@@ -1046,8 +1048,29 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument('--yolo-weights', type=str, default=None, help="yolov7 .pt path or synthetic:<seed> (default: config/yolo_config.py)")
     ap.add_argument('--precise-detector', action='store_true',
                     help="run YOLOv7 in fp32 (the reference's CPU branch) instead of fp16: its boxes, at about twice the detector time")
+    _precise_hamer_args(ap)
     _render_args(ap)
     return ap
+
+
+def _precise_hamer_args(ap: argparse.ArgumentParser) -> None:
+    ap.add_argument('--precise-hamer', action='store_true',
+                    help="run HaMeR in fp32 (the reference's arithmetic; results do not depend on batching) instead of fp16, at about a tenth of the speed")
+    ap.add_argument('--precise', action='store_true', help="every precise switch this driver has at once")
+
+
+def apply_precise_args(args) -> None:
+    """Set the config switches the precise flags stand for: ``--precise-detector`` -> ``yolo_opt.precise``, ``--precise-hamer``
+    -> ``hamer_opt.precise``, ``--precise-rootnet`` (d_infer) -> ``rgb_opt.precise``; ``--precise`` sets every one the driver has."""
+    everything = bool(getattr(args, "precise", False))
+    if everything or getattr(args, "precise_hamer", False):
+        hamer_opt.precise = True
+    if everything or getattr(args, "precise_detector", False):
+        from .config.yolo_config import yolo_opt
+        yolo_opt.precise = True
+    if hasattr(args, "precise_rootnet") and (everything or args.precise_rootnet):
+        from .rootnet.sar_config_stage_1 import rgb_opt
+        rgb_opt.precise = True
 
 
 def _render_args(ap: argparse.ArgumentParser) -> None:
@@ -1063,12 +1086,10 @@ def main(argv=None):
     k_real = load_intrinsics(args.intrinsics) if args.intrinsics else None
     if args.ckpt:
         hamer_opt.ckpt_path = args.ckpt
-    if args.yolo_weights or args.precise_detector:
+    if args.yolo_weights:
         from .config.yolo_config import yolo_opt
-        if args.yolo_weights:
-            yolo_opt.weights = args.yolo_weights
-        if args.precise_detector:
-            yolo_opt.precise = True
+        yolo_opt.weights = args.yolo_weights
+    apply_precise_args(args)
     # under `python -m torch.distributed.run --nproc-per-node N -m hamer_yolo_amd.infer ...` every rank takes its share of
     # the folder on its own GPU (RANK / LOCAL_RANK / WORLD_SIZE from the environment); a plain launch is one process
     from . import shard

@@ -35,6 +35,7 @@ EXPORTS = [
     "hm_option_count", "hm_gemm_px_grid", "hm_absmax16", "hm_mesh_overlay_workspace_bytes", "hm_mesh_overlay",
     "hm_sar_saigb", "hm_sar_graph_mix", "hm_sar_linear", "hm_sar_softargmax", "hm_sar_postprocess",
     "hm_conv2d_f32_relu", "hm_nchw3_to_nhwc8_f32", "hm_gap_linear_f32", "hm_sar_saigb_f32", "hm_sar_graph_mix_f32", "hm_sar_linear_f32",
+    "hm_gemm_f32", "hm_vit_attention_f32",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -222,6 +223,8 @@ def load() -> C.CDLL:
     lib.hm_sar_saigb_f32.argtypes = [vp, vp, vp, vp, vp, i, vp]
     lib.hm_sar_graph_mix_f32.argtypes = [vp, i, vp, i, vp, vp]
     lib.hm_sar_linear_f32.argtypes = [vp, i, i, vp, vp, vp, i, i, vp]
+    lib.hm_gemm_f32.argtypes = [C.POINTER(GemmArgs), vp]
+    lib.hm_vit_attention_f32.argtypes = [vp, vp, i, i, i, i, f, vp]
     lib.hm_prof_begin.argtypes = [i]
     lib.hm_prof_collect.argtypes = [C.POINTER(ProfRecord), i]
     lib.hm_prof_end.argtypes = []

@@ -63,6 +63,33 @@ def gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
     return out
 
 
+def gemm_f32(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: int = L.HM_EPI_F32,
+             resid: Optional[torch.Tensor] = None, resid_mod: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """hm_gemm_f32 (the precise route): out (M,N) fp32 = epilogue(x @ w.T + bias), x (M,K) and w (N,K) fp32 row-major;
+    epilogue HM_EPI_F32, HM_EPI_GELU or HM_EPI_RESID_F32 (+ resid[m % resid_mod], which may be `out` itself)."""
+    _dev(x, w, bias, resid, out)
+    M, K = x.shape
+    N = w.shape[0]
+    assert w.shape[1] == K and x.stride(1) == 1 and w.stride(1) == 1 and x.dtype == w.dtype == torch.float32
+    if out is None:
+        out = torch.empty(M, N, device=x.device, dtype=torch.float32)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32
+    a = L.GemmArgs(L.ptr(x), L.ptr(w), L.ptr(out), L.ptr(bias), L.ptr(resid), M, N, K, x.stride(0), w.stride(0),
+                   out.stride(0), resid.stride(0) if resid is not None else 0, resid_mod, epilogue, L.HM_DTYPE_F32)
+    L.check(L.load().hm_gemm_f32(C.byref(a), L.current_stream()), "hm_gemm_f32")
+    return out
+
+
+def vit_attention_f32(qkv: torch.Tensor, B: int, tokens: int, heads: int, head_dim: int, scale: float) -> torch.Tensor:
+    """hm_vit_attention_f32 (the precise route): qkv (B*tokens, 3*heads*head_dim) fp32 -> (B*tokens, heads*head_dim) fp32."""
+    _dev(qkv)
+    assert qkv.dtype == torch.float32 and qkv.is_contiguous() and qkv.shape == (B * tokens, 3 * heads * head_dim)
+    out = torch.empty(B * tokens, heads * head_dim, device=qkv.device, dtype=torch.float32)
+    L.check(L.load().hm_vit_attention_f32(L.ptr(qkv), L.ptr(out), B, tokens, heads, head_dim, scale, L.current_stream()),
+            "hm_vit_attention_f32")
+    return out
+
+
 def layernorm_accum(x: torch.Tensor, partials: torch.Tensor, bias: Optional[torch.Tensor], gamma: torch.Tensor,
                     beta: torch.Tensor, eps: float, out_dtype=torch.bfloat16) -> torch.Tensor:
     """x (M,D) f32 += bias + partials.sum(0) in place (partials (S,M,D) from gemm(k_split=S)); returns LayerNorm(x)."""

@@ -72,7 +72,8 @@ def broadcast_state_dict(sd: Optional[Dict[str, torch.Tensor]], device, src: int
     """Rank `src` holds the fp32 state dict `sd`; every rank returns it.  Three collectives in all: the key/shape table,
     ONE flat buffer of the GEMM matrices rounded to `half_dtype` (what the engine would round them to anyway: 1.3 GB instead
     of 2.6 GB for ViT-H) and ONE flat fp32 buffer of everything else.  The returned tensors are views of the two buffers;
-    GEMM matrices come back in `half_dtype`."""
+    GEMM matrices come back in `half_dtype`.  The flat buffer takes the engine's operand type: ``half_dtype=torch.float32``
+    carries the matrices unrounded, which is what the precise fp32 route (HamerEngine(dtype=torch.float32)) needs."""
     if not _multi():
         return {k: v.to(device) for k, v in sd.items()}
     rank = dist.get_rank()

@@ -24,10 +24,11 @@
 extern "C" {
 #endif
 
-#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
+#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32) and the additive fp32 HaMeR entry points (hm_gemm_f32, hm_vit_attention_f32; hm_hamer_forward, hm_patch_im2col and hm_cross_attention take HM_DTYPE_F32); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
 
 enum { HM_DTYPE_BF16 = 0, HM_DTYPE_F16 = 1,
-       HM_DTYPE_F32 = 2 /* the YOLOv7 detector path only (same value as HM_OUT_F32): see its section below */ };
+       HM_DTYPE_F32 = 2 /* same value as HM_OUT_F32.  The fp32 YOLOv7 route (its section below) and the precise HaMeR route
+                           (hm_hamer_forward, hm_gemm_f32, hm_patch_im2col, hm_cross_attention); every other entry point rejects it */ };
 
 /* GEMM epilogues */
 enum {
@@ -180,7 +181,7 @@ int hm_vit_attention_mx8(const void* qkv, void* out8, void* out_scales, int B, i
  * img [B][3][img_h][img_w_full] f32, window columns [x0, x0+win_w), conv k=patch, s=patch,
  * zero pad `pad` -> patches [B*gh*gw][3*patch*patch] 16-bit, K order (c, ky, kx). */
 int hm_patch_im2col(const float* img, void* patches, int B, int img_h, int img_w_full, int x0, int win_w,
-                    int patch, int pad, int dtype, void* stream);
+                    int patch, int pad, int dtype, void* stream);   /* HM_DTYPE_F32: fp32 patches (32-byte aligned) */
 
 /* Small f32 nn.Linear on f32-input MFMA: out[M][N] = act(x[M][K] . W[N][K]^T + bias) (+ resid).
  * act: 0 none, 1 gelu_erf.  Decoder layers (pose_transformer.py:40-124) and the read-out
@@ -197,6 +198,7 @@ int hm_broadcast_rows(const float* vec, float* out, int B, int D, void* stream);
  * k_off + h*dim_head, v at v_off + h*dim_head; out [B][heads*dim_head] f32.  dim_head == 64. */
 int hm_cross_attention(const float* q, const void* kv, int ldkv, int k_off, int v_off, float* out, int B, int tokens,
                        int heads, int dim_head, float scale, int dtype, void* stream);
+/* HM_DTYPE_F32: kv holds fp32 (32-byte aligned) and the softmax takes the accurate expf: the precise route. */
 
 /* MANO-shaped model parameters (smplx.MANOLayer buffers; mano_wrapper.py:12-30). */
 typedef struct hm_mano_model {
@@ -318,13 +320,20 @@ typedef struct hm_hamer_outputs {
   float* joints;   /* [B][21][3] */
   float* cam_t;    /* [B][3]     */
   float* kp2d;     /* [B][21][2] */
-  void* tokens;    /* optional [B*tokens][D] 16-bit copy of the backbone output, or NULL */
+  void* tokens;    /* optional [B*tokens][D] 16-bit copy of the backbone output (fp32 with HM_DTYPE_F32), or NULL */
 } hm_hamer_outputs;
 
 /* Bytes of workspace hm_hamer_forward needs for a batch of B crops. */
 size_t hm_hamer_workspace_bytes(const hm_hamer_weights* w, int B);
 
-/* img [B][3][img_h][img_w_full] f32 normalised crops -> outputs.  Enqueues ~300 kernels. */
+/* img [B][3][img_h][img_w_full] f32 normalised crops -> outputs.  Enqueues ~300 kernels.
+ *
+ * hm_hamer_weights.dtype == HM_DTYPE_F32 is the precise route (HAMER(..., dtype=torch.float32); the reference's fp32 CPU
+ * arithmetic, hamer.py:99-156 with an fp32 model): every `const void*` weight is fp32, hm_hamer_outputs.tokens (when asked
+ * for) is fp32, the workspace holds fp32 activations (hm_hamer_workspace_bytes sizes it).  tome_r, range_stats, the fp8
+ * pointers, *_colsum / *_bias_ln, kmean_* must be NULL and the prescale factors 0 or 1, else HM_ERR_ARG.  The backbone runs
+ * hm_layernorm (fp32 out), hm_gemm_f32 and hm_vit_attention_f32; every output is bias + one sum over K in a fixed order with
+ * the residual added behind it, at every B -- a hand's outputs are the same bytes alone, in any batch, at any position. */
 int hm_hamer_forward(const hm_hamer_weights* w, const float* img, int B, const hm_hamer_outputs* out,
                      void* workspace, size_t workspace_bytes, void* stream);
 
@@ -554,6 +563,22 @@ int hm_sar_graph_mix_f32(const float* lap, int ldl, const float* x, int N, float
  * activation (the second layer's logits, rows 0 .. 777 of hm_sar_softargmax's [799][B][1024] buffers).  K % 32 == 0
  * (zero-padded columns in both operands); x / w 16-byte aligned. */
 int hm_sar_linear_f32(const float* x, int M, int K, const float* w, const float* bias, float* y, int N, int logits, void* stream);
+
+/* ---- The precise (fp32) route of HaMeR (HAMER(..., dtype=torch.float32), load_hamer(path, precise=True)).
+ * nn.Linear in fp32 on v_mfma_f32_32x32x2_f32: C [M][ldc] f32 = epilogue(X [M][ldx] f32 . W [N][ldw]^T f32).  Replaces the
+ * fp32 aten::addmm behind Attention.qkv / .proj (vit.py:114,:124), Mlp.fc1 / .fc2 (vit.py:83,:85), PatchEmbed.proj (vit.py:172,
+ * after hm_patch_im2col) and CrossAttention.to_kv (pose_transformer.py:114).  args->dtype must be HM_DTYPE_F32; epilogues
+ * HM_EPI_F32 (acc + bias), HM_EPI_GELU (gelu_erf(acc + bias)), HM_EPI_RESID_F32 ((acc + bias) + resid[m % resid_mod][n], resid
+ * may alias C); C is fp32 in all three; bias may be NULL.  k_split, ln_*, out_scale must be unset.  Any M >= 1, any N >= 1,
+ * K % 32 == 0, ldx / ldw multiples of 4, X / W 16-byte aligned.  Every output's sum over K is ONE fmaf chain from zero in an
+ * order fixed by K alone (no split-K, no tile- or grid-dependent reduction): a row's result does not depend on M or on its
+ * position, and is within ~4.5e-7 * (1 + sum|x w|) of exact up to K = 5120. */
+int hm_gemm_f32(const hm_gemm_args* args, void* stream);
+/* Attention.forward core (vit.py:115-123) in fp32: qkv [B*192][3*heads*80] f32 (column = which*H*d + head*d + i) -> out
+ * [B*192][heads*80] f32, head-major.  q * scale first (vit.py:116-117), q k^T and P V on v_mfma_f32_16x16x4_f32, softmax with
+ * the row maximum subtracted, expf, a row sum in one fixed order and IEEE division.  tokens == 192 and head_dim == 80 only.
+ * A hand's result does not depend on B. */
+int hm_vit_attention_f32(const float* qkv, float* out, int B, int tokens, int heads, int head_dim, float scale, void* stream);
 
 /* Optional per-launch timing (HIP events on the launch stream); kinds below. */
 enum { HM_K_GEMM = 0, HM_K_LAYERNORM = 1, HM_K_ATTENTION = 2, HM_K_IM2COL = 3, HM_K_LINEAR_F32 = 4,
