@@ -268,10 +268,24 @@ __global__ __launch_bounds__(256) void sar_post_kernel(const float* __restrict__
 
 }  // namespace
 
+static int saigb_launch(const void* feat, const void* w, const float* bias, const float* tmpl, void* g, int B, int channels, void* stream) {
+  GemmP p{(const _Float16*)w, (const _Float16*)feat, g, bias, tmpl, 8 * NV, B * 64, channels, channels, channels, 0, 0, B};
+  return launch_gemm<G_SAIGB>(p, (hipStream_t)stream, "hm_sar_saigb");
+}
+
+// SAIGB on a backbone of `channels` feature channels (512: ResNet-34, 1024: ConvNeXt-base).  Only the K of the 1 x 1
+// convolution changes: its 6224 output channels, and so the [778][B][544] graph, are the same.
+extern "C" int hm_sar_saigb_ch(const void* feat, const void* w, const float* bias, const float* tmpl, void* g, int B, int channels,
+                               void* stream) {
+  if (!feat || !w || !bias || !tmpl || !g || B <= 0) return hm_set_error(HM_ERR_ARG, "hm_sar_saigb_ch: bad arguments");
+  if (channels != 512 && channels != 1024) return hm_set_error(HM_ERR_ARG, "hm_sar_saigb_ch: channels must be 512 or 1024");
+  if (((uintptr_t)feat | (uintptr_t)w) & 15) return hm_set_error(HM_ERR_ARG, "hm_sar_saigb_ch: feat and w must be 16-byte aligned");
+  return saigb_launch(feat, w, bias, tmpl, g, B, channels, stream);
+}
+
 extern "C" int hm_sar_saigb(const void* feat, const void* w, const float* bias, const float* tmpl, void* g, int B, void* stream) {
   if (!feat || !w || !bias || !tmpl || !g || B <= 0) return hm_set_error(HM_ERR_ARG, "hm_sar_saigb: bad arguments");
-  GemmP p{(const _Float16*)w, (const _Float16*)feat, g, bias, tmpl, 8 * NV, B * 64, 512, 512, 512, 0, 0, B};
-  return launch_gemm<G_SAIGB>(p, (hipStream_t)stream, "hm_sar_saigb");
+  return saigb_launch(feat, w, bias, tmpl, g, B, 512, stream);
 }
 
 extern "C" int hm_sar_graph_mix(const void* lap, int ldl, const void* x, int N, void* y, void* stream) {

@@ -49,15 +49,27 @@ def _parser() -> argparse.ArgumentParser:
                     help="run YOLOv7 in fp32 (the reference's CPU branch) instead of fp16: its boxes, at about twice the detector time")
     ap.add_argument('--precise-rootnet', action='store_true',
                     help="run the RootNet backbone and depth head in fp32, as the reference does, instead of fp16 (DESIGN §9)")
+    ap.add_argument('--rootnet-backbone', choices=('resnet34', 'convnext'), default=None,
+                    help="the SAR backbone of the RootNet checkpoint (rgb_opt.backbone / rgb_opt.in_channels: 512 / 1024); "
+                         "default: the config's (resnet34)")
     _precise_hamer_args(ap)
     _render_args(ap)
     return ap
+
+
+def apply_rootnet_backbone(args) -> None:
+    """``--rootnet-backbone`` -> ``rgb_opt.backbone`` and the ``rgb_opt.in_channels`` that goes with it."""
+    if getattr(args, "rootnet_backbone", None):
+        from .rootnet.sar_config_stage_1 import rgb_opt
+        rgb_opt.backbone = args.rootnet_backbone
+        rgb_opt.in_channels = {'resnet34': 512, 'convnext': 1024}[args.rootnet_backbone]
 
 
 def main(argv=None):
     """``python -m hamer_yolo_amd.d_infer --input <RGB_dir> --output <out_dir> --intrinsics <cam_K.txt>``."""
     args = _parser().parse_args(argv)
     apply_precise_args(args)
+    apply_rootnet_backbone(args)
     k_real = load_intrinsics(args.intrinsics)
     hamer = hamer_inference(hamer_opt)
     process_batch_manopara(args.input, args.output, k_real, hamer=hamer)

@@ -36,6 +36,7 @@ EXPORTS = [
     "hm_sar_saigb", "hm_sar_graph_mix", "hm_sar_linear", "hm_sar_softargmax", "hm_sar_postprocess",
     "hm_conv2d_f32_relu", "hm_nchw3_to_nhwc8_f32", "hm_gap_linear_f32", "hm_sar_saigb_f32", "hm_sar_graph_mix_f32", "hm_sar_linear_f32",
     "hm_gemm_f32", "hm_vit_attention_f32",
+    "hm_dwconv7_ln", "hm_ln_patchify2", "hm_stem4_im2col", "hm_sar_saigb_ch",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -225,6 +226,10 @@ def load() -> C.CDLL:
     lib.hm_sar_linear_f32.argtypes = [vp, i, i, vp, vp, vp, i, i, vp]
     lib.hm_gemm_f32.argtypes = [C.POINTER(GemmArgs), vp]
     lib.hm_vit_attention_f32.argtypes = [vp, vp, i, i, i, i, f, vp]
+    lib.hm_dwconv7_ln.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, f, i, vp]
+    lib.hm_ln_patchify2.argtypes = [vp, vp, vp, vp, i, i, i, i, f, i, vp]
+    lib.hm_stem4_im2col.argtypes = [vp, vp, i, i, i, i, vp]
+    lib.hm_sar_saigb_ch.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
     lib.hm_prof_begin.argtypes = [i]
     lib.hm_prof_collect.argtypes = [C.POINTER(ProfRecord), i]
     lib.hm_prof_end.argtypes = []

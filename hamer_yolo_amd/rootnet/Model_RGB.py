@@ -2,6 +2,7 @@
 ``get_model()`` -> object with ``estimate_root_depth_custom(img, K, bbox) -> float`` (absolute root depth) and
 ``calculate_k``; and the reference's own estimator ``run(input)`` (:500-570): the SAR hand-mesh head (SAIGB + GBBMR +
 SoftHeatmap) on the same ResNet-34 features, root depth from ResRootNet or a depth image, and ``post_processing`` (:428-480).
+``cfg.backbone = 'convnext'`` with ``cfg.in_channels = 1024`` runs the ConvNeXt-base SAR instead (ConvNextEngine; default route only).
 ``run_frames`` is the batched form: all hands of several frames through one backbone, one head, one RootNet and one
 post-process launch.  ``EstimateRGB(cfg, precise=True)`` (or ``cfg.precise``) runs the backbone, the depth head and the SAR
 head in fp32, as the reference does, on the fp32-input MFMA: deterministic and batch-invariant."""
@@ -12,6 +13,7 @@ import torch
 
 from .. import lib as L
 from .. import ops, synth
+from .convnext_engine import ConvNextEngine
 from .engine import RootNetEngine
 from .preprocessing import patch_boxes, patch_transforms, process_bbox, uvd2xyz
 from .sar import NV, SarHeadEngine, head_keys, sar_hand
@@ -58,14 +60,27 @@ class EstimateRGB:
         self.cfg = cfg
         self.mode = 'estimate'
         self.precise = bool(getattr(cfg, 'precise', False) if precise is None else precise)
-        if getattr(cfg, 'backbone', 'resnet34') != 'resnet34':
-            raise NotImplementedError(f"EstimateRGB: backbone {cfg.backbone!r} is not supported; only the resnet34 SAR "
-                                      "checkpoint runs here (the ConvNeXt SAR is out of scope)")
+        backbone = getattr(cfg, 'backbone', 'resnet34')
+        if backbone == 'convnext':
+            # SAR builds convnext_base only (Model_RGB.py:226-227), whose head takes cfg.in_channels = 1024 (:319)
+            if getattr(cfg, 'in_channels', None) != 1024:
+                raise NotImplementedError(f"EstimateRGB: backbone 'convnext' runs as ConvNeXt-base only, which needs cfg.in_channels "
+                                          f"== 1024 (got {getattr(cfg, 'in_channels', None)!r})")
+            if self.precise:
+                raise ValueError("EstimateRGB: the fp32 route (precise=True) of the convnext backbone does not exist yet; "
+                                 "precise=True runs with backbone='resnet34' only")
+        elif backbone != 'resnet34':
+            raise NotImplementedError(f"EstimateRGB: backbone {backbone!r} is not supported; the resnet34 and the convnext "
+                                      "(ConvNeXt-base, in_channels 1024) SAR checkpoints run here")
+        in_channels = 1024 if backbone == 'convnext' else 512
         ck = str(cfg.checkpoint)
         if ck.startswith("synthetic"):
             seed = int(ck.split(":")[1]) if ":" in ck else 0
-            net, root = synth.rootnet_state_dict(seed)
-            net = {**net, **synth.sar_head_state_dict(seed)}
+            if backbone == 'convnext':
+                net, root = synth.convnext_state_dict(seed), synth.convnext_rootnet_state_dict(seed)
+            else:
+                net, root = synth.rootnet_state_dict(seed)
+            net = {**net, **synth.sar_head_state_dict(seed, in_channels)}
         else:
             from ..utils.checkpoint import load_checkpoint
             checkpoint = load_checkpoint(ck)                       # FileNotFoundError when missing
@@ -74,9 +89,13 @@ class EstimateRGB:
         self.device = torch.device(cfg.device if torch.cuda.is_available() else 'cpu')
         if self.device.type != 'cuda':
             raise L.HipLibraryError("EstimateRGB runs on an MI355X only: the HIP hot path has no CPU fallback")
-        self.engine = RootNetEngine(net, root, device=self.device, dtype=torch.float32 if self.precise else torch.float16)
+        if backbone == 'convnext':
+            self.engine = ConvNextEngine(net, root, device=self.device, dtype=torch.float16)
+        else:
+            self.engine = RootNetEngine(net, root, device=self.device, dtype=torch.float32 if self.precise else torch.float16)
         self.rootnet = self.engine if root is not None else None
-        self.head = SarHeadEngine(net, device=self.device, precise=self.precise) if all(k in net for k in head_keys()) else None
+        self.head = (SarHeadEngine(net, device=self.device, precise=self.precise, in_channels=in_channels)
+                     if all(k in net for k in head_keys()) else None)
         self.mean = 255.0 * np.array([0.485, 0.456, 0.406])
         self.std = 255.0 * np.array([0.229, 0.224, 0.225])
 

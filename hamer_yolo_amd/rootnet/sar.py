@@ -44,13 +44,17 @@ def _pad(w: torch.Tensor, rows: int, cols: int) -> torch.Tensor:
     return out
 
 
-def host_weights(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """The engine's operands on the host, fp32 (cast to f16 / kept fp32 on upload): named by what the kernels take."""
+def host_weights(sd: Dict[str, torch.Tensor], in_channels: int = 512) -> Dict[str, torch.Tensor]:
+    """The engine's operands on the host, fp32 (cast to f16 / kept fp32 on upload): named by what the kernels take.
+    in_channels: the backbone's feature channels (512: ResNet-34, 1024: ConvNeXt-base), the K of SAIGB's 1 x 1 convolution."""
     missing = [k for k in head_keys() if k not in sd]
     if missing:
         raise KeyError(f"SAR head weights missing from the checkpoint: {missing[:4]}{' ...' if len(missing) > 4 else ''}")
     h = "head."
-    w = {"saigb_w": sd[h + "saigb.group.0.weight"].float().reshape(8 * NV, 512),
+    if tuple(sd[h + "saigb.group.0.weight"].shape[:2]) != (8 * NV, in_channels):
+        raise ValueError(f"head.saigb.group.0.weight has shape {tuple(sd[h + 'saigb.group.0.weight'].shape)}; a backbone of "
+                         f"{in_channels} channels needs ({8 * NV}, {in_channels}, 1, 1)")
+    w = {"saigb_w": sd[h + "saigb.group.0.weight"].float().reshape(8 * NV, in_channels),
          "saigb_b": sd[h + "saigb.group.0.bias"].float(),
          "template": sd[h + "saigb.template"].float().reshape(NV, 3)}
     for br in ("xy", "z"):
@@ -74,15 +78,20 @@ _F16_KEYS = ("saigb_w", "xy.lap0", "xy.w0", "xy.lap1", "xy.w1", "z.lap0", "z.w0"
 
 
 class SarHeadEngine:
-    def __init__(self, net_sd: Dict[str, torch.Tensor], device="cuda", precise: bool = False):
+    def __init__(self, net_sd: Dict[str, torch.Tensor], device="cuda", precise: bool = False, in_channels: int = 512):
+        if in_channels not in (512, 1024):
+            raise ValueError(f"SarHeadEngine: in_channels {in_channels} (512: ResNet-34 features, 1024: ConvNeXt-base features)")
+        if precise and in_channels != 512:
+            raise ValueError("SarHeadEngine: the fp32 route of the 1024-channel (ConvNeXt) head does not exist yet")
         if not torch.cuda.is_available():
             raise L.HipLibraryError("SarHeadEngine needs an MI355X (HIP device); there is no CPU fallback")
         self.lib = L.load()
         self.device = torch.device(device)
         self.precise = bool(precise)
+        self.in_channels = int(in_channels)
         self.act_dtype = torch.float32 if self.precise else torch.float16          # features, g, mix and h
         self.w = {k: v.to(self.device, torch.float16 if k in _F16_KEYS and not self.precise else torch.float32).contiguous()
-                  for k, v in host_weights(net_sd).items()}
+                  for k, v in host_weights(net_sd, self.in_channels).items()}
         self._ws: Dict[int, Dict[str, torch.Tensor]] = {}
         f = "_f32" if self.precise else ""
         self._saigb, self._mix, self._linear = (getattr(self.lib, n + f) for n in ("hm_sar_saigb", "hm_sar_graph_mix", "hm_sar_linear"))
@@ -101,11 +110,15 @@ class SarHeadEngine:
         return ws
 
     def saigb(self, feat: torch.Tensor) -> torch.Tensor:
-        """feat (B, 8, 8, 512) NHWC, f16 (fp32 when precise) -> the init graph [778][B][544] in the same dtype (a view of the
-        workspace)."""
+        """feat (B, 8, 8, in_channels) NHWC, f16 (fp32 when precise) -> the init graph [778][B][544] in the same dtype (a view
+        of the workspace)."""
         B = feat.shape[0]
-        assert feat.shape[1:] == (8, 8, 512) and feat.dtype == self.act_dtype and feat.is_contiguous()
+        assert feat.shape[1:] == (8, 8, self.in_channels) and feat.dtype == self.act_dtype and feat.is_contiguous()
         g = self._workspace(B)["g"]
+        if self.in_channels != 512:
+            L.check(self.lib.hm_sar_saigb_ch(L.ptr(feat), L.ptr(self.w["saigb_w"]), L.ptr(self.w["saigb_b"]), L.ptr(self.w["template"]),
+                                             L.ptr(g), B, self.in_channels, L.current_stream()), "hm_sar_saigb_ch")
+            return g
         L.check(self._saigb(L.ptr(feat), L.ptr(self.w["saigb_w"]), L.ptr(self.w["saigb_b"]), L.ptr(self.w["template"]),
                             L.ptr(g), B, L.current_stream()), "hm_sar_saigb")
         return g

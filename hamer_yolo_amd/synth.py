@@ -379,9 +379,45 @@ def rootnet_state_dict(seed: int = 0):
 SAR_NV, SAR_NJ, SAR_HM = 778, 21, 32
 
 
-def sar_head_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
+def convnext_state_dict(seed: int = 0, prefix: str = "backbone.") -> Dict[str, torch.Tensor]:
+    """Seeded weights with the keys and shapes of the reference's ConvNeXt-base SAR backbone (rootnet/convnext.py:66-114 under
+    ``backbone.``; pass ``prefix=""`` for the bare module's keys).  The classifier ``head.*`` (21841 x 1024), which the forward
+    never reads, is left out.  Widths keep every activation O(1): the depthwise and pointwise weights preserve unit variance
+    (GELU halves the second moment, pwconv2 makes up for it), LayerNorm weights are 1 +- 0.1.  The layer scale ``gamma`` is
+    0.1 .. 0.5, NOT the 1e-6 of the reference's initialisation: at 1e-6 the 36 blocks add nothing to the stream and a parity
+    test would cover the stem and the LayerNorms only."""
+    from .rootnet import convnext_arch as arch
+    sd: Dict[str, torch.Tensor] = {}
+    for key, shape in arch.key_shapes().items():
+        name = key[len(arch.PREFIX):]
+        if name.endswith("gamma"):
+            t = uniform(key, shape, 0.2, 0.3, seed=seed)
+        elif name.endswith("bias"):
+            t = uniform(key, shape, 0.1, 0.0, seed=seed)
+        elif len(shape) == 1:                                   # LayerNorm weight
+            t = uniform(key, shape, 0.1, 1.0, seed=seed)
+        else:
+            fan_in = 1
+            for d in shape[1:]:
+                fan_in *= d
+            gain = 1.5 if name.endswith("pwconv2.weight") else 1.0
+            t = uniform(key, shape, gain * (3.0 / fan_in) ** 0.5, 0.0, seed=seed)
+        sd[prefix + name] = t
+    return sd
+
+
+def convnext_rootnet_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
+    """``rootnet`` of a ConvNeXt SAR checkpoint: ResRootNet(inplanes=1024).depth_layer (rootnet/Model_RGB.py:254-260, :329)."""
+    return {"depth_layer.weight": uniform("convnext.depth_layer.weight", (1, 1024, 1, 1), 0.05, 0.02, seed=seed),
+            "depth_layer.bias": uniform("convnext.depth_layer.bias", (1,), 0.05, 0.3, seed=seed)}
+
+
+def sar_head_state_dict(seed: int = 0, in_channels: int = 512) -> Dict[str, torch.Tensor]:
     """Seeded weights with the ``head.*`` keys of the reference's SAR state dict (SARhead, rootnet/Model_RGB.py:198-222 with
-    resnet34: in_channels 512, 8 feature maps of 64 cells, 778 vertices, 21 joints, 32 x 32 heatmaps).
+    resnet34: in_channels 512, 8 feature maps of 64 cells, 778 vertices, 21 joints, 32 x 32 heatmaps).  in_channels = 1024 is
+    the ConvNeXt-base head: only SAIGB's 1 x 1 convolution changes shape, and its width is set for post-LayerNorm features
+    (unit variance, signed) so that its output has the variance the 512-channel head sees on ReLU features and the heatmaps
+    stay peaked; every other tensor is the 512-channel head's.
 
     Calibrated so the soft-argmax sees PEAKED heatmaps (a near-uniform softmax puts every coordinate at the centre and
     coordinate parity would prove nothing): the xy logits have a spread of ~3 after ``beta``, the z logits ~0.3 (depths of
@@ -390,7 +426,8 @@ def sar_head_state_dict(seed: int = 0) -> Dict[str, torch.Tensor]:
     sd: Dict[str, torch.Tensor] = {}
     h = "head."
     sd[h + "saigb.template"] = uniform(h + "saigb.template", (SAR_NV, 3), 0.08, 0.0, seed=seed)
-    sd[h + "saigb.group.0.weight"] = uniform(h + "saigb.group.0.weight", (8 * SAR_NV, 512, 1, 1), 0.11, 0.0, seed=seed)
+    saigb_hw = 0.11 if in_channels == 512 else (3.0 / in_channels) ** 0.5
+    sd[h + "saigb.group.0.weight"] = uniform(h + "saigb.group.0.weight", (8 * SAR_NV, in_channels, 1, 1), saigb_hw, 0.0, seed=seed)
     sd[h + "saigb.group.0.bias"] = uniform(h + "saigb.group.0.bias", (8 * SAR_NV,), 0.3, 0.0, seed=seed)
     cells = SAR_HM * SAR_HM
     for br, out_gain in (("reg_xy", 5.0), ("reg_z", 0.05)):

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32) and the additive fp32 HaMeR entry points (hm_gemm_f32, hm_vit_attention_f32; hm_hamer_forward, hm_patch_im2col and hm_cross_attention take HM_DTYPE_F32); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
+#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32) and the additive fp32 HaMeR entry points (hm_gemm_f32, hm_vit_attention_f32; hm_hamer_forward, hm_patch_im2col and hm_cross_attention take HM_DTYPE_F32) and the additive ConvNeXt SAR entry points (hm_dwconv7_ln, hm_ln_patchify2, hm_stem4_im2col, hm_sar_saigb_ch); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
 
 enum { HM_DTYPE_BF16 = 0, HM_DTYPE_F16 = 1,
        HM_DTYPE_F32 = 2 /* same value as HM_OUT_F32.  The fp32 YOLOv7 route (its section below) and the precise HaMeR route
@@ -502,6 +502,11 @@ int hm_mesh_overlay(const uint8_t* frames, int N, int H, int W, const double* K,
  * tmpl [778][3] f32 (head.saigb.template) -> g [778][B][544] f16: node v, hand b holds LeakyReLU_0.1(conv + bias) of
  * channels 8v .. 8v+7 x the 64 positions (the .view(-1, 778, 512) of NCHW), then the 3 template values, then 29 zeros. */
 int hm_sar_saigb(const void* feat, const void* w, const float* bias, const float* tmpl, void* g, int B, void* stream);
+/* hm_sar_saigb for a backbone of `channels` feature channels: 512 (the ResNet-34, the same bytes as hm_sar_saigb) or 1024
+ * (ConvNeXt-base): feat [B][8][8][channels] f16, w [6224][channels] f16; g as above (SAIGB's output channels do not depend on
+ * its input channels).  feat / w 16-byte aligned. */
+int hm_sar_saigb_ch(const void* feat, const void* w, const float* bias, const float* tmpl, void* g, int B, int channels,
+                    void* stream);
 /* The L . x of GraphConv.forward (:110-115) for all hands at once: y [778][N] f16 = lap [778][ldl] f16 . x [778][N] f16,
  * lap = adj / (rowsum(adj) + 1e-5) with columns 778 .. ldl-1 zero; ldl % 32 == 0, N % 8 == 0 (N = B * C). */
 int hm_sar_graph_mix(const void* lap, int ldl, const void* x, int N, void* y, void* stream);
@@ -579,6 +584,25 @@ int hm_gemm_f32(const hm_gemm_args* args, void* stream);
  * the row maximum subtracted, expf, a row sum in one fixed order and IEEE division.  tokens == 192 and head_dim == 80 only.
  * A hand's result does not depend on B. */
 int hm_vit_attention_f32(const float* qkv, float* out, int B, int tokens, int heads, int head_dim, float scale, void* stream);
+
+/* ---- The ConvNeXt-base SAR backbone (rootnet/convnext.py; EstimateRGB with backbone = 'convnext'): the kernels around its
+ * GEMMs.  The residual stream is fp32 NHWC [B][H][W][C]; the 16-bit outputs are the X operands of hm_gemm.  fp32 arithmetic,
+ * one rounding at the store; a pixel's bytes depend on C alone, not on B or on its position in the batch.  dtype:
+ * HM_DTYPE_BF16 or HM_DTYPE_F16.  fp32 pointers 16-byte aligned, 16-bit outputs 8-byte aligned; C % 4 == 0, C <= 1024. */
+
+/* Block.dwconv + Block.norm (convnext.py:28-29, :39-41): out [B*H*W][C] 16-bit = LayerNorm_C(depthwise 7 x 7 conv of x, zero
+ * padding 3, + bias) * gamma + beta.  w [49][C] fp32, tap-major (ky * 7 + kx): nn.Conv2d's [C][1][7][7] weight transposed. */
+int hm_dwconv7_ln(const float* x, const float* w, const float* bias, const float* gamma, const float* beta, void* out, int B, int H,
+                  int W, int C, float eps, int dtype, void* stream);
+/* downsample_layers[1..3] up to their GEMM (convnext.py:79-82): LayerNorm over C of every pixel of x, written into the row of its
+ * 2 x 2 patch: out [B*(H/2)*(W/2)][4C] 16-bit, column (ky * 2 + kx) * C + c (the Conv2d weight permuted to [2C][ky][kx][c]).
+ * H and W even. */
+int hm_ln_patchify2(const float* x, const float* gamma, const float* beta, void* out, int B, int H, int W, int C, float eps,
+                    int dtype, void* stream);
+/* The im2col of the stem (Conv2d(3, 128, 4, stride 4), convnext.py:74): img [B][3][H][W] fp32 planes (hm_crop_batch's output)
+ * -> patches [B*(H/4)*(W/4)][64] 16-bit: 48 values in the weight's (c, ky, kx) order, then 16 zeros (hm_gemm: K % 64 == 0).
+ * H % 4 == 0, W % 4 == 0. */
+int hm_stem4_im2col(const float* img, void* patches, int B, int H, int W, int dtype, void* stream);
 
 /* Optional per-launch timing (HIP events on the launch stream); kinds below. */
 enum { HM_K_GEMM = 0, HM_K_LAYERNORM = 1, HM_K_ATTENTION = 2, HM_K_IM2COL = 3, HM_K_LINEAR_F32 = 4,

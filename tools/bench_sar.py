@@ -3,7 +3,9 @@
 end-to-end estimator on prepared patches (ResNet-34 features + head + ResRootNet + post-process, what run_frames does after
 the crops) at B = 1 / 64 / 256 hands, synthetic weights.  Prints one JSON line per batch size with device milliseconds
 (median of --iters CUDA-event timings after --warmup) and the head's TFLOP/s.  --precise times the fp32 route
-(EstimateRGB(cfg, precise=True)) instead and adds "route" and the backbone's TFLOP/s to each line."""
+(EstimateRGB(cfg, precise=True)) instead and adds "route" and the backbone's TFLOP/s to each line.  --backbone convnext times
+the ConvNeXt-base SAR (ConvNextEngine + the 1024-channel head) the same way, with the backbone's TFLOP/s on 40.1 GFLOP per
+hand."""
 import argparse
 import json
 import os
@@ -58,11 +60,27 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--precise", action="store_true", help="time the fp32 route (backbone, RootNet and head in fp32)")
+    ap.add_argument("--backbone", choices=("resnet34", "convnext", "both"), default="resnet34",
+                    help="both: the ResNet-34 lines, then the ConvNeXt lines, from one process")
     a = ap.parse_args()
+    if a.precise and a.backbone != "resnet34":
+        ap.error("the fp32 route of the convnext backbone does not exist yet")
+    for backbone in (("resnet34", "convnext") if a.backbone == "both" else (a.backbone,)):
+        run(a, backbone)
+
+
+def run(a, backbone):
     dev = "cuda:0"
-    net, root = synth.rootnet_state_dict(0)
-    bb = RootNetEngine(net, root, device=dev, dtype=torch.float32 if a.precise else torch.float16)
-    head = SarHeadEngine(synth.sar_head_state_dict(0), device=dev, precise=a.precise)
+    convnext = backbone == "convnext"
+    if convnext:
+        from hamer_yolo_amd.rootnet import convnext_arch
+        from hamer_yolo_amd.rootnet.convnext_engine import ConvNextEngine
+        bb = ConvNextEngine(synth.convnext_state_dict(0), synth.convnext_rootnet_state_dict(0), device=dev)
+        head = SarHeadEngine(synth.sar_head_state_dict(0, in_channels=1024), device=dev, in_channels=1024)
+    else:
+        net, root = synth.rootnet_state_dict(0)
+        bb = RootNetEngine(net, root, device=dev, dtype=torch.float32 if a.precise else torch.float16)
+        head = SarHeadEngine(synth.sar_head_state_dict(0), device=dev, precise=a.precise)
     K = np.array([[906.96, 0, 960], [0, 906.79, 540], [0, 0, 1]])
     for B in [int(x) for x in a.batches.split(",")]:
         img = torch.randn(B, 3, 256, 256, device=dev)
@@ -83,6 +101,11 @@ def main():
         if a.precise:
             rec = {"route": "precise", **rec, "backbone_tflops": round(backbone_flop_per_hand() * B / t_bb / 1e9, 1),
                    "backbone_gflop_per_hand": round(backbone_flop_per_hand() / 1e9, 2)}
+        if convnext:
+            # (SAIGB's K is 1024 here: twice its flops in the head's count)
+            rec = {"backbone": "convnext", **rec, "backbone_tflops": round(convnext_arch.GFLOP_PER_HAND * B / t_bb, 1),
+                   "backbone_gflop_per_hand": convnext_arch.GFLOP_PER_HAND,
+                   "head_tflops": round((head_flop_per_hand() + 2 * 8 * NV * 512 * 64) * B / t_head / 1e9, 1)}
         print(json.dumps(rec), flush=True)
 
 
