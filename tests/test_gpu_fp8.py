@@ -5,6 +5,8 @@ tolerances below are those of the 16-bit GEMM tests; quantisers (LayerNorm -> MX
 the oracle's bytes except where a last-bit fp32 difference crosses an e4m3 rounding boundary.
 """
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -12,6 +14,9 @@ import torch
 import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import exact_data as ED  # noqa: E402
 
 from hamer_yolo_amd import lib as L
 from hamer_yolo_amd import ops, synth
@@ -34,19 +39,17 @@ def _operands(M, N, K, seed):
 
 
 def test_gemm_fp8_exact_integers():
-    """Small-integer e4m3 values and power-of-two scales: every product and sum is exact in fp32 -> bit-exact result,
-    which pins the operand and scale lane maps of v_mfma_scale_f32_16x16x128_f8f6f4 through the whole kernel."""
-    M, N, K = 272, 320, 384
-    xi = (torch.arange(M * K).reshape(M, K) * 7 % 9 - 4).float()                       # -4 .. 4
-    wi = ((torch.arange(N * K).reshape(N, K) * 5 + torch.arange(N)[:, None]) % 7 - 3).float()
-    x8 = xi.to(torch.float8_e4m3fn).view(torch.uint8)
-    w8 = wi.to(torch.float8_e4m3fn).view(torch.uint8)
-    xs = (127 + (torch.arange(K // 32)[:, None] * 3 + torch.arange(M)[None, :]) % 4 - 1).to(torch.uint8)     # 2^-1 .. 2^2
-    ws = torch.ldexp(torch.ones(N), (torch.arange(N) % 3 - 1).to(torch.int32))
-    ref = (Q.mx8_dequantize(x8, xs).double() @ (wi.double() * ws.double()[:, None]).t())
-    out = ops.gemm_fp8(x8.to(DEV), xs.to(DEV), w8.to(DEV), ws.to(DEV), None, L.HM_EPI_RESID_F32,
-                       resid=torch.zeros(M, N, device=DEV))
-    assert torch.equal(out.cpu().double(), ref)
+    """Hashed small-integer e4m3 values and hashed power-of-two scales (tests/exact_data.py): every product and sum is exact
+    in fp32 -> bit-exact result, and no operand element or scale repeats with a period along K, M or N, which pins the operand
+    and scale lane maps of v_mfma_scale_f32_16x16x128_f8f6f4 through the whole kernel (the faults this data sees are listed in
+    tests/test_exact_data_host.py)."""
+    for (M, N, K) in ED.GEMM_FP8:
+        x8, xs, w8, ws, xi, wi = ED.fp8_case(M, N, K)
+        ref = (Q.mx8_dequantize(x8, xs).double() @ (wi.double() * ws.double()[:, None]).t())
+        assert torch.equal(ref, ED.fp8_reference(xi, xs, wi, ws))                  # the oracle's dequantiser and the plain statement agree
+        out = ops.gemm_fp8(x8.to(DEV), xs.to(DEV), w8.to(DEV), ws.to(DEV), None, L.HM_EPI_RESID_F32,
+                           resid=torch.zeros(M, N, device=DEV))
+        ED.assert_exact(out.cpu().double(), ref, (M, N, K))
 
 
 @pytest.mark.parametrize("M,N,K", [(384, 3840, 1280), (768, 1280, 5120), (1040, 320, 256), (16, 64, 128)])

@@ -18,6 +18,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import exact_data as ED  # noqa: E402
 import hamer_precise_chain as PC  # noqa: E402
 
 from hamer_yolo_amd import lib as L  # noqa: E402
@@ -123,6 +124,80 @@ def test_gemm_f32_rows_do_not_depend_on_the_batch(name, K, N, epi):
     ref = ops.gemm_f32(x, w, bias, L.HM_EPI_F32)
     torch.cuda.synchronize()
     assert one.shape == (1, N - 32) and torch.equal(one[0], ref[777, :N - 32])
+
+
+def _f32_exact_epilogues(x, w, bias, resid, pos, xd, wd, what):
+    """bias, no bias, residual (into a new buffer and in place) and the positional residual (resid_mod = 192) of one
+    hm_gemm_f32 problem on exact-integer data, each torch.equal to the torch result.  xd / wd: the device operands."""
+    M, N = x.shape[0], w.shape[0]
+    acc = x @ w.t()
+    bd, rd = bias.cuda(), resid.cuda()
+    ED.assert_exact(ops.gemm_f32(xd, wd, bd, L.HM_EPI_F32), acc + bias, what + ("bias",))
+    ED.assert_exact(ops.gemm_f32(xd, wd, None, L.HM_EPI_F32), acc, what + ("no bias",))
+    ED.assert_exact(ops.gemm_f32(xd, wd, bd, L.HM_EPI_RESID_F32, resid=rd), acc + bias + resid, what + ("residual",))
+    ED.assert_exact(ops.gemm_f32(xd, wd, None, L.HM_EPI_RESID_F32, resid=rd), acc + resid, what + ("residual, no bias",))
+    inplace = rd.clone()
+    ops.gemm_f32(xd, wd, bd, L.HM_EPI_RESID_F32, resid=inplace, out=inplace)
+    ED.assert_exact(inplace, acc + bias + resid, what + ("residual in place",))
+    if pos is not None:
+        got = ops.gemm_f32(xd, wd, bd, L.HM_EPI_RESID_F32, resid=pos.cuda(), resid_mod=192)
+        ED.assert_exact(got, acc + bias + pos.repeat(M // 192, 1), what + ("resid_mod 192",))
+
+
+@pytest.mark.parametrize("M,N,K", ED.gemm_f32_shapes())
+def test_gemm_f32_exact_integers(M, N, K):
+    """hm_gemm_f32 (v_mfma_f32_32x32x2_f32) on hashed exact-integer data (tests/exact_data.py: x in -3..3, w in -2..2, bias in
+    -4..4, residual in -5..5; every sum below 2^24, so exact in fp32 whatever the order): bit-equal to torch at the six ViT-H
+    shapes of SHAPES at one and seven hands (64 x 64 tiles and 128 x 128 tiles) and at M = 1 with an N that fills no tile,
+    for the bias, no-bias, residual, in-place residual and positional (resid_mod = 192) epilogues.  The tolerance tests above
+    cannot tell an operand element read from a neighbouring K position from rounding; tests/test_exact_data_host.py shows
+    that this data can."""
+    x, w, bias, resid = ED.gemm_case(M, N, K, resid=5)
+    pos = ED.gemm_case(M, N, K, resid=5, resid_rows=192)[3] if M % 192 == 0 else None
+    _f32_exact_epilogues(x, w, bias, resid, pos, x.cuda(), w.cuda(), (M, N, K))
+
+
+def test_gemm_f32_exact_shapes_are_the_vit_h_shapes():
+    assert sorted(ED.GEMM_F32_KN) == sorted({(K, N) for (_, K, N, _) in SHAPES})
+    assert all(M == 1 and N % 64 != 0 for (M, N, K) in ED.GEMM_F32_RAGGED)            # partial tiles in both directions
+
+
+@pytest.mark.parametrize("M,N,K", ED.GEMM_F32_STRIDED)
+def test_gemm_f32_leading_dimensions_wider_than_the_row_exact(M, N, K):
+    """hm_gemm_f32 with ldx > K, ldw > K (multiples of 4, 16-byte aligned slices), ldc > N and ldr > N: X and W as column
+    slices of wider buffers whose other columns hold a non-zero value, C and the residual between sentinel columns that must
+    come back untouched; exact-integer data, torch.equal; one shape of whole 64 x 64 tiles and one ragged in M and N."""
+    SX, S = 7.0, -12345.0
+    x, w, bias, resid = ED.gemm_case(M, N, K, resid=5)
+
+    def sl(t, left, right, fill):
+        buf = torch.full((t.shape[0], left + t.shape[1] + right), fill, device="cuda")
+        view = buf[:, left:left + t.shape[1]]
+        view.copy_(t)
+        return buf, view
+
+    def untouched(buf, left, cols, fill):
+        return bool((buf[:, :left] == fill).all()) and bool((buf[:, left + cols:] == fill).all())
+
+    xb, xd = sl(x, 4, 8, SX)
+    wb, wd = sl(w, 8, 12, SX)
+    assert xd.stride(0) % 4 == 0 and wd.stride(0) % 4 == 0 and xd.data_ptr() % 16 == 0 and wd.data_ptr() % 16 == 0
+    pos = ED.gemm_case(M, N, K, resid=5, resid_rows=192)[3] if M % 192 == 0 else None
+    _f32_exact_epilogues(x, w, bias, resid, pos, xd, wd, (M, N, K, "strided X / W"))
+    acc = x @ w.t()
+    cb, cd = sl(torch.full((M, N), S), 3, 5, S)                        # C needs 4-byte alignment only
+    rb, rd = sl(resid, 1, 2, S)
+    before = rb.clone()
+    ops.gemm_f32(xd, wd, bias.cuda(), L.HM_EPI_RESID_F32, resid=rd, out=cd)
+    ED.assert_exact(cd, acc + bias + resid, (M, N, K, "strided C / resid"))
+    assert untouched(cb, 3, N, S) and torch.equal(rb, before)
+    ops.gemm_f32(xd, wd, bias.cuda(), L.HM_EPI_RESID_F32, resid=rd, out=rd)
+    ED.assert_exact(rd, acc + bias + resid, (M, N, K, "strided, in place"))
+    assert untouched(rb, 1, N, S)
+    cb.fill_(S)
+    ops.gemm_f32(xd, wd, bias.cuda(), L.HM_EPI_F32, out=cd)
+    ED.assert_exact(cd, acc + bias, (M, N, K, "strided C, bias"))
+    assert untouched(cb, 3, N, S) and untouched(xb, 4, K, SX) and untouched(wb, 8, K, SX)
 
 
 # ------------------------------------------------------------------------------------------------ 2. the attention kernel

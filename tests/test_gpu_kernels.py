@@ -6,6 +6,8 @@ difference is fp32 accumulation order (a value may flip one 16-bit ulp).  Intege
 work (crop) must be bit-exact.
 """
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -13,6 +15,9 @@ import torch
 import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import exact_data as ED  # noqa: E402
 
 from hamer_yolo_amd import lib as L
 from hamer_yolo_amd import ops, synth
@@ -32,40 +37,39 @@ def _ulp16(dtype):
 
 # ------------------------------------------------------------------------------------ GEMM
 def test_gemm_exact_integers_asymmetric():
-    """Small-integer operands: every product and partial sum is exact in fp32, so the result must
-    be bit-exact whatever the accumulation order; W asymmetric to catch transposed writes."""
-    M, N, K = 192, 256, 128
-    x = (torch.arange(M * K).reshape(M, K) % 7 - 3).float()
-    w = ((torch.arange(N * K).reshape(N, K) * 5 + torch.arange(N)[:, None]) % 5 - 2).float()
-    ref = x @ w.t()
-    for dt in (torch.bfloat16, torch.float16):
-        out = ops.gemm(x.to(DEV, dt), w.to(DEV, dt), epilogue=L.HM_EPI_F32)
-        assert torch.equal(out.cpu(), ref)
+    """Hashed small-integer operands (tests/exact_data.py): every product and partial sum is exact in fp32, so the result
+    must be bit-exact whatever the accumulation order, and every element of X and W differs from its neighbours along both
+    axes, so a transposed write or a misplaced operand element changes the result."""
+    for (M, N, K) in ED.GEMM_ASYMMETRIC:
+        x, w, _, _ = ED.gemm_case(M, N, K, bias=False)
+        ref = x @ w.t()
+        for dt in (torch.bfloat16, torch.float16):
+            out = ops.gemm(x.to(DEV, dt), w.to(DEV, dt), epilogue=L.HM_EPI_F32)
+            ED.assert_exact(out, ref, ("asymmetric", M, N, K, dt))
 
 
 def _tile_variant_exact(variant):
     lib = L.load()
     try:
         L.check(lib.hm_gemm_set_variant(variant))
-        for (M, N, K) in ((300, 260, 64), (513, 388, 128), (1000, 1284, 448), (700, 516, 192), (257, 260, 1280)):
-            x = (torch.arange(M * K).reshape(M, K) % 7 - 3).float()
-            w = ((torch.arange(N * K).reshape(N, K) * 5 + torch.arange(N)[:, None]) % 5 - 2).float()
-            bias = (torch.arange(N) % 9 - 4).float()
+        for (M, N, K) in ED.GEMM_TILE_VARIANTS:
+            x, w, bias, _ = ED.gemm_case(M, N, K)
             ref = x @ w.t() + bias
             out = ops.gemm(x.to(DEV, torch.bfloat16), w.to(DEV, torch.bfloat16), bias.to(DEV), L.HM_EPI_F32)
-            assert torch.equal(out.cpu(), ref), (variant, M, N, K)
+            ED.assert_exact(out, ref, (variant, M, N, K))
     finally:
         lib.hm_gemm_set_variant(-1)
 
 
 @pytest.mark.parametrize("variant", [0, 10, 24, 26])
 def test_gemm_tile_variants_exact(variant):
-    """Every tile / pipeline configuration the product library ships (what pick_variant can choose) on exact-integer data
-    (bit-exact whatever the summation order), ragged M and N, several K-tile counts (ring prologue / steady state / tail)."""
+    """Every tile / pipeline configuration the product library ships (what pick_variant can choose) on hashed exact-integer
+    data (bit-exact whatever the summation order; which operand index faults that data sees is tests/test_exact_data_host.py's
+    subject), ragged M and N, several K-tile counts (ring prologue / steady state / tail)."""
     _tile_variant_exact(variant)
 
 
-@pytest.mark.parametrize("hands", [16, 17, 23, 40, 45, 68, 72])
+@pytest.mark.parametrize("hands", ED.GEMM_TILE_RULE_HANDS)
 def test_gemm_tile_rule_exact_at_every_batch_size(hands):
     """Round 3: pick_variant's rate model (HM_OPT_GEMM_TILE_RULE = 0; 1 = round 2's 85 % rule) and the persistent kernel's grid
     (rounded UP to the 8 XCDs when there are fewer tiles than workgroups: 180 tiles -> 184 workgroups, four of them idle; all
@@ -73,20 +77,18 @@ def test_gemm_tile_rule_exact_at_every_batch_size(hands):
     come back bit-exact, for the three epilogues the choice depends on, and both rules agree."""
     M = hands * 192
     lib = L.load()
-    for (N, K, epi) in ((3840, 128, L.HM_EPI_STORE), (1280, 192, L.HM_EPI_RESID_F32), (5120, 128, L.HM_EPI_STORE)):
-        x = (torch.arange(M * K).reshape(M, K) % 7 - 3).float()
-        w = ((torch.arange(N * K).reshape(N, K) * 5 + torch.arange(N)[:, None]) % 5 - 2).float()
-        bias = (torch.arange(N) % 9 - 4).float()
+    for (N, K, epi_name) in ED.GEMM_TILE_RULE_NK:
+        epi = {"store": L.HM_EPI_STORE, "resid": L.HM_EPI_RESID_F32}[epi_name]
+        x, w, bias, r = ED.gemm_case(M, N, K, resid=5 if epi == L.HM_EPI_RESID_F32 else None)
         ref = x @ w.t() + bias
-        r = ((torch.arange(M * N).reshape(M, N) % 11) - 5).float() if epi == L.HM_EPI_RESID_F32 else None
         outs = []
         for rule in (0, 1):
             with L.option(L.HM_OPT_GEMM_TILE_RULE, rule):
                 out = ops.gemm(x.to(DEV, torch.float16), w.to(DEV, torch.float16), bias.to(DEV), epi,
                                resid=r.to(DEV) if r is not None else None)
             outs.append(out.float().cpu())
-        assert torch.equal(outs[0], ref + (r if r is not None else 0)), (hands, N, K, epi)
-        assert torch.equal(outs[0], outs[1])
+        ED.assert_exact(outs[0], ref + (r if r is not None else 0), (hands, N, K, epi_name))
+        ED.assert_exact(outs[1], outs[0], (hands, N, K, epi_name, "both rules"))
 
 
 def test_gemm_set_variant_accepts_shipped_tiles_only():
@@ -106,18 +108,15 @@ def test_gemm_deep_prefetch_variant_exact(dt):
     lib = L.load()
     try:
         L.check(lib.hm_gemm_set_variant(24))
-        for (M, N, K) in ((300, 260, 64), (513, 388, 128), (1000, 1284, 192), (700, 516, 448), (257, 260, 1280), (1536, 512, 5120)):
-            x = (torch.arange(M * K).reshape(M, K) % 7 - 3).float()
-            w = ((torch.arange(N * K).reshape(N, K) * 5 + torch.arange(N)[:, None]) % 5 - 2).float()
-            bias = (torch.arange(N) % 9 - 4).float()
-            resid = ((torch.arange(M * N).reshape(M, N) * 3) % 11 - 5).float()
+        for (M, N, K) in ED.GEMM_DEEP_PREFETCH:
+            x, w, bias, resid = ED.gemm_case(M, N, K, resid=5)
             ref = x @ w.t() + bias + resid
             xd, wd, bd, rd = x.to(DEV, dt), w.to(DEV, dt), bias.to(DEV), resid.to(DEV)
-            for _ in range(4):
+            for rep in range(4):
                 out = ops.gemm(xd, wd, bd, L.HM_EPI_RESID_F32, resid=rd)
-                assert torch.equal(out.cpu(), ref), (M, N, K)
-            o16 = ops.gemm(xd, wd, bd, L.HM_EPI_STORE)
-            assert torch.equal(o16.float().cpu(), (x @ w.t() + bias).to(dt).float()), (M, N, K)
+                ED.assert_exact(out, ref, (M, N, K, dt, "launch", rep))
+            o16 = ops.gemm(xd, wd, bd, L.HM_EPI_STORE)                  # (bf16 at K >= 1280: sums beyond +-256, rounded to nearest even)
+            ED.assert_exact(o16.float(), (x @ w.t() + bias).to(dt).float(), (M, N, K, dt, "16-bit store"))
     finally:
         lib.hm_gemm_set_variant(-1)
 
@@ -134,18 +133,16 @@ def _persistent_kernel_exact(dt, pv):
     shares), repeated launches as a race screen; the GELU epilogue bit-equal to the one-tile kernel's (variant 24)."""
     lib = L.load()
     try:
-        for (M, N, K) in ((2048, 256, 128), (2304, 2560, 128), (4096, 4096, 192), (2560, 10240, 128), (12288, 3840, 1280), (5120, 5120, 64 * 7)):
-            x = (torch.arange(M * K).reshape(M, K) % 7 - 3).float()
-            w = ((torch.arange(N * K).reshape(N, K) * 5 + torch.arange(N)[:, None]) % 5 - 2).float()
-            bias = (torch.arange(N) % 9 - 4).float()
+        for (M, N, K) in ED.GEMM_PERSISTENT:
+            x, w, bias, _ = ED.gemm_case(M, N, K)
             xd, wd, bd = x.to(DEV, dt), w.to(DEV, dt), bias.to(DEV)
             ref = (xd.float() @ wd.float().t()).cpu()                     # exact in fp32: small integers
             L.check(lib.hm_gemm_set_variant(pv))
             for rep in range(3):
                 o = ops.gemm(xd, wd, bd, L.HM_EPI_STORE)
-                assert torch.equal(o.float().cpu(), (ref + bias).to(dt).float()), (M, N, K, rep)
+                ED.assert_exact(o.float(), (ref + bias).to(dt).float(), (M, N, K, dt, "launch", rep))
             o = ops.gemm(xd, wd, None, L.HM_EPI_STORE)
-            assert torch.equal(o.float().cpu(), ref.to(dt).float()), (M, N, K, "no bias")
+            ED.assert_exact(o.float(), ref.to(dt).float(), (M, N, K, dt, "no bias"))
             # random operands, GELU: the same rounding order as the one-tile kernel, so bit-equal to it
             xr = _u("px", (M, K), 1.0, seed=M).to(DEV, dt)
             wr = _u("pw", (N, K), 0.05, seed=N).to(DEV, dt)
@@ -160,11 +157,10 @@ def _persistent_kernel_exact(dt, pv):
             assert torch.equal(g26[0], g24) and torch.equal(g26[1], g24) and torch.equal(s26, s24), (M, N, K)
         # shapes the persistent kernel does not take (ragged M / N, one K-step) fall back to the one-tile kernels
         L.check(lib.hm_gemm_set_variant(pv))
-        for (M, N, K) in ((300, 260, 64), (2048, 2048, 64), (1000, 1284, 192)):
-            x = (torch.arange(M * K).reshape(M, K) % 7 - 3).float()
-            w = ((torch.arange(N * K).reshape(N, K) * 5 + torch.arange(N)[:, None]) % 5 - 2).float()
+        for (M, N, K) in ED.GEMM_PERSISTENT_FALLBACK:
+            x, w, _, _ = ED.gemm_case(M, N, K, bias=False)
             o = ops.gemm(x.to(DEV, dt), w.to(DEV, dt), None, L.HM_EPI_STORE)
-            assert torch.equal(o.float().cpu(), (x @ w.t()).to(dt).float()), (M, N, K)
+            ED.assert_exact(o.float(), (x @ w.t()).to(dt).float(), (M, N, K, dt, "fall-back"))
     finally:
         lib.hm_gemm_set_variant(-1)
 
@@ -212,21 +208,18 @@ def test_gemm_inloop_residual_exact(dt):
     repeated launches as a race screen; and against the round-2 epilogue form (HM_OPT_RESID_IN_EPILOGUE) on random data,
     where the two differ by the position of one fp32 add."""
     lib = L.load()
-    for (M, N, K) in ((512, 1280, 1280), (768, 256, 1344), (256, 512, 5120), (2304, 1280, 1280)):
-        x = (torch.arange(M * K).reshape(M, K) % 7 - 3).float()
-        w = ((torch.arange(N * K).reshape(N, K) * 5 + torch.arange(N)[:, None]) % 5 - 2).float()
-        bias = (torch.arange(N) % 9 - 4).float()
-        resid = ((torch.arange(M * N).reshape(M, N) * 3 + torch.arange(N)[None, :] * 7) % 1021 - 510).float()
+    for (M, N, K) in ED.GEMM_INLOOP_RESIDUAL:
+        x, w, bias, resid = ED.gemm_case(M, N, K, resid=ED.GEMM_INLOOP_RESIDUAL_RANGE)
         xd, wd, bd, rd = x.to(DEV, dt), w.to(DEV, dt), bias.to(DEV), resid.to(DEV)
         ref = x @ w.t() + bias + resid
-        for _ in range(3):
-            assert torch.equal(ops.gemm(xd, wd, bd, L.HM_EPI_RESID_F32, resid=rd).cpu(), ref), (M, N, K)
+        for rep in range(3):
+            ED.assert_exact(ops.gemm(xd, wd, bd, L.HM_EPI_RESID_F32, resid=rd), ref, (M, N, K, dt, "launch", rep))
         inplace = rd.clone()
         ops.gemm(xd, wd, bd, L.HM_EPI_RESID_F32, resid=inplace, out=inplace)
-        assert torch.equal(inplace.cpu(), ref), (M, N, K)
-        assert torch.equal(ops.gemm(xd, wd, None, L.HM_EPI_RESID_F32, resid=rd).cpu(), ref - bias), (M, N, K)     # no bias
+        ED.assert_exact(inplace, ref, (M, N, K, dt, "in place"))
+        ED.assert_exact(ops.gemm(xd, wd, None, L.HM_EPI_RESID_F32, resid=rd), ref - bias, (M, N, K, dt, "no bias"))
         with L.option(L.HM_OPT_RESID_IN_EPILOGUE, 1):
-            assert torch.equal(ops.gemm(xd, wd, bd, L.HM_EPI_RESID_F32, resid=rd).cpu(), ref), (M, N, K)
+            ED.assert_exact(ops.gemm(xd, wd, bd, L.HM_EPI_RESID_F32, resid=rd), ref, (M, N, K, dt, "residual in the epilogue"))
     M, N, K = 1024, 1280, 5120
     a, wt = _u("ra", (M, K), 1.0, seed=1).to(DEV, dt), _u("rw", (N, K), 0.05, seed=2).to(DEV, dt)
     bb, rr = _u("rb", (N,), 0.5, seed=3).to(DEV), _u("rr", (M, N), 2.0, seed=4).to(DEV)
@@ -236,6 +229,64 @@ def test_gemm_inloop_residual_exact(dt):
     ref64 = (a.double() @ wt.double().t() + bb.double() + rr.double()).cpu()
     assert float((new - old).abs().max()) < 2e-5                         # one fp32 add moved: a few ulps of |x| <= ~10
     assert float((new.cpu().double() - ref64).abs().max()) <= float((old.cpu().double() - ref64).abs().max()) * 1.5 + 1e-6
+
+
+def _column_slice(t, left, right, fill):
+    """t (rows, cols) on the device as the columns left .. left + cols of a wider buffer whose other columns hold `fill`."""
+    buf = torch.full((t.shape[0], left + t.shape[1] + right), fill, dtype=t.dtype, device=DEV)
+    view = buf[:, left:left + t.shape[1]]
+    view.copy_(t)
+    return buf, view
+
+
+def _outside_untouched(buf, left, cols, fill):
+    return bool((buf[:, :left] == fill).all()) and bool((buf[:, left + cols:] == fill).all())
+
+
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("variant", [-1, 0, 10, 24, 26])
+def test_gemm_leading_dimensions_wider_than_the_row_exact(variant, dt):
+    """hm_gemm with ldx > K, ldw > K, ldc > N and ldr > N, as the forward calls it (activations, outputs and the residual
+    stream as column slices of wider buffers), on hashed exact-integer data: X and W are slices whose neighbouring columns
+    hold a non-zero value (a K loop that runs past the row, or rows taken at the wrong pitch, change the sums); C and the
+    residual are slices between sentinel columns that must come back untouched.  The default choice and every shipped tile
+    forced, on a shape of whole 256 x 256 tiles that the persistent kernel (16-bit store under 26) and the in-loop-residual
+    kernel (24, 26) take and on one ragged in M and N; 16-bit store, fp32 residual into a second buffer, and in place.
+    Slice offsets keep what hm_gemm demands: 16-byte aligned pointers, ldx / ldw % 8, ldc / ldr % 4 (ldc % 8 for the
+    persistent kernel)."""
+    lib = L.load()
+    SX, S16, S32 = 7.0, -1024.0, -12345.0
+    try:
+        L.check(lib.hm_gemm_set_variant(variant))
+        for (M, N, K) in ED.GEMM_STRIDED:
+            x, w, bias, resid = ED.gemm_case(M, N, K, resid=5)
+            ref = x @ w.t() + bias
+            xb, xd = _column_slice(x.to(dt), 8, 16, SX)
+            wb, wd = _column_slice(w.to(dt), 16, 8, SX)
+            bd = bias.to(DEV)
+            assert xd.stride(0) == K + 24 and wd.stride(0) == K + 24 and xd.data_ptr() % 16 == 0 and wd.data_ptr() % 16 == 0
+            what = (variant, M, N, K, dt)
+            # 16-bit store
+            cb, cd = _column_slice(torch.full((M, N), S16, dtype=dt), 8, 8, S16)
+            ops.gemm(xd, wd, bd, L.HM_EPI_STORE, out=cd)
+            ED.assert_exact(cd.float(), ref.to(dt).float(), what + ("16-bit store",))
+            assert _outside_untouched(cb, 8, N, S16), what
+            # fp32 residual, C and resid two slices of different pitch
+            cb, cd = _column_slice(torch.full((M, N), S32), 4, 4, S32)
+            rb, rd = _column_slice(resid, 8, 4, S32)
+            before = rb.clone()
+            ops.gemm(xd, wd, bd, L.HM_EPI_RESID_F32, resid=rd, out=cd)
+            ED.assert_exact(cd, ref + resid, what + ("residual",))
+            assert _outside_untouched(cb, 4, N, S32) and torch.equal(rb, before), what
+            # in place: x += X W^T + b on a slice of the wider residual stream
+            ops.gemm(xd, wd, bd, L.HM_EPI_RESID_F32, resid=rd, out=rd)
+            ED.assert_exact(rd, ref + resid, what + ("residual in place",))
+            assert _outside_untouched(rb, 8, N, S32), what
+            # the operands and their neighbours are as they were
+            assert _outside_untouched(xb, 8, K, SX) and _outside_untouched(wb, 16, K, SX), what
+            assert torch.equal(xd.float().cpu(), x) and torch.equal(wd.float().cpu(), w), what
+    finally:
+        lib.hm_gemm_set_variant(-1)
 
 
 @pytest.mark.parametrize("variant", [-1, 0, 10])

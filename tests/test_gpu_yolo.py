@@ -2,6 +2,7 @@
 letterbox (byte-exact), decode, NMS (index-exact) and the whole Detector.detect."""
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -9,6 +10,9 @@ import torch
 import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import exact_data as ED  # noqa: E402
 
 from hamer_yolo_amd import lib as L
 from hamer_yolo_amd import synth
@@ -65,11 +69,13 @@ def test_conv2d_nhwc_vs_torch(Ci, Co, k, s, H, W, dt):
 
 
 def test_conv_exact_integer_data():
-    x = (torch.arange(2 * 16 * 9 * 11).reshape(2, 16, 9, 11) % 5 - 2).float()
-    w = ((torch.arange(32 * 16 * 9).reshape(32, 16, 3, 3) * 7 + torch.arange(32)[:, None, None, None]) % 3 - 1).float()
-    ref = F.conv2d(x, w, torch.zeros(32), stride=1, padding=1)
-    y = _conv_gpu(x, w, torch.zeros(32), 3, 1, act=False, dt=torch.float16, out_f32=True)
-    assert torch.equal(y, ref)
+    """Hashed integers (tests/exact_data.py): every sum exact in fp32, every element of x and w distinct from its neighbours
+    along every axis (which index faults that sees: tests/test_exact_data_host.py)."""
+    for (n, Ci, Co, k, s, H, W) in ED.CONV_BASIC:
+        x, w, _ = ED.conv_case(n, Ci, Co, k, H, W)
+        ref = F.conv2d(x, w, torch.zeros(Co), stride=s, padding=k // 2)
+        y = _conv_gpu(x, w, torch.zeros(Co), k, s, act=False, dt=torch.float16, out_f32=True)
+        ED.assert_exact(y, ref, (Ci, Co, k, s, H, W))
 
 
 @pytest.mark.parametrize("tile", [1, 2, 3, 4, 5, 6, 7, 8, 9])
@@ -80,14 +86,12 @@ def test_conv_every_tile_exact_and_equal(tile):
     M (not a multiple of any tile), Cout below and above the tile width, strided input and output slices -- must give the
     exact result, and on random data bit for bit what the default choice gives (same K order in every tile)."""
     with L.option(L.HM_OPT_CONV_TILE, tile):
-        for (Ci, Co, k, s, H, W) in ((16, 32, 3, 1, 9, 11), (32, 264, 3, 2, 21, 19), (64, 72, 1, 1, 33, 35), (8, 256, 3, 1, 30, 34)):
-            x = (torch.arange(2 * Ci * H * W).reshape(2, Ci, H, W) % 5 - 2).float()
-            w = ((torch.arange(Co * Ci * k * k).reshape(Co, Ci, k, k) * 7 + torch.arange(Co)[:, None, None, None]) % 3 - 1).float()
-            b = (torch.arange(Co) % 7 - 3).float()
+        for (n, Ci, Co, k, s, H, W) in ED.CONV_EVERY_TILE:
+            x, w, b = ED.conv_case(n, Ci, Co, k, H, W)
             ref = F.conv2d(x, w, b, stride=s, padding=k // 2)
-            assert torch.equal(_conv_gpu(x, w, b, k, s, act=False, dt=torch.float16, out_f32=True), ref), (tile, Ci, Co, k, s)
+            ED.assert_exact(_conv_gpu(x, w, b, k, s, act=False, dt=torch.float16, out_f32=True), ref, (tile, Ci, Co, k, s, "f32"))
             y = _conv_gpu(x, w, b, k, s, act=False, dt=torch.float16, ld_extra=8, y_extra=8)       # 16-bit store path, strided slices
-            assert torch.equal(y, ref.half().float()), (tile, Ci, Co, k, s)
+            ED.assert_exact(y, ref.half().float(), (tile, Ci, Co, k, s, "fp16"))
     x = synth.uniform("tx", (2, 128, 24, 40), 1.0, seed=3).half().float()
     w = synth.uniform("tw", (256, 128, 3, 3), 0.05, seed=4).half().float()
     b = synth.uniform("tb", (256,), 0.3, seed=5)
@@ -109,17 +113,14 @@ def test_conv_k_groups_exact_and_close(tile):
     random data within fp32 summation-order distance of the kernel without K groups (HM_OPT_CONV_KGROUPS = 1), and a frame gets
     the same bytes alone and inside a batch of five (the rule looks at one image)."""
     with L.option(L.HM_OPT_CONV_TILE, tile):
-        for (Ci, Co, k, s, H, W, ws) in ((128, 72, 3, 1, 12, 20, False), (128, 264, 3, 2, 47, 79, False), (512, 40, 1, 1, 24, 40, False),
-                                         (512, 64, 3, 1, 12, 20, True)):
-            x = (torch.arange(2 * Ci * H * W).reshape(2, Ci, H, W) % 5 - 2).float()
-            w = ((torch.arange(Co * Ci * k * k).reshape(Co, Ci, k, k) * 7 + torch.arange(Co)[:, None, None, None]) % 3 - 1).float()
-            b = (torch.arange(Co) % 7 - 3).float()
+        for (n, Ci, Co, k, s, H, W), ws in zip(ED.CONV_K_GROUPS, ED.CONV_K_GROUPS_SPLIT):
+            x, w, b = ED.conv_case(n, Ci, Co, k, H, W)
             ref = F.conv2d(x, w, b, stride=s, padding=k // 2)
-            wsb = torch.empty(8 * 2 * H * W * Co * 4, dtype=torch.uint8, device=DEV) if ws else None
+            wsb = torch.empty(8 * n * H * W * Co * 4, dtype=torch.uint8, device=DEV) if ws else None
             y = _conv_gpu(x, w, b, k, s, act=False, dt=torch.float16, ld_extra=8, y_extra=8, splitk_ws=wsb)
-            assert torch.equal(y, ref.half().float()), (tile, Ci, Co, k, s)
+            ED.assert_exact(y, ref.half().float(), (tile, Ci, Co, k, s, "fp16"))
             if not ws:
-                assert torch.equal(_conv_gpu(x, w, b, k, s, act=False, dt=torch.float16, out_f32=True), ref), (tile, Ci, Co, k, s)
+                ED.assert_exact(_conv_gpu(x, w, b, k, s, act=False, dt=torch.float16, out_f32=True), ref, (tile, Ci, Co, k, s, "f32"))
     x = synth.uniform("kx", (5, 256, 24, 40), 1.0, seed=3).half().float()
     w = synth.uniform("kw", (256, 256, 3, 3), 0.03, seed=4).half().float()
     b = synth.uniform("kb", (256,), 0.3, seed=5)
@@ -135,8 +136,7 @@ def test_conv_k_groups_exact_and_close(tile):
     assert (base - ref).abs().max() < 2e-3 and (plain - ref).abs().max() < 2e-3 and (base - plain).abs().max() < 2e-3
 
 
-@pytest.mark.parametrize("Ci,Co,k,s,H,W", [(64, 64, 3, 1, 23, 37), (128, 72, 3, 2, 47, 79), (256, 128, 1, 1, 24, 40), (128, 96, 5, 1, 13, 13),
-                                           (512, 264, 3, 1, 12, 20), (64, 40, 3, 2, 9, 11)])
+@pytest.mark.parametrize("Ci,Co,k,s,H,W", [c[1:] for c in ED.CONV_LEAN_LOADER])
 def test_conv_lean_loader_equals_the_general_loader(Ci, Co, k, s, H, W):
     """Round 4: with Cin % 64 == 0 a 64-deep K-step of the implicit GEMM lies inside one tap, and the lean loader keeps the K
     position in scalar registers and the in-image test as one bit of a per-lane mask (one 64-bit add, a bit test and a select per
@@ -154,17 +154,15 @@ def test_conv_lean_loader_equals_the_general_loader(Ci, Co, k, s, H, W):
         assert torch.equal(lean, gen), (Ci, Co, k, s, kw.keys())
     ref = F.silu(F.conv2d(x.double(), w.double(), b.double(), stride=s, padding=k // 2)).float()
     assert (lean - ref).abs().max() < 3e-3
-    xi = (torch.arange(3 * Ci * H * W).reshape(3, Ci, H, W) % 5 - 2).float()
-    wi = ((torch.arange(Co * Ci * k * k).reshape(Co, Ci, k, k) * 7 + torch.arange(Co)[:, None, None, None]) % 3 - 1).float()
-    bi = (torch.arange(Co) % 7 - 3).float()
-    assert torch.equal(_conv_gpu(xi, wi, bi, k, s, act=False, dt=torch.float16), F.conv2d(xi, wi, bi, stride=s, padding=k // 2).half().float())
+    xi, wi, bi = ED.conv_case(3, Ci, Co, k, H, W)
+    ED.assert_exact(_conv_gpu(xi, wi, bi, k, s, act=False, dt=torch.float16), F.conv2d(xi, wi, bi, stride=s, padding=k // 2).half().float(),
+                    (Ci, Co, k, s, H, W))
 
 
-@pytest.mark.parametrize("Ci,Co,k,s,H,W,nb", [(1024, 512, 1, 1, 12, 20, 40),     # 1x1, K = 1024 -> 2 ranges (one chain each), 128 x 128 tile
-                                              (256, 256, 3, 1, 12, 20, 72),      # 3x3, K = 2304 -> 4 ranges of 9 tiles: one chain each (odd count)
-                                              (512, 264, 3, 1, 12, 20, 48),      # K = 4608 -> 4 ranges of 18 tiles: even / odd sets inside a range; ragged N
-                                              (256, 128, 3, 1, 24, 40, 36),      # 24 x 40 map, K = 2304 -> 2 ranges of 18: two sets, 128 x 128 tile (3 accumulator sets)
-                                              (512, 64, 3, 2, 24, 40, 140)])     # stride 2 onto 12 x 20, narrow layer: 128 x 64 tile
+# ED.CONV_SERIAL_K, in order: 1x1, K = 1024 -> 2 ranges (one chain each), 128 x 128 tile; 3x3, K = 2304 -> 4 ranges of 9 tiles: one
+# chain each (odd count); K = 4608 -> 4 ranges of 18 tiles: even / odd sets inside a range, ragged N; 24 x 40 map, K = 2304 -> 2
+# ranges of 18: two sets, 128 x 128 tile (3 accumulator sets); stride 2 onto 12 x 20, narrow layer: 128 x 64 tile
+@pytest.mark.parametrize("Ci,Co,k,s,H,W,nb", [c[1:] + c[:1] for c in ED.CONV_SERIAL_K])
 def test_conv_serial_k_ranges_give_the_split_k_bytes(Ci, Co, k, s, H, W, nb):
     """Round 4: split-K is a rule on ONE image (a frame must get the same bytes alone and in a batch), but its slabs and reduce
     launch cost 15-30 % once a detector pass carries 48 frames.  From 256 tiles on, launch_conv hands the layer to
@@ -189,11 +187,9 @@ def test_conv_serial_k_ranges_give_the_split_k_bytes(Ci, Co, k, s, H, W, nb):
     assert torch.equal(auto, par) and torch.equal(auto[5:6], one)
     ref = F.silu(F.conv2d(x.double(), w.double(), b.double(), stride=s, padding=k // 2)).float()
     assert (auto - ref).abs().max() < 3e-3
-    xi = (torch.arange(nb * Ci * H * W).reshape(nb, Ci, H, W) % 5 - 2).float()
-    wi = ((torch.arange(Co * Ci * k * k).reshape(Co, Ci, k, k) * 7 + torch.arange(Co)[:, None, None, None]) % 3 - 1).float()
-    bi = (torch.arange(Co) % 7 - 3).float()
+    xi, wi, bi = ED.conv_case(nb, Ci, Co, k, H, W)
     yi = _conv_gpu(xi, wi, bi, k, s, act=False, dt=torch.float16, splitk_ws=ws)
-    assert torch.equal(yi, F.conv2d(xi, wi, bi, stride=s, padding=k // 2).half().float())
+    ED.assert_exact(yi, F.conv2d(xi, wi, bi, stride=s, padding=k // 2).half().float(), (Ci, Co, k, s, H, W, nb))
 
 
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
@@ -329,16 +325,15 @@ def test_conv_split_k_exact_and_close(dt):
     8 ranges and for the automatic choice (a rule on ONE image's output size, so a frame's result does not depend on the batch it
     rides in); on random data within fp32 summation-order distance of the unsplit kernel; a workspace smaller than
     hm_conv_splitk_bytes is an error."""
-    Ci, Co, H, W = 256, 256, 12, 20                                   # K = 2304 = 36 K tiles; 2 x 240 rows -> 4 x 1 tiles of 128 x 256
-    x = (torch.arange(2 * Ci * H * W).reshape(2, Ci, H, W) % 5 - 2).float()
-    w = ((torch.arange(Co * Ci * 9).reshape(Co, Ci, 3, 3) * 7 + torch.arange(Co)[:, None, None, None]) % 3 - 1).float()
-    b = (torch.arange(Co) % 7 - 3).float()
+    (n, Ci, Co, k, s, H, W), = ED.CONV_SPLIT_K                        # K = 2304 = 36 K tiles; 2 x 240 rows -> 4 x 1 tiles of 128 x 256
+    assert (n, k, s) == (2, 3, 1)
+    x, w, b = ED.conv_case(n, Ci, Co, k, H, W)
     ref = F.conv2d(x, w, b, stride=1, padding=1)
     ws = torch.full((8 * 2 * H * W * Co * 4 + 64,), 0xAB, dtype=torch.uint8, device=DEV)
     for ranges in (0, 2, 4, 8):
         with L.option(L.HM_OPT_CONV_SPLITK, ranges):
             y = _conv_gpu(x, w, b, 3, 1, act=False, dt=dt, ld_extra=8, y_extra=8, splitk_ws=ws[:-64])
-        assert torch.equal(y, ref.to(dt).float()), ranges
+        ED.assert_exact(y, ref.to(dt).float(), (dt, "ranges", ranges))
         assert bool((ws[-64:] == 0xAB).all())                        # nothing written past the workspace
     tiny = torch.empty(2 * H * W * Co * 4 * 2, dtype=torch.uint8, device=DEV)      # room for two slabs only: an error, never a
     with pytest.raises(L.HipLibraryError, match="splitk_ws too small"):            # silent change of the summation order

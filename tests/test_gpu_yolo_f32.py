@@ -8,6 +8,7 @@ and recorded in DESIGN.md."""
 import ctypes as C
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -15,6 +16,9 @@ import torch
 import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import exact_data as ED  # noqa: E402
 
 from hamer_yolo_amd import lib as L
 from hamer_yolo_amd import synth
@@ -108,12 +112,12 @@ def test_conv_f32_within_the_fp32_summation_bound(Ci, Co, k, s, H, W, N):
 
 
 def test_conv_f32_exact_integer_data_bit_equal():
-    for Ci, Co, k, s in ((16, 32, 3, 1), (64, 72, 3, 2), (256, 128, 1, 1)):
-        x = (torch.arange(2 * Ci * 9 * 11).reshape(2, Ci, 9, 11) % 5 - 2).float()
-        w = ((torch.arange(Co * Ci * k * k).reshape(Co, Ci, k, k) * 7 + torch.arange(Co)[:, None, None, None]) % 3 - 1).float()
-        b = (torch.arange(Co) % 7 - 3).float()
+    """Hashed integers (tests/exact_data.py): exact in fp32 whatever the summation order, and no two operand elements alike
+    along any axis (tests/test_exact_data_host.py lists the index faults that data sees)."""
+    for (n, Ci, Co, k, s, H, W) in ED.CONV_F32:
+        x, w, b = ED.conv_case(n, Ci, Co, k, H, W)
         ref = F.conv2d(x, w, b, stride=s, padding=k // 2)
-        assert torch.equal(_conv_f32(x, w, b, k, s, act=False), ref), (Ci, Co, k, s)
+        ED.assert_exact(_conv_f32(x, w, b, k, s, act=False), ref, (Ci, Co, k, s))
 
 
 # ------------------------------------------------------------------ 2. determinism and batch invariance
