@@ -1,0 +1,523 @@
+// Z-buffered mesh renderer (reference: hamer/utils/mesh_renderer.py MeshRenderer.__call__, :243-320, `color, rend_depth =
+// renderer.render(...)`): per view an RGBA image, a per-pixel depth map and a per-pixel mesh label, and optionally the
+// colour composed onto BGR frames.  The rule is stated in include/hamer_hip.h (hm_mesh_render) and DESIGN.md section 8.1;
+// tests/zrender_rule.py restates it in numpy.  It keeps the shape of render.hip: one workspace whose key buffer stays
+// 0xFF between calls, mesh records as kernel arguments, no host synchronisation.
+//  * normals - one thread per vertex walks its mesh's faces, staged in LDS 1024 at a time, and sums the fp64 face cross
+//              products of the faces that name it in ascending row order: no float atomics, one order.
+//  * setup   - one workgroup per mesh: per face the fp64 projection to 24.8 fixed point, the validity tests, the winding
+//              swap, 1/z per corner, the top-left ownership bits, the pixel box clipped to the view; the mesh's box, cut into
+//              16 x 16 tiles, appended to a work list through one atomic counter.
+//  * raster  - a grid-strided loop over the work list: per (mesh, tile) the faces are culled into LDS (ballot + prefix),
+//              one lane per pixel evaluates the edge functions at the pixel centre (int32 when the face's box spans less
+//              than 2^15 sub-pixel units, int64 otherwise), computes the fp64 perspective-correct depth of the covered
+//              (pixel, face) pairs only, and sends the smallest (fp32 depth bits, face id) key to the view's key buffer with
+//              one unsigned 64-bit atomicMin.
+//  * resolve - one pass over the views, four pixels per lane where the row length and the pointers allow 16-byte
+//              accesses: keys are read and reset in flagged tiles only, the winning face's barycentrics are recomputed, the
+//              vertex normals interpolated and shaded, and the requested outputs written.
+// The whole file is compiled without contraction, and every fp64 expression is written in the rule's order.
+#include <math.h>
+#include <algorithm>
+#include <vector>
+#include "common.h"
+#include "hamer_hip_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int TILE = 16;
+constexpr int MESHES_PER_LAUNCH = 48;              // kernel argument block stays under 4 KiB
+constexpr int NORMAL_CHUNK = 1024;                 // faces staged in LDS per step of the normals kernel
+constexpr unsigned long long NO_KEY = ~0ull;
+constexpr int F_SMALL = 1, F_OWN0 = 2, F_OWN1 = 4, F_OWN2 = 8;
+
+struct ZMesh {
+  hm_mesh m;
+  double k[6];                                     // K00 K01 K02 K10 K11 K12 of the mesh's view
+};
+struct ZMeshBlock {
+  ZMesh m[MESHES_PER_LAUNCH];
+  int count, first;
+};
+
+// Per face, written by setup, indexed by the global face id.  Corners are in the order the rule leaves them (1 and 2
+// swapped when the signed area was negative), in 24.8 fixed point.
+struct ZFace {
+  int x0, y0, x1, y1, x2, y2;
+  int flags, mesh;                                 // mesh: row of the mesh table
+  double area2;                                    // twice the area (> 0), exact
+  double r0, r1, r2;                               // 1 / z per corner
+  int v0, v1, v2, pad;                             // global vertex rows of the corners
+};
+struct ZTileFace {                                 // what raster keeps in LDS
+  int x0, y0, x1, y1, x2, y2;
+  int flags, j;                                    // j: the face's index inside its mesh
+  double area2, r0, r1, r2;
+};
+struct ZMeshRec { int view, f0, nf, pad; };
+
+struct ZLayout {
+  size_t keys, counter, flags, meshes, items, recs, boxes, normals, total;
+};
+
+size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+ZLayout layout(int N, int H, int W, int n_verts, int n_meshes, int n_faces) {
+  const size_t tiles = (size_t)((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
+  ZLayout L;
+  L.keys = 0;                                                          // N*H*W keys, first: their place never moves
+  L.counter = align256((size_t)N * H * W * 8);
+  L.flags = L.counter + 256;                                           // one byte per (view, tile): a key was written there
+  L.meshes = align256(L.flags + (size_t)N * tiles);
+  L.items = align256(L.meshes + (size_t)n_meshes * sizeof(ZMeshRec));
+  L.recs = align256(L.items + (size_t)n_meshes * tiles * sizeof(int2));
+  L.boxes = align256(L.recs + (size_t)n_faces * sizeof(ZFace));
+  L.normals = align256(L.boxes + (size_t)n_faces * sizeof(int4));
+  L.total = align256(L.normals + (size_t)n_verts * 3 * sizeof(double));
+  return L;
+}
+
+__device__ __forceinline__ long long edge64(int ax, int ay, int bx, int by, int px, int py) {
+  return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
+}
+__device__ __forceinline__ int edge32(int ax, int ay, int bx, int by, int px, int py) {
+  return (bx - ax) * (py - ay) - (by - ay) * (px - ax);
+}
+// Edge a -> b owns the samples on its line: a top edge or a left edge of a triangle of positive area.
+__device__ __forceinline__ bool owns(int ax, int ay, int bx, int by) {
+  const int dy = by - ay, dx = bx - ax;
+  return dy < 0 || (dy == 0 && dx > 0);
+}
+
+__device__ __forceinline__ unsigned rint_u8(double v) {
+  const double r = rint(v);
+  return !(r >= 0.0) ? 0u : (r > 255.0 ? 255u : (unsigned)r);          // not-a-number -> 0
+}
+
+// Grid (ceil(max nv / 256), meshes of the block): one thread per vertex.
+__global__ __launch_bounds__(256) void zrender_normals_kernel(ZMeshBlock mb, const double* __restrict__ verts,
+                                                              const int* __restrict__ faces, char* __restrict__ ws, ZLayout L) {
+  __shared__ int s_f[NORMAL_CHUNK * 3];
+  const hm_mesh m = mb.m[blockIdx.y].m;
+  if ((int)(blockIdx.x * 256) >= m.nv) return;                         // the whole workgroup leaves together
+  const int tid = threadIdx.x, v = blockIdx.x * 256 + tid;
+  const double* vb = verts + (size_t)m.v0 * 3;
+  double nx = 0.0, ny = 0.0, nz = 0.0;
+  for (int c0 = 0; c0 < m.nf; c0 += NORMAL_CHUNK) {
+    const int n = min(NORMAL_CHUNK, m.nf - c0);
+    for (int j = tid; j < n; j += 256) {
+      const size_t fid = (size_t)m.f0 + c0 + j;
+      const int a = faces[fid * 3], b = faces[fid * 3 + 1], c = faces[fid * 3 + 2];
+      const bool ok = a >= 0 && a < m.nv && b >= 0 && b < m.nv && c >= 0 && c < m.nv;
+      s_f[j * 3] = ok ? a : -1; s_f[j * 3 + 1] = ok ? b : -1; s_f[j * 3 + 2] = ok ? c : -1;
+    }
+    __syncthreads();
+    if (v < m.nv) {
+      for (int j = 0; j < n; ++j) {
+        const int a = s_f[j * 3], b = s_f[j * 3 + 1], c = s_f[j * 3 + 2];
+        if (a != v && b != v && c != v) continue;
+        const double* p0 = vb + (size_t)a * 3;
+        const double* p1 = vb + (size_t)b * 3;
+        const double* p2 = vb + (size_t)c * 3;
+        const double ax = p1[0] - p0[0], ay = p1[1] - p0[1], az = p1[2] - p0[2];
+        const double cx = p2[0] - p0[0], cy = p2[1] - p0[1], cz = p2[2] - p0[2];
+        nx = nx + (ay * cz - az * cy);
+        ny = ny + (az * cx - ax * cz);
+        nz = nz + (ax * cy - ay * cx);
+      }
+    }
+    __syncthreads();                                                   // the list is rewritten by the next chunk
+  }
+  if (v < m.nv) {
+    double* out = (double*)(ws + L.normals) + ((size_t)m.v0 + v) * 3;
+    out[0] = nx; out[1] = ny; out[2] = nz;
+  }
+}
+
+// One workgroup per mesh of the block.
+__global__ __launch_bounds__(256) void zrender_setup_kernel(ZMeshBlock mb, const double* __restrict__ verts,
+                                                            const int* __restrict__ faces, int H, int W, double znear,
+                                                            char* __restrict__ ws, ZLayout L) {
+  const int mi = blockIdx.x, tid = threadIdx.x;
+  const hm_mesh m = mb.m[mi].m;
+  const int mesh = mb.first + mi;
+  const double k00 = mb.m[mi].k[0], k01 = mb.m[mi].k[1], k02 = mb.m[mi].k[2];
+  const double k10 = mb.m[mi].k[3], k11 = mb.m[mi].k[4], k12 = mb.m[mi].k[5];
+  const double* vb = verts + (size_t)m.v0 * 3;
+  ZFace* recs = (ZFace*)(ws + L.recs);
+  int4* boxes = (int4*)(ws + L.boxes);
+  __shared__ int bx0, by0, bx1, by1, base;
+  if (tid == 0) { bx0 = INT_MAX; by0 = INT_MAX; bx1 = INT_MIN; by1 = INT_MIN; }
+  __syncthreads();
+  int lx0 = INT_MAX, ly0 = INT_MAX, lx1 = INT_MIN, ly1 = INT_MIN;
+  for (int j = tid; j < m.nf; j += 256) {
+    const size_t fid = (size_t)m.f0 + j;
+    int c[3] = {faces[fid * 3], faces[fid * 3 + 1], faces[fid * 3 + 2]};
+    bool ok = true;
+    int X[3] = {0, 0, 0}, Y[3] = {0, 0, 0};
+    double R[3] = {0, 0, 0};
+    for (int q = 0; q < 3; ++q) {
+      if (c[q] < 0 || c[q] >= m.nv) { ok = false; continue; }         // never read outside the mesh's vertices
+      const double x = vb[(size_t)c[q] * 3], y = vb[(size_t)c[q] * 3 + 1], z = vb[(size_t)c[q] * 3 + 2];
+      const double u = ((k00 * x + k01 * y) + k02 * z) / z;
+      const double v = ((k10 * x + k11 * y) + k12 * z) / z;
+      if (!(z >= znear) || !(fabs(u) < 65536.0) || !(fabs(v) < 65536.0)) { ok = false; continue; }
+      X[q] = (int)rint(256.0 * u); Y[q] = (int)rint(256.0 * v);      // |.| <= 2^24
+      R[q] = 1.0 / z;
+    }
+    int4 box = make_int4(1, 1, 0, 0);                                  // empty
+    ZFace r = {};
+    if (ok) {
+      long long area = edge64(X[0], Y[0], X[1], Y[1], X[2], Y[2]);
+      if (area < 0) {
+        int t = X[1]; X[1] = X[2]; X[2] = t;
+        t = Y[1]; Y[1] = Y[2]; Y[2] = t;
+        t = c[1]; c[1] = c[2]; c[2] = t;
+        const double d = R[1]; R[1] = R[2]; R[2] = d;
+        area = -area;
+      }
+      if (area != 0) {
+        const int fx0 = min(X[0], min(X[1], X[2])), fx1 = max(X[0], max(X[1], X[2]));
+        const int fy0 = min(Y[0], min(Y[1], Y[2])), fy1 = max(Y[0], max(Y[1], Y[2]));
+        r.x0 = X[0]; r.y0 = Y[0]; r.x1 = X[1]; r.y1 = Y[1]; r.x2 = X[2]; r.y2 = Y[2];
+        // E_i is the edge function of the edge opposite corner i: 1 -> 2, 2 -> 0, 0 -> 1
+        r.flags = ((fx1 - fx0) < 32768 && (fy1 - fy0) < 32768 ? F_SMALL : 0) | (owns(X[1], Y[1], X[2], Y[2]) ? F_OWN0 : 0) |
+                  (owns(X[2], Y[2], X[0], Y[0]) ? F_OWN1 : 0) | (owns(X[0], Y[0], X[1], Y[1]) ? F_OWN2 : 0);
+        r.mesh = mesh;
+        r.area2 = (double)area;
+        r.r0 = R[0]; r.r1 = R[1]; r.r2 = R[2];
+        r.v0 = m.v0 + c[0]; r.v1 = m.v0 + c[1]; r.v2 = m.v0 + c[2];
+        // pixels whose centre 256 p + 128 lies inside the corners' box (arithmetic shifts: floor), clipped to the view
+        box = make_int4(max((fx0 + 127) >> 8, 0), max((fy0 + 127) >> 8, 0), min((fx1 - 128) >> 8, W - 1), min((fy1 - 128) >> 8, H - 1));
+        if (box.x <= box.z && box.y <= box.w) {
+          lx0 = min(lx0, box.x); ly0 = min(ly0, box.y); lx1 = max(lx1, box.z); ly1 = max(ly1, box.w);
+        } else {
+          box = make_int4(1, 1, 0, 0);
+        }
+      }
+    }
+    recs[fid] = r;
+    boxes[fid] = box;
+  }
+  if (lx0 <= lx1) { atomicMin(&bx0, lx0); atomicMin(&by0, ly0); atomicMax(&bx1, lx1); atomicMax(&by1, ly1); }
+  __syncthreads();
+  const bool any = bx0 <= bx1;
+  const int tx0 = any ? bx0 / TILE : 0, ty0 = any ? by0 / TILE : 0;
+  const int ntx = any ? bx1 / TILE - tx0 + 1 : 0, nty = any ? by1 / TILE - ty0 + 1 : 0;
+  if (tid == 0) {
+    base = ntx * nty ? (int)atomicAdd((unsigned*)(ws + L.counter), (unsigned)(ntx * nty)) : 0;
+    ZMeshRec mr = {m.frame, m.f0, m.nf, 0};
+    ((ZMeshRec*)(ws + L.meshes))[mesh] = mr;
+  }
+  __syncthreads();
+  int2* items = (int2*)(ws + L.items);
+  for (int t = tid; t < ntx * nty; t += 256)
+    items[base + t] = make_int2(mesh, ((ty0 + t / ntx) << 16) | (tx0 + t % ntx));
+}
+
+__device__ __forceinline__ bool covered(long long e, bool own) { return e > 0 || (e == 0 && own); }
+
+// fp32 depth of a covered sample from its edge values: the rule's expression, in its order.
+__device__ __forceinline__ float sample_depth(double e0, double e1, double e2, double area2, double r0, double r1, double r2) {
+  const double l0 = e0 / area2, l1 = e1 / area2, l2 = e2 / area2;
+  const double q = (l0 * r0 + l1 * r1) + l2 * r2;
+  return (float)(1.0 / q);
+}
+
+// Grid-strided over the work list; one lane per pixel of a 16 x 16 tile.
+__global__ __launch_bounds__(256) void zrender_raster_kernel(int H, int W, char* __restrict__ ws, ZLayout L) {
+  __shared__ ZTileFace s_face[256];
+  __shared__ int s_wave[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned count = *(const unsigned*)(ws + L.counter);
+  const int2* items = (const int2*)(ws + L.items);
+  const ZMeshRec* meshes = (const ZMeshRec*)(ws + L.meshes);
+  const ZFace* recs = (const ZFace*)(ws + L.recs);
+  const int4* boxes = (const int4*)(ws + L.boxes);
+  unsigned long long* keys = (unsigned long long*)(ws + L.keys);
+  const int tiles_x = (W + TILE - 1) / TILE, tiles = tiles_x * ((H + TILE - 1) / TILE);
+  for (unsigned w = blockIdx.x; w < count; w += gridDim.x) {
+    const int2 it = items[w];
+    const ZMeshRec m = meshes[it.x];
+    const int tx = it.y & 0xFFFF, ty = it.y >> 16;
+    const int x0 = tx * TILE, y0 = ty * TILE;
+    const int px = x0 + (tid & (TILE - 1)), py = y0 + (tid >> 4);
+    const int sx = 256 * px + 128, sy = 256 * py + 128;                // the sample: the pixel's centre
+    unsigned long long best = NO_KEY;
+    for (int c0 = 0; c0 < m.nf; c0 += 256) {
+      // cull 256 faces against the tile into the LDS list
+      const int j = c0 + tid;
+      bool hit = false;
+      if (j < m.nf) {
+        const int4 b = boxes[(size_t)m.f0 + j];
+        hit = b.x <= b.z && b.x <= x0 + TILE - 1 && b.z >= x0 && b.y <= y0 + TILE - 1 && b.w >= y0;
+      }
+      const unsigned long long mask = __ballot(hit);
+      const int before = __popcll(mask & ((1ull << lane) - 1));
+      if (lane == 0) s_wave[wave] = __popcll(mask);
+      __syncthreads();
+      int off = 0, n = 0;
+      for (int q = 0; q < 4; ++q) { off += q < wave ? s_wave[q] : 0; n += s_wave[q]; }
+      if (hit) {
+        const ZFace r = recs[(size_t)m.f0 + j];
+        const ZTileFace t = {r.x0, r.y0, r.x1, r.y1, r.x2, r.y2, r.flags, j, r.area2, r.r0, r.r1, r.r2};
+        s_face[off + before] = t;
+      }
+      __syncthreads();
+      if (px < W && py < H) {
+        for (int q = 0; q < n; ++q) {
+          const ZTileFace& f = s_face[q];
+          const int fx0 = min(f.x0, min(f.x1, f.x2)), fx1 = max(f.x0, max(f.x1, f.x2));
+          const int fy0 = min(f.y0, min(f.y1, f.y2)), fy1 = max(f.y0, max(f.y1, f.y2));
+          if (sx < fx0 || sx > fx1 || sy < fy0 || sy > fy1) continue;    // inside the box every difference is < the span
+          double e0, e1, e2;
+          bool in;
+          if (f.flags & F_SMALL) {                                       // |e| < 2^31: two products below 2^30
+            const int a = edge32(f.x1, f.y1, f.x2, f.y2, sx, sy), b = edge32(f.x2, f.y2, f.x0, f.y0, sx, sy),
+                      c = edge32(f.x0, f.y0, f.x1, f.y1, sx, sy);
+            in = covered(a, f.flags & F_OWN0) && covered(b, f.flags & F_OWN1) && covered(c, f.flags & F_OWN2);
+            e0 = (double)a; e1 = (double)b; e2 = (double)c;
+          } else {
+            const long long a = edge64(f.x1, f.y1, f.x2, f.y2, sx, sy), b = edge64(f.x2, f.y2, f.x0, f.y0, sx, sy),
+                            c = edge64(f.x0, f.y0, f.x1, f.y1, sx, sy);
+            in = covered(a, f.flags & F_OWN0) && covered(b, f.flags & F_OWN1) && covered(c, f.flags & F_OWN2);
+            e0 = (double)a; e1 = (double)b; e2 = (double)c;
+          }
+          if (!in) continue;
+          const float d = sample_depth(e0, e1, e2, f.area2, f.r0, f.r1, f.r2);
+          const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(m.f0 + f.j);
+          if (key < best) best = key;
+        }
+      }
+      __syncthreads();                                               // the list is rewritten by the next chunk
+    }
+    if (best != NO_KEY) {
+      atomicMin(keys + ((size_t)m.view * H + py) * W + px, best);
+      ((unsigned char*)(ws + L.flags))[(size_t)m.view * tiles + ty * tiles_x + tx] = 1;
+    }
+  }
+}
+
+struct ZOut {
+  const uint8_t* frames;
+  uint8_t* out;
+  uint8_t* rgba;
+  float* depth;
+  int* mesh_id;
+  double base[3];
+  unsigned bg;                                     // R | G << 8 | B << 16 | A << 24: the bytes of an uncovered RGBA pixel
+};
+
+struct ZPixel { unsigned rgba; float depth; int mesh; };
+
+// The winning face of pixel (px, py), shaded.
+__device__ __forceinline__ ZPixel shade(unsigned long long key, int px, int py, const ZOut& o, const char* __restrict__ ws,
+                                        const ZLayout& L) {
+  const ZFace f = ((const ZFace*)(ws + L.recs))[(unsigned)key];
+  const double* nrm = (const double*)(ws + L.normals);
+  const int sx = 256 * px + 128, sy = 256 * py + 128;
+  const double e0 = (double)edge64(f.x1, f.y1, f.x2, f.y2, sx, sy), e1 = (double)edge64(f.x2, f.y2, f.x0, f.y0, sx, sy),
+               e2 = (double)edge64(f.x0, f.y0, f.x1, f.y1, sx, sy);
+  const double l0 = e0 / f.area2, l1 = e1 / f.area2, l2 = e2 / f.area2;
+  const double a0 = l0 * f.r0, a1 = l1 * f.r1, a2 = l2 * f.r2;
+  const double* n0 = nrm + (size_t)f.v0 * 3;
+  const double* n1 = nrm + (size_t)f.v1 * 3;
+  const double* n2 = nrm + (size_t)f.v2 * 3;
+  const double mx = (a0 * n0[0] + a1 * n1[0]) + a2 * n2[0];
+  const double my = (a0 * n0[1] + a1 * n1[1]) + a2 * n2[1];
+  const double mz = (a0 * n0[2] + a1 * n1[2]) + a2 * n2[2];
+  const double len = sqrt((mx * mx + my * my) + mz * mz);
+  const double t = len > 0.0 ? fabs(mz) / len : 0.0;
+  const double I = 0.3 + 0.7 * t;
+  ZPixel p;
+  p.rgba = rint_u8(255.0 * o.base[0] * I) | (rint_u8(255.0 * o.base[1] * I) << 8) | (rint_u8(255.0 * o.base[2] * I) << 16) | 0xFF000000u;
+  p.depth = __uint_as_float((unsigned)(key >> 32));
+  p.mesh = f.mesh;
+  return p;
+}
+
+// Block (64, 4); a lane owns PX consecutive pixels of one row (PX = 4: W % 4 == 0 and every pointer 16-byte aligned, so the
+// keys, RGBA, depth and label rows move 16 bytes at a time and the BGR rows 12).  Grid (ceil(W / (64 PX)), ceil(H / 4), N).
+template <int PX>
+__global__ __launch_bounds__(256) void zrender_resolve_kernel(ZOut o, int H, int W, char* __restrict__ ws, ZLayout L) {
+  const int x = (blockIdx.x * 64 + threadIdx.x) * PX, y = blockIdx.y * 4 + threadIdx.y, n = blockIdx.z;
+  if (x >= W || y >= H) return;
+  const int tiles_x = (W + TILE - 1) / TILE, tiles = tiles_x * ((H + TILE - 1) / TILE);
+  const size_t p = ((size_t)n * H + y) * W + x;
+  unsigned long long key[PX];
+#pragma unroll
+  for (int i = 0; i < PX; ++i) key[i] = NO_KEY;
+  if (((const unsigned char*)(ws + L.flags))[(size_t)n * tiles + (y / TILE) * tiles_x + x / TILE]) {   // PX divides TILE
+    unsigned long long* kp = (unsigned long long*)(ws + L.keys) + p;
+    bool any = false;
+    if (PX == 4) {
+      const ulonglong2 a = ((const ulonglong2*)kp)[0], b = ((const ulonglong2*)kp)[1];
+      key[0] = a.x; key[1] = a.y; key[2 % PX] = b.x; key[3 % PX] = b.y;
+    } else {
+      key[0] = kp[0];
+    }
+#pragma unroll
+    for (int i = 0; i < PX; ++i) any |= key[i] != NO_KEY;
+    if (any) {
+      if (PX == 4) {
+        const ulonglong2 ff = make_ulonglong2(NO_KEY, NO_KEY);
+        ((ulonglong2*)kp)[0] = ff; ((ulonglong2*)kp)[1] = ff;
+      } else {
+        kp[0] = NO_KEY;
+      }
+    }
+  }
+  unsigned rgba[PX];
+  float depth[PX];
+  int mesh[PX];
+  bool hit[PX];
+#pragma unroll
+  for (int i = 0; i < PX; ++i) {
+    hit[i] = key[i] != NO_KEY;
+    rgba[i] = o.bg; depth[i] = 0.0f; mesh[i] = -1;
+    if (hit[i]) {
+      const ZPixel s = shade(key[i], x + i, y, o, ws, L);
+      rgba[i] = s.rgba; depth[i] = s.depth; mesh[i] = s.mesh;
+    }
+  }
+  if (PX == 4) {
+    if (o.rgba) *(uint4*)(o.rgba + p * 4) = make_uint4(rgba[0], rgba[1 % PX], rgba[2 % PX], rgba[3 % PX]);
+    if (o.depth) *(float4*)(o.depth + p) = make_float4(depth[0], depth[1 % PX], depth[2 % PX], depth[3 % PX]);
+    if (o.mesh_id) *(int4*)(o.mesh_id + p) = make_int4(mesh[0], mesh[1 % PX], mesh[2 % PX], mesh[3 % PX]);
+    if (o.out) {
+      const unsigned* src = (const unsigned*)(o.frames + p * 3);       // 12 bytes: B G R B | G R B G | R B G R
+      const unsigned wds[3] = {src[0], src[1], src[2]};
+      unsigned b[12];                                                  // unrolled: the bytes stay in registers
+#pragma unroll
+      for (int k = 0; k < 12; ++k) b[k] = (wds[k >> 2] >> (8 * (k & 3))) & 255u;
+#pragma unroll
+      for (int i = 0; i < PX; ++i)
+        if (hit[i]) { b[i * 3] = (rgba[i] >> 16) & 255u; b[i * 3 + 1] = (rgba[i] >> 8) & 255u; b[i * 3 + 2] = rgba[i] & 255u; }
+      unsigned* dst = (unsigned*)(o.out + p * 3);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) dst[k] = b[4 * k] | (b[4 * k + 1] << 8) | (b[4 * k + 2] << 16) | (b[4 * k + 3] << 24);
+    }
+  } else {
+    if (o.rgba) *(unsigned*)(o.rgba + p * 4) = rgba[0];
+    if (o.depth) o.depth[p] = depth[0];
+    if (o.mesh_id) o.mesh_id[p] = mesh[0];
+    if (o.out) {
+      const uint8_t* src = o.frames + p * 3;
+      uint8_t* dst = o.out + p * 3;
+      dst[0] = hit[0] ? (uint8_t)(rgba[0] >> 16) : src[0];
+      dst[1] = hit[0] ? (uint8_t)(rgba[0] >> 8) : src[1];
+      dst[2] = hit[0] ? (uint8_t)rgba[0] : src[2];
+    }
+  }
+}
+
+int check_args(int N, int H, int W, const double* K, const double* verts, int n_verts, const int32_t* faces, int n_faces,
+               const hm_mesh* meshes, int n_meshes, const double* base_rgb, double znear, const uint8_t* frames, const uint8_t* out,
+               const uint8_t* rgba, const float* depth, const int32_t* mesh_id, const void* ws, size_t ws_bytes) {
+  if (!K || !ws) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: null pointer");
+  // the keys take 64-bit atomics and the face records hold doubles; the one-pixel resolve stores whole words
+  if ((uintptr_t)ws & 7) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: workspace must be 8-byte aligned");
+  if (((uintptr_t)rgba | (uintptr_t)depth | (uintptr_t)mesh_id) & 3)
+    return hm_set_error(HM_ERR_ARG, "hm_mesh_render: rgba, depth and mesh_id must be 4-byte aligned");
+  if (((uintptr_t)verts & 7) || ((uintptr_t)faces & 3)) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: verts must be 8-byte, faces 4-byte aligned");
+  if (N <= 0 || N > 65535 || H <= 0 || W <= 0 || H > 32767 || W > 32767)
+    return hm_set_error(HM_ERR_ARG, "hm_mesh_render: need 1 <= N <= 65535 and 1 <= H, W <= 32767");
+  if (n_meshes < 0 || n_verts < 0 || n_faces < 0) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: negative count");
+  if (n_meshes > 0 && !meshes) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: null mesh table");
+  if ((n_verts > 0 && !verts) || (n_faces > 0 && !faces)) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: null vertices or faces");
+  if (!(znear > 0.0) || !(znear < INFINITY)) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: znear must be a finite number > 0");
+  for (int n = 0; n < N; ++n)
+    if (!(K[n * 9 + 6] == 0.0 && K[n * 9 + 7] == 0.0 && K[n * 9 + 8] == 1.0))
+      return hm_set_error(HM_ERR_ARG, "hm_mesh_render: the last row of every K must be exactly (0, 0, 1)");
+  if (base_rgb)
+    for (int c = 0; c < 3; ++c)
+      if (!(base_rgb[c] >= 0.0 && base_rgb[c] <= 1.0)) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: base_rgb outside [0, 1]");
+  if (!out && !rgba && !depth && !mesh_id) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: no output requested");
+  if ((frames == nullptr) != (out == nullptr)) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: frames and out are given both or neither");
+  const size_t fb = (size_t)N * H * W * 3;
+  if (frames && frames < out + fb && out < frames + fb) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: out overlaps frames (never in place)");
+  for (int i = 0; i < n_meshes; ++i) {
+    const hm_mesh& m = meshes[i];
+    if (m.frame < 0 || m.frame >= N) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: mesh view outside the batch");
+    if (m.nv < 0 || m.nf < 0 || m.v0 < 0 || m.f0 < 0) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: negative mesh range");
+    if (m.nv == 0 && m.nf > 0) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: a mesh with faces but no vertices");
+    if ((long long)m.v0 + m.nv > n_verts || (long long)m.f0 + m.nf > n_faces)
+      return hm_set_error(HM_ERR_ARG, "hm_mesh_render: mesh range outside the vertex or face array");
+  }
+  // a face id names one face of one mesh, and a vertex row carries one normal: neither range is shared by two meshes.
+  // Sorted by their first row, overlapping ranges are neighbours.
+  std::vector<int> order;
+  for (int i = 0; i < n_meshes; ++i) order.push_back(i);
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return meshes[a].f0 < meshes[b].f0; });
+  long long end = 0;
+  for (int i : order) {
+    if (meshes[i].nf == 0) continue;
+    if (meshes[i].f0 < end) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: two meshes share faces");
+    end = (long long)meshes[i].f0 + meshes[i].nf;
+  }
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return meshes[a].v0 < meshes[b].v0; });
+  end = 0;
+  for (int i : order) {
+    if (meshes[i].nv == 0) continue;
+    if (meshes[i].v0 < end) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: two meshes share vertices");
+    end = (long long)meshes[i].v0 + meshes[i].nv;
+  }
+  if (ws_bytes < layout(N, H, W, n_verts, n_meshes, n_faces).total) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: workspace too small");
+  return HM_OK;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" size_t hm_mesh_render_workspace_bytes(int N, int H, int W, int n_verts, int n_meshes, int n_faces) {
+  if (N <= 0 || H <= 0 || W <= 0 || n_verts < 0 || n_meshes < 0 || n_faces < 0) return 0;
+  return layout(N, H, W, n_verts, n_meshes, n_faces).total;
+}
+
+extern "C" int hm_mesh_render(int N, int H, int W, const double* K_host, const double* verts, int n_verts, const int32_t* faces,
+                              int n_faces, const hm_mesh* meshes_host, int n_meshes, const double* base_rgb, const uint8_t* bg_rgba,
+                              double znear, const uint8_t* frames, uint8_t* out, uint8_t* rgba, float* depth, int32_t* mesh_id,
+                              void* workspace, size_t workspace_bytes, void* stream_) {
+  const int rc = check_args(N, H, W, K_host, verts, n_verts, faces, n_faces, meshes_host, n_meshes, base_rgb, znear, frames, out, rgba,
+                            depth, mesh_id, workspace, workspace_bytes);
+  if (rc != HM_OK) return rc;
+  hipStream_t s = (hipStream_t)stream_;
+  const ZLayout L = layout(N, H, W, n_verts, n_meshes, n_faces);
+  char* ws = (char*)workspace;
+  HmProfScope prof(HM_K_OTHER, 1, N, H, W, s);
+  if (hipMemsetAsync(ws + L.counter, 0, L.meshes - L.counter, s) != hipSuccess)     // counter and tile flags
+    return hm_set_error(HM_ERR_HIP, "hm_mesh_render: hipMemsetAsync");
+  for (int first = 0; first < n_meshes; first += MESHES_PER_LAUNCH) {
+    ZMeshBlock mb;
+    mb.first = first;
+    mb.count = n_meshes - first < MESHES_PER_LAUNCH ? n_meshes - first : MESHES_PER_LAUNCH;
+    int max_nv = 0;
+    for (int i = 0; i < mb.count; ++i) {
+      mb.m[i].m = meshes_host[first + i];
+      for (int c = 0; c < 6; ++c) mb.m[i].k[c] = K_host[(size_t)mb.m[i].m.frame * 9 + c];
+      max_nv = mb.m[i].m.nv > max_nv ? mb.m[i].m.nv : max_nv;
+    }
+    if (max_nv > 0)
+      hipLaunchKernelGGL(zrender_normals_kernel, dim3((max_nv + 255) / 256, mb.count), dim3(256), 0, s, mb, verts, faces, ws, L);
+    hipLaunchKernelGGL(zrender_setup_kernel, dim3(mb.count), dim3(256), 0, s, mb, verts, faces, H, W, znear, ws, L);
+  }
+  if (n_meshes > 0) {
+    const size_t upper = (size_t)n_meshes * ((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
+    const int grid = (int)(upper < 2048 ? upper : 2048);
+    hipLaunchKernelGGL(zrender_raster_kernel, dim3(grid), dim3(256), 0, s, H, W, ws, L);
+  }
+  ZOut o;
+  o.frames = frames; o.out = out; o.rgba = rgba; o.depth = depth; o.mesh_id = mesh_id;
+  o.base[0] = base_rgb ? base_rgb[0] : 1.0; o.base[1] = base_rgb ? base_rgb[1] : 1.0; o.base[2] = base_rgb ? base_rgb[2] : 0.9;
+  o.bg = bg_rgba ? (unsigned)bg_rgba[0] | ((unsigned)bg_rgba[1] << 8) | ((unsigned)bg_rgba[2] << 16) | ((unsigned)bg_rgba[3] << 24) : 0u;
+  const bool vec = W % 4 == 0 && aligned16(ws) && aligned16(rgba) && aligned16(depth) && aligned16(mesh_id) &&
+                   ((uintptr_t)frames & 3) == 0 && ((uintptr_t)out & 3) == 0;
+  if (vec)
+    hipLaunchKernelGGL(zrender_resolve_kernel<4>, dim3((W + 255) / 256, (H + 3) / 4, N), dim3(64, 4), 0, s, o, H, W, ws, L);
+  else
+    hipLaunchKernelGGL(zrender_resolve_kernel<1>, dim3((W + 63) / 64, (H + 3) / 4, N), dim3(64, 4), 0, s, o, H, W, ws, L);
+  return hm_check_launch("hm_mesh_render");
+}

@@ -80,6 +80,11 @@ def main(argv=None):
         from .render import render_folder
         rank, world = _rank_world(None, None)
         render_folder(args.input, args.output, args.render, hamer, k_real, style=args.render_style, rank=rank, world=world)
+    if args.hand_maps:
+        from .infer import _rank_world
+        from .render import hand_maps_folder
+        rank, world = _rank_world(None, None)
+        hand_maps_folder(args.input, args.output, args.hand_maps, hamer, k_real, label=args.hand_label, rank=rank, world=world)
 
 
 if __name__ == '__main__':

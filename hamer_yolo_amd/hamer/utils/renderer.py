@@ -1,8 +1,9 @@
 """Crop camera -> full-image camera (reference behaviour: hamer/hamer/utils/renderer.py:12-74 ``cam_crop_to_full`` /
 ``custom_cam_crop_to_full``).  The weak-perspective camera (s, tx, ty) predicted on the crop is moved into the frame of
 the full image: with ``bs = S * s`` the size of the hand box in focal-normalised units, depth is ``2 fx / bs`` and the
-principal-point offset of the box centre adds ``2 (c_box - c) / bs``.  The pyrender/trimesh renderer classes of that module
-are visualisation and out of scope."""
+principal-point offset of the box centre adds ``2 (c_box - c) / bs``.  The pyrender/trimesh ``Renderer`` class of that module
+is not restated; the ``MeshRenderer`` of utils/mesh_renderer.py, which infer.py builds, is: ``hamer/utils/mesh_renderer.py`` over
+the z-buffered GPU renderer."""
 import torch
 
 

@@ -6,7 +6,8 @@ Kept in Python (drop-in): ``hamer_inference`` (:117-528), ``matrix_to_axis_angle
 ``reconstruct_and_save_obj_with_wrapper`` (:1321-1436), ``load_intrinsics`` (:1458-1477) and the CLI
 (:1479-1536).  Pixel and tensor work is HIP: one ``hm_crop_batch`` launch for all hands of a frame
 (the reference crops hand by hand on the CPU and copies the frame per hand, :208) and one
-``hm_hamer_forward`` enqueue for the batch.  Out of scope: ONNX export/compare, pyrender overlays.
+``hm_hamer_forward`` enqueue for the batch.  ``get_mesh_renderer`` / ``get_image`` / ``image_fusion`` draw with the z-buffered
+GPU renderer (render.render_views).  Out of scope: ONNX export/compare, pyrender's own lighting.
 """
 from __future__ import annotations
 
@@ -89,11 +90,30 @@ class hamer_inference():
         self.mano = self.model.mano
 
     def get_mesh_renderer(self):
-        """infer.py:148-152 builds pyrender's MeshRenderer; no pyrender object is built here (returns None): the overlays are
-        drawn by render.render_folder / ``--render`` on the GPU.  The MANO model (with ``.faces``) is what
-        reconstruct_and_save_obj_with_wrapper needs."""
+        """infer.py:148-152: the ``MeshRenderer`` of hamer/utils/mesh_renderer.py over this model's MANO faces -- here the
+        z-buffered GPU renderer with the reference's call signature, no pyrender object.  Building it does no device work.
+        The MANO model (with ``.faces``) is what reconstruct_and_save_obj_with_wrapper needs."""
+        from .hamer.utils.mesh_renderer import MeshRenderer
         self.mano = self.model.mano
-        return None
+        return MeshRenderer(self.cfg, faces=self.mano.faces)
+
+    @torch.no_grad()
+    def get_image(self, dets, image, renderer):
+        """infer.py:531-599: one uint8 (H, W, 4) RGBA image per detection, the hand's mesh alone on a transparent frame of
+        the image's size.  ``dets``: a list of ``[label, [x1, y1, x2, y2]]`` or such a list nested once.  The reference
+        estimates and renders hand by hand; here ONE ``estimate_from_rgb`` and ONE render call serve all hands.  A left
+        hand's vertices are mirrored (x := -x) as in the OBJ and ``--render``.  The reference asks for ``side_view=True`` of
+        a ``__call__`` that ignores it: the front view is what it gets, and what this returns."""
+        if not (isinstance(dets, list) and len(dets) > 0):
+            return []
+        nested = isinstance(dets[0], list) and len(dets[0]) > 0 and isinstance(dets[0][0], list)
+        detection_list = dets[0] if nested else dets
+        out, _ = self.estimate_from_rgb(image, detection_list)
+        verts = out['pred_vertices'].float().clone()
+        verts[:, :, 0] = verts[:, :, 0] * (1.0 - 2.0 * out['do_flip'].view(-1, 1).to(verts.device))
+        H, W = int(image.shape[0]), int(image.shape[1])
+        rgba = renderer.render_hands(verts, out['pred_cam_t_full'], H, W, out['focal_length'])["rgba"].cpu().numpy()
+        return [rgba[i] for i in range(rgba.shape[0])]
 
     # ------------------------------------------------------------------ crop
     def _box_scalars(self, bboxs: List):
@@ -912,6 +932,17 @@ def process_batch(input_folder, output_folder, k_real=None, hamer=None, detector
     return stats
 
 
+def image_fusion(ori, mesh_images):
+    """infer.py:739-753: every mesh image in turn replaces the pixels of ``ori`` where any of its first three channels is
+    non-zero (``np.where``); later images win.  A mesh image's leading channels are taken as they are, as many as ``ori``
+    has (the reference needs a four-channel ``ori``).  Returns the result; no file is written."""
+    result = np.asarray(ori).copy()
+    for overlay_img in mesh_images:
+        mask = np.any(overlay_img[:, :, :3] > 0, axis=-1)
+        result = np.where(mask[:, :, np.newaxis], overlay_img[:, :, :result.shape[2]], result)
+    return result
+
+
 def get_bbox_from_npy(npy_path, target_val=3):
     """infer.py:1040-1072: tight box [x1, y1, x2, y2] (floats) around the pixels of a label mask equal to
     ``target_val``; None when the file or the label is missing."""
@@ -1076,8 +1107,13 @@ def apply_precise_args(args) -> None:
 def _render_args(ap: argparse.ArgumentParser) -> None:
     ap.add_argument('--render', type=str, default=None, metavar="DIR",
                     help="after the records are written, draw the hand meshes onto their frames into DIR (<name>.jpg)")
-    ap.add_argument('--render-style', type=str, default="flat", choices=["flat", "shaded"],
-                    help="flat: the reference's 0.6 green blend (reconstruct.py); shaded: opaque normal-shaded meshes")
+    ap.add_argument('--render-style', type=str, default="flat", choices=["flat", "shaded", "smooth"],
+                    help="flat: the reference's 0.6 green blend (reconstruct.py); shaded: opaque normal-shaded meshes; "
+                         "smooth: z-buffered per pixel, smooth-shaded (the MeshRenderer look)")
+    ap.add_argument('--hand-maps', type=str, default=None, metavar="DIR",
+                    help="after the records are written, write per frame into DIR the label mask <name>.npy (uint8, --hand-label on "
+                         "hand pixels) and <name>_maps.npz (depth in metres, index of the covering hand)")
+    ap.add_argument('--hand-label', type=int, default=3, help="the label --hand-maps writes on hand pixels (default 3)")
 
 
 def main(argv=None):
@@ -1110,6 +1146,10 @@ def main(argv=None):
         from .render import render_folder
         n = render_folder(args.input, args.output, args.render, hamer, k_real, style=args.render_style, rank=rank, world=world)
         print(f"{n} overlays written to {args.render}" + (f" (rank {rank})" if world > 1 else ""))
+    if args.hand_maps:
+        from .render import hand_maps_folder
+        n = hand_maps_folder(args.input, args.output, args.hand_maps, hamer, k_real, label=args.hand_label, rank=rank, world=world)
+        print(f"{n} hand maps written to {args.hand_maps}" + (f" (rank {rank})" if world > 1 else ""))
 
 
 if __name__ == '__main__':

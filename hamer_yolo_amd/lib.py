@@ -37,6 +37,7 @@ EXPORTS = [
     "hm_conv2d_f32_relu", "hm_nchw3_to_nhwc8_f32", "hm_gap_linear_f32", "hm_sar_saigb_f32", "hm_sar_graph_mix_f32", "hm_sar_linear_f32",
     "hm_gemm_f32", "hm_vit_attention_f32",
     "hm_dwconv7_ln", "hm_ln_patchify2", "hm_stem4_im2col", "hm_sar_saigb_ch",
+    "hm_mesh_render_workspace_bytes", "hm_mesh_render",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -213,6 +214,10 @@ def load() -> C.CDLL:
     lib.hm_mesh_overlay_workspace_bytes.argtypes = [i, i, i, i, i]
     lib.hm_mesh_overlay_workspace_bytes.restype = C.c_size_t
     lib.hm_mesh_overlay.argtypes = [vp, i, i, i, vp, vp, i, vp, i, C.POINTER(Mesh), i, i, d, vp, vp, C.c_size_t, vp]
+    lib.hm_mesh_render_workspace_bytes.argtypes = [i, i, i, i, i, i]
+    lib.hm_mesh_render_workspace_bytes.restype = C.c_size_t
+    lib.hm_mesh_render.argtypes = [i, i, i, C.POINTER(d), vp, i, vp, i, C.POINTER(Mesh), i, C.POINTER(d), C.POINTER(C.c_uint8), d,
+                                   vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.hm_sar_saigb.argtypes = [vp, vp, vp, vp, vp, i, vp]
     lib.hm_sar_graph_mix.argtypes = [vp, i, vp, i, vp, vp]
     lib.hm_sar_linear.argtypes = [vp, i, i, vp, vp, vp, i, i, vp]
@@ -238,7 +243,7 @@ def load() -> C.CDLL:
             raise HipLibraryError(f"{LIB_PATH} does not export {name}")
         fn = getattr(lib, name)
         if name not in ("hm_version", "hm_last_error_string", "hm_hamer_workspace_bytes", "hm_nms_workspace_bytes", "hm_tome_index_bytes", "hm_conv_splitk_bytes",
-                        "hm_mesh_overlay_workspace_bytes"):
+                        "hm_mesh_overlay_workspace_bytes", "hm_mesh_render_workspace_bytes"):
             fn.restype = i
     if lib.hm_version() != HM_VERSION:
         raise HipLibraryError(f"{LIB_PATH} reports HM_VERSION {lib.hm_version()}, this binding is written for {HM_VERSION}: "

@@ -1,12 +1,16 @@
 """Hand meshes drawn onto their frames on the GPU (reference: hamer/reconstruct.py project_and_draw / main, :50-178; the
-pyrender look of infer.py get_mesh_renderer / image_fusion and utils/mesh_renderer.py approximated by the ``shaded``
-style).  The drawing rule is stated in include/hamer_hip.h (hm_mesh_overlay) and DESIGN.md section 8.
+pyrender look of infer.py get_mesh_renderer / image_fusion and utils/mesh_renderer.py approximated per face by the ``shaded``
+style and per pixel by ``render_views``).  The drawing rule is stated in include/hamer_hip.h (hm_mesh_overlay) and DESIGN.md section 8.
 
 * ``overlay_frames``: device frames + meshes -> device frames, one hm_mesh_overlay call.
+* ``render_views``: meshes -> per view RGBA, depth and mesh-label maps resolved per pixel by a z-buffer (hm_mesh_render, DESIGN.md
+  section 8.1; reference utils/mesh_renderer.py:243-320), optionally drawn over frames: what ``MeshRenderer``, ``get_image``,
+  the ``smooth`` folder style and ``hand_maps_folder`` (``--hand-maps``: label mask, depth and hand index per frame) stand on.
 * ``render_folder``: the ``.npy`` records of a folder job -> one overlay image per frame with hands, a batched MANO forward per
   pass of equally sized frames, PIL encoding on a small thread pool."""
 from __future__ import annotations
 
+import ctypes as C
 import glob
 import os
 from concurrent.futures import ThreadPoolExecutor
@@ -54,6 +58,31 @@ def _mesh_color(m: dict, color_right, color_left):
     return tuple(color_right if m.get("is_right", True) else color_left)
 
 
+def _pack_meshes(meshes: Sequence[dict], dev: torch.device, N: int, color=None):
+    """The mesh table of one call and its concatenated device arrays: (table, verts fp64 (V,3), faces int32 (F,3), V, F)."""
+    table = (L.Mesh * max(len(meshes), 1))()
+    verts, faces, v0, f0 = [], [], 0, 0
+    checked = {}                                 # (id of a faces object, nv) -> its range is known good (one sync per object)
+    for i, m in enumerate(meshes):
+        v = torch.as_tensor(m["vertices"]).to(dev, torch.float64).reshape(-1, 3)
+        f = torch.as_tensor(m["faces"]).to(dev, torch.int32).reshape(-1, 3)
+        ck = (id(m["faces"]), v.shape[0])
+        if f.numel() and ck not in checked:
+            if v.shape[0] == 0 or int(f.min()) < 0 or int(f.max()) >= v.shape[0]:
+                raise ValueError(f"mesh {i}: face corner outside its {v.shape[0]} vertices")
+            checked[ck] = m["faces"]
+        if not 0 <= int(m["frame"]) < N:
+            raise ValueError(f"mesh {i}: frame {m['frame']} outside the batch of {N}")
+        t = table[i]
+        t.frame, t.v0, t.nv, t.f0, t.nf = int(m["frame"]), v0, v.shape[0], f0, f.shape[0]
+        if color is not None:
+            t.color_bgr[:] = color(m)
+        verts.append(v); faces.append(f); v0 += v.shape[0]; f0 += f.shape[0]
+    vd = torch.cat(verts).contiguous() if verts else torch.zeros(0, 3, dtype=torch.float64, device=dev)
+    fd = torch.cat(faces).contiguous() if faces else torch.zeros(0, 3, dtype=torch.int32, device=dev)
+    return table, vd, fd, v0, f0
+
+
 def overlay_frames(frames_dev: torch.Tensor, K, meshes: Sequence[dict], style: str = "flat", alpha: float = 0.6,
                    color_right=COLOR_RIGHT, color_left=COLOR_LEFT, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """frames_dev (N,H,W,3) uint8 BGR on the GPU; K (3,3) for every frame or (N,3,3); meshes: dicts with ``frame``,
@@ -71,25 +100,7 @@ def overlay_frames(frames_dev: torch.Tensor, K, meshes: Sequence[dict], style: s
     if tuple(Kt.shape) != (N, 3, 3):
         raise ValueError(f"K must be (3,3) or ({N},3,3), got {tuple(Kt.shape)}")
     Kd = Kt.contiguous().to(dev)
-    table = (L.Mesh * max(len(meshes), 1))()
-    verts, faces, v0, f0 = [], [], 0, 0
-    checked = {}                                 # (id of a faces object, nv) -> its range is known good (one sync per object)
-    for i, m in enumerate(meshes):
-        v = torch.as_tensor(m["vertices"]).to(dev, torch.float64).reshape(-1, 3)
-        f = torch.as_tensor(m["faces"]).to(dev, torch.int32).reshape(-1, 3)
-        ck = (id(m["faces"]), v.shape[0])
-        if f.numel() and ck not in checked:
-            if v.shape[0] == 0 or int(f.min()) < 0 or int(f.max()) >= v.shape[0]:
-                raise ValueError(f"mesh {i}: face corner outside its {v.shape[0]} vertices")
-            checked[ck] = m["faces"]
-        if not 0 <= int(m["frame"]) < N:
-            raise ValueError(f"mesh {i}: frame {m['frame']} outside the batch of {N}")
-        t = table[i]
-        t.frame, t.v0, t.nv, t.f0, t.nf = int(m["frame"]), v0, v.shape[0], f0, f.shape[0]
-        t.color_bgr[:] = _mesh_color(m, color_right, color_left)
-        verts.append(v); faces.append(f); v0 += v.shape[0]; f0 += f.shape[0]
-    vd = torch.cat(verts).contiguous() if verts else torch.zeros(0, 3, dtype=torch.float64, device=dev)
-    fd = torch.cat(faces).contiguous() if faces else torch.zeros(0, 3, dtype=torch.int32, device=dev)
+    table, vd, fd, v0, f0 = _pack_meshes(meshes, dev, N, lambda m: _mesh_color(m, color_right, color_left))
     if out is None:
         out = torch.empty_like(frames_dev)
     elif not (out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == tuple(frames_dev.shape) and out.is_contiguous()):
@@ -102,6 +113,70 @@ def overlay_frames(frames_dev: torch.Tensor, K, meshes: Sequence[dict], style: s
                                     L.ptr(fd) if f0 else None, f0, table, len(meshes), STYLES[style], float(alpha), L.ptr(out),
                                     L.ptr(ws), ws.numel(), L.current_stream()), "hm_mesh_overlay")
     return out
+
+
+RENDER_OUTPUTS = ("rgba", "depth", "mesh_id")
+BASE_COLOR = (1.0, 1.0, 0.9)       # MeshRenderer's default baseColorFactor, R G B
+
+
+def render_views(H: int, W: int, K, meshes: Sequence[dict], *, frames: Optional[torch.Tensor] = None,
+                 outputs: Sequence[str] = RENDER_OUTPUTS, base_color=BASE_COLOR, bg=(0, 0, 0, 0), znear: float = 0.05,
+                 views: Optional[int] = None, device=None) -> Dict[str, torch.Tensor]:
+    """The z-buffered renderer (hm_mesh_render; the rule is in include/hamer_hip.h and DESIGN.md section 8.1): N views of
+    H x W pixels, every mesh drawn into the view its ``frame`` names (the meshes format of ``overlay_frames``; colours are not
+    used).  K (3,3) for every view or (N,3,3), last row exactly (0, 0, 1).  Returns a dict of new device tensors, one per name
+    in ``outputs``: ``rgba`` (N,H,W,4) uint8 R G B A (uncovered: ``bg``), ``depth`` (N,H,W) float32 (uncovered 0),
+    ``mesh_id`` (N,H,W) int32, a mesh's position in ``meshes`` (uncovered -1); with ``frames`` (N,H,W,3) uint8 BGR on the
+    GPU also ``out``, the frames with the colour drawn over them.  N is ``views``, else the frames', else K's, else one more
+    than the largest ``frame``.  One call, enqueued on the current stream; the workspace is the overlay's (per device and
+    stream, ``release_workspaces``)."""
+    unknown = [o for o in outputs if o not in RENDER_OUTPUTS]
+    if unknown:
+        raise ValueError(f"outputs must be among {RENDER_OUTPUTS}, got {unknown}")
+    Kh = np.asarray(K.cpu() if torch.is_tensor(K) else K, dtype=np.float64)
+    if frames is not None:
+        if not (frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3
+                and tuple(frames.shape[1:3]) == (H, W)):
+            raise ValueError(f"frames must be a (N,{H},{W},3) uint8 GPU tensor")
+        frames = frames.contiguous()
+    elif not outputs:
+        raise ValueError("no output requested")
+    N = views if views is not None else frames.shape[0] if frames is not None else Kh.shape[0] if Kh.ndim == 3 else \
+        max([int(m["frame"]) for m in meshes], default=0) + 1
+    if frames is not None and frames.shape[0] != N:
+        raise ValueError(f"{frames.shape[0]} frames for {N} views")
+    Kh = np.broadcast_to(Kh, (N, 3, 3)) if Kh.ndim == 2 else Kh
+    if tuple(Kh.shape) != (N, 3, 3):
+        raise ValueError(f"K must be (3,3) or ({N},3,3), got {tuple(Kh.shape)}")
+    Kh = np.ascontiguousarray(Kh)
+    if device is not None:
+        dev = torch.device(device)
+    elif frames is not None:
+        dev = frames.device
+    else:
+        dev = next((m["vertices"].device for m in meshes if torch.is_tensor(m["vertices"]) and m["vertices"].is_cuda),
+                   torch.device("cuda", torch.cuda.current_device()))
+    table, vd, fd, v0, f0 = _pack_meshes(meshes, dev, N)
+    res = {}
+    if "rgba" in outputs:
+        res["rgba"] = torch.empty(N, H, W, 4, dtype=torch.uint8, device=dev)
+    if "depth" in outputs:
+        res["depth"] = torch.empty(N, H, W, dtype=torch.float32, device=dev)
+    if "mesh_id" in outputs:
+        res["mesh_id"] = torch.empty(N, H, W, dtype=torch.int32, device=dev)
+    if frames is not None:
+        res["out"] = torch.empty_like(frames)
+    base = (C.c_double * 3)(*[float(c) for c in base_color])
+    bgc = (C.c_uint8 * 4)(*[int(c) for c in bg])
+    lib = L.load()
+    need = lib.hm_mesh_render_workspace_bytes(N, H, W, v0, len(meshes), f0)
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, L.current_stream(), need, N * H * W * 8)
+        L.check(lib.hm_mesh_render(N, H, W, Kh.ctypes.data_as(C.POINTER(C.c_double)), L.ptr(vd) if v0 else None, v0,
+                                   L.ptr(fd) if f0 else None, f0, table, len(meshes), base, bgc, float(znear), L.ptr(frames),
+                                   L.ptr(res.get("out")), L.ptr(res.get("rgba")), L.ptr(res.get("depth")),
+                                   L.ptr(res.get("mesh_id")), L.ptr(ws), ws.numel(), L.current_stream()), "hm_mesh_render")
+    return res
 
 
 def default_camera(H: int, W: int, cfg) -> np.ndarray:
@@ -160,8 +235,8 @@ class PassWriter:
     """Encodes a pass's images on ``pool`` and keeps at most ``in_flight`` passes pending: submitting one more first waits
     for the oldest, so host memory holds a bounded number of decoded outputs however long the folder."""
 
-    def __init__(self, pool, in_flight: int = PASSES_IN_FLIGHT):
-        self.pool, self.in_flight, self.pending, self.written = pool, in_flight, [], 0
+    def __init__(self, pool, in_flight: int = PASSES_IN_FLIGHT, save=None):
+        self.pool, self.in_flight, self.pending, self.written, self.save = pool, in_flight, [], 0, save or _save
 
     def _finish_oldest(self):
         for f in self.pending.pop(0):
@@ -169,10 +244,10 @@ class PassWriter:
             self.written += 1
 
     def submit(self, items) -> None:
-        """items: (path, (H,W,3) uint8 BGR)."""
+        """items: (path, (H,W,3) uint8 BGR), or the arguments of the writer's own ``save``."""
         while len(self.pending) >= self.in_flight:
             self._finish_oldest()
-        self.pending.append([self.pool.submit(_save, p, img) for p, img in items])
+        self.pending.append([self.pool.submit(self.save, *item) for item in items])
 
     def close(self) -> int:
         while self.pending:
@@ -195,23 +270,13 @@ def render_folder(image_folder, npy_folder, out_folder, hamer, k_real=None, styl
     """Draw the hands of every ``<name>.npy`` record of ``npy_folder`` onto ``image_folder``'s ``<name>.*`` frame and write
     ``out_folder/<name><ext>`` (``.jpg`` as the reference; any extension PIL writes).  Frames are grouped by the size their
     headers give and drawn in passes of ``frames_per_pass``: per pass the frames are decoded, ONE MANO forward runs for all its
-    hands (the formulation of reconstruct_and_save_obj_with_wrapper), one overlay call, one copy back, and the encodes go to
+    hands (the formulation of reconstruct_and_save_obj_with_wrapper), one overlay call (``style`` "flat" or "shaded":
+    ``overlay_frames``; "smooth": the z-buffered ``render_views``), one copy back, and the encodes go to
     a ``PassWriter`` -- host memory stays bounded by a few passes whatever the folder's length.  ``k_real`` None: the camera
     the records were made with (``default_camera``).  ``rank`` / ``world``: this process draws ``shard_paths(records, rank,
     world)``.  Returns the number of images written; the overlay workspaces are released at the end."""
-    from .infer import _list_images, shard_paths
     os.makedirs(out_folder, exist_ok=True)
-    frames_by_stem = {os.path.splitext(os.path.basename(p))[0]: p for p in _list_images(image_folder)}
-    records = shard_paths(sorted(glob.glob(os.path.join(npy_folder, "*.npy"))), rank, world)
-    jobs = []
-    for npy in records:
-        stem = os.path.splitext(os.path.basename(npy))[0]
-        if stem not in frames_by_stem:
-            continue
-        data = np.load(npy, allow_pickle=True).item()
-        hands = [data[t] for t in ("right", "left") if data.get(t) is not None]
-        if hands:
-            jobs.append((stem, frames_by_stem[stem], hands))
+    jobs = _record_jobs(image_folder, npy_folder, rank, world, keep_empty=False)
     dev = hamer.device
     faces = torch.as_tensor(np.asarray(hamer.mano.faces, np.int32), device=dev)
     try:
@@ -230,9 +295,74 @@ def render_folder(image_folder, npy_folder, out_folder, hamer, k_real=None, styl
                 verts = camera_vertices(hamer, [h for _, h in hands])
                 meshes = [{"frame": n, "vertices": verts[j], "faces": faces, "is_right": bool(h["is_right"])}
                           for j, (n, h) in enumerate(hands)]
-                out = overlay_frames(torch.from_numpy(batch).to(dev), K, meshes, style=style)
+                if style == "smooth":
+                    out = render_views(H, W, K, meshes, frames=torch.from_numpy(batch).to(dev), outputs=())["out"]
+                else:
+                    out = overlay_frames(torch.from_numpy(batch).to(dev), K, meshes, style=style)
                 res = out.cpu().numpy()
                 writer.submit([(os.path.join(out_folder, jobs[i][0] + ext), res[n]) for n, i in enumerate(part)])
+            return writer.close()
+    finally:
+        release_workspaces()
+
+
+def _record_jobs(image_folder, npy_folder, rank: int, world: int, keep_empty: bool):
+    """(stem, frame path, hand records in right, left order) of this rank's share of the records that have a frame."""
+    from .infer import _list_images, shard_paths
+    frames_by_stem = {os.path.splitext(os.path.basename(p))[0]: p for p in _list_images(image_folder)}
+    jobs = []
+    for npy in shard_paths(sorted(glob.glob(os.path.join(npy_folder, "*.npy"))), rank, world):
+        stem = os.path.splitext(os.path.basename(npy))[0]
+        if stem not in frames_by_stem:
+            continue
+        data = np.load(npy, allow_pickle=True).item()
+        hands = [data[t] for t in ("right", "left") if data.get(t) is not None]
+        if hands or keep_empty:
+            jobs.append((stem, frames_by_stem[stem], hands))
+    return jobs
+
+
+def _save_maps(out_folder: str, stem: str, label: np.ndarray, depth: np.ndarray, hand: np.ndarray) -> None:
+    np.save(os.path.join(out_folder, stem + ".npy"), label)
+    np.savez_compressed(os.path.join(out_folder, stem + "_maps.npz"), depth=depth, hand=hand)
+
+
+def hand_maps_folder(image_folder, npy_folder, out_folder, hamer, k_real=None, label: int = 3, rank: int = 0, world: int = 1,
+                     frames_per_pass: int = FRAMES_PER_PASS) -> int:
+    """Per ``<stem>.npy`` record of ``npy_folder`` with a frame in ``image_folder``: which pixels its hands cover, how far
+    away, and which hand.  Writes ``out_folder/<stem>.npy``, uint8 (H, W) with ``label`` on hand pixels and 0 elsewhere -- the
+    label mask get_bbox_from_npy / process_batch_manopara_with_mask read -- and ``<stem>_maps.npz`` with ``depth`` (float32
+    metres, 0 = none) and ``hand`` (int8 index into the record's hands in right, left order, -1 = none).  The frame size comes
+    from the image header (``frame_size``): no frame is decoded.  Streams in passes like ``render_folder``: one MANO forward
+    and one ``render_views`` call per pass of equally sized frames.  A record without hands gets empty maps.  Returns the
+    number of records written; the workspaces are released at the end."""
+    if not 1 <= int(label) <= 255:
+        raise ValueError(f"label must be in 1..255, got {label}")
+    os.makedirs(out_folder, exist_ok=True)
+    jobs = _record_jobs(image_folder, npy_folder, rank, world, keep_empty=True)
+    dev = hamer.device
+    faces = torch.as_tensor(np.asarray(hamer.mano.faces, np.int32), device=dev)
+    try:
+        with ThreadPoolExecutor(_encode_threads()) as pool:
+            writer = PassWriter(pool, save=_save_maps)
+            sizes = list(pool.map(frame_size, [j[1] for j in jobs]))
+            for i in (i for i, hw in enumerate(sizes) if hw is None):
+                print(f"Skipping {jobs[i][0]}: image load failed")
+            for (H, W), part in size_passes(sizes, frames_per_pass):
+                K = np.asarray(k_real, np.float64) if k_real is not None else default_camera(H, W, hamer.cfg)
+                hands = [(n, h) for n, i in enumerate(part) for h in jobs[i][2]]
+                first = np.cumsum([0] + [len(jobs[i][2]) for i in part])[:-1]      # a frame's first row of the mesh table
+                meshes = []
+                if hands:
+                    verts = camera_vertices(hamer, [h for _, h in hands])
+                    meshes = [{"frame": n, "vertices": verts[j], "faces": faces} for j, (n, _) in enumerate(hands)]
+                r = render_views(H, W, K, meshes, outputs=("depth", "mesh_id"), views=len(part), device=dev)
+                mid = r["mesh_id"]
+                hand = torch.where(mid >= 0, mid - torch.as_tensor(first, dtype=torch.int32, device=dev)[:, None, None],
+                                   mid).to(torch.int8)
+                lab = ((mid >= 0).to(torch.uint8) * int(label)).cpu().numpy()
+                depth, hand = r["depth"].cpu().numpy(), hand.cpu().numpy()
+                writer.submit([(out_folder, jobs[i][0], lab[n], depth[n], hand[n]) for n, i in enumerate(part)])
             return writer.close()
     finally:
         release_workspaces()

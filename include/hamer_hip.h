@@ -493,6 +493,46 @@ int hm_mesh_overlay(const uint8_t* frames, int N, int H, int W, const double* K,
                     const int32_t* faces, int n_faces, const hm_mesh* meshes_host, int n_meshes, int style, double alpha,
                     uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Z-buffered mesh renderer (hamer/utils/mesh_renderer.py MeshRenderer.__call__, :243-320: `color, rend_depth =
+ * renderer.render(...)`): per view an RGBA image, a depth map and a mesh-label map, resolved per
+ * pixel.  The rule, stated once (tests/zrender_rule.py restates it in numpy).  Every fp64 expression is evaluated left to
+ * right as written, without contraction:
+ *  - geometry: vertices are camera-frame fp64, x right, y down, z forward.  K is given per view on the HOST and its last row
+ *    must be exactly (0, 0, 1).  u = ((K00*x + K01*y) + K02*z) / z, v = ((K10*x + K11*y) + K12*z) / z; fixed point
+ *    X = rint_half_even(256*u), Y = rint_half_even(256*v) (int64).  A face is skipped if a corner has z < znear (or z not a
+ *    number), if |u| or |v| >= 2^16 (or not a number), if a corner index lies outside [0, nv), or if twice its signed area
+ *    A = (X1-X0)*(Y2-Y0) - (Y1-Y0)*(X2-X0) is 0.  There is no near-plane clipping (a deviation from pyrender);
+ *  - coverage: pixel (px, py) is sampled at its centre (256*px + 128, 256*py + 128).  If A < 0, corners 1 and 2 are swapped
+ *    with everything they carry, and A := -A.  E_i is the edge function (bx-ax)*(py-ay) - (by-ay)*(px-ax) of the edge opposite
+ *    corner i (1->2, 2->0, 0->1) at the sample.  The pixel is covered if every E_i is > 0, or == 0 on an edge that owns its
+ *    boundary: edge a->b owns it when dy < 0, or dy == 0 and dx > 0 (the top-left rule), so faces that share an edge cover
+ *    each sample on it exactly once;
+ *  - depth: lambda_i = (double)E_i / (double)A, r_i = 1.0 / z_i, q = (lambda0*r0 + lambda1*r1) + lambda2*r2,
+ *    d = (float)(1.0 / q).  A pixel takes the covering face of smallest key (bits(d) << 32) | global face id: the nearest,
+ *    ties to the lower face row; the result depends neither on the order of the mesh table nor on scheduling;
+ *  - shading: the vertex normal n_v is the sum, from zero and in ascending face row, over the mesh's faces with three valid
+ *    corner indices that name v (once per face), of (p1-p0) x (p2-p0) in the face's own corner order, components
+ *    ay*cz - az*cy, az*cx - ax*cz, ax*cy - ay*cx.  At a pixel a_i = lambda_i*r_i, m_c = (a0*n0c + a1*n1c) + a2*n2c,
+ *    t = |m_z| / sqrt((m_x*m_x + m_y*m_y) + m_z*m_z) (0 when the length is not > 0), I = 0.3 + 0.7*t, and each channel is
+ *    rint_half_even(255*base_c*I) clamped to 0..255 (not-a-number gives 0).  Smooth, per pixel and two-sided: a left hand
+ *    needs no flipped faces.  It is the SHADED style's ambient + headlight term, not pyrender's BRDF;
+ *  - outputs, each optional (NULL), at least one: rgba u8 [N][H][W][4] in R G B A order (uncovered: bg_rgba; covered: the
+ *    colour, alpha 255); depth f32 [N][H][W] (uncovered 0.0f, covered d); mesh_id i32 [N][H][W] (uncovered -1, covered the
+ *    mesh's row in meshes_host); frames + out u8 BGR [N][H][W][3], both or neither, never overlapping (uncovered: the
+ *    frame's bytes; covered: the colour, opaque).
+ * hm_mesh.frame is the view; color_bgr is not used; two meshes share neither face rows nor vertex rows.  base_rgb: HOST
+ * double[3] in [0, 1], NULL = (1.0, 1.0, 0.9); bg_rgba: HOST u8[4], NULL = all 0; znear > 0 (pyrender's default is 0.05).
+ * The workspace's first N*H*W*8 bytes are the key buffer with hm_mesh_overlay's contract (0xFF on entry, 0xFF on return), so
+ * one 0xFF-filled workspace serves both entry points.  Launches: one memset, normals + setup per 48 meshes, raster, resolve;
+ * no host synchronisation; argument errors return HM_ERR_ARG before any device work.  Alignment: workspace and verts 8 bytes,
+ * faces, rgba, depth and mesh_id 4 bytes; with W % 4 == 0, workspace, rgba, depth and mesh_id 16-byte and frames, out 4-byte
+ * aligned, resolve moves four pixels per lane. */
+size_t hm_mesh_render_workspace_bytes(int N, int H, int W, int n_verts, int n_meshes, int n_faces);
+int hm_mesh_render(int N, int H, int W, const double* K_host, const double* verts, int n_verts, const int32_t* faces,
+                   int n_faces, const hm_mesh* meshes_host, int n_meshes, const double* base_rgb, const uint8_t* bg_rgba,
+                   double znear, const uint8_t* frames, uint8_t* out, uint8_t* rgba, float* depth, int32_t* mesh_id,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- SAR hand-mesh head of the RootNet checkpoint (rootnet/Model_RGB.py:76-177 SoftHeatmap / GraphConv / SAIGB / GBBMR,
  * :198-222 SARhead, :428-480 post_processing, :500-570 EstimateRGB.run).  f16 operands, fp32 accumulation; activations are
  * node-major across the batch, [778][B][C].  No split-K and no batch-dependent reduction order: a hand's numbers are the

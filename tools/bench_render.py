@@ -1,13 +1,18 @@
-"""Mesh overlay measurements.
+"""Mesh overlay and z-buffered renderer measurements (DESIGN.md sections 8 and 8.1).
 
-  python tools/bench_render.py device [--iters 20] [--topology surface|synthetic]
-                                                     64 synthetic 1080p frames x 4 hands through hm_mesh_overlay; prints the
-                                                     event time per call.  Run it a second time under
+  python tools/bench_render.py device [--iters 20] [--topology surface|synthetic] [--renderer overlay|zbuffer|both]
+                                                     64 synthetic 1080p frames x 4 hands through hm_mesh_overlay (flat; with
+                                                     --renderer both: shaded) and / or hm_mesh_render (frames + out, and in a
+                                                     second figure rgba + depth + mesh_id); prints the event time per call.
+                                                     Run it a second time under
                                                      `rocprofv3 --kernel-trace --stats -- python tools/bench_render.py device`
-                                                     for the per-kernel device time (overlay_setup / raster / compose).
-  python tools/bench_render.py folder [--frames 64]  render_folder on a folder of synthetic 1080p .jpg frames with 2 hands each
-                                                     (records made from seeded MANO parameters, synthetic:0 weights): frames/s
-                                                     of the whole call (decode, MANO, overlay, copy back, JPEG encode).
+                                                     for the per-kernel device time (overlay_setup / raster / compose,
+                                                     zrender_normals / setup / raster / resolve).
+  python tools/bench_render.py folder [--frames 64] [--style flat|shaded|smooth] [--hand-maps]
+                                                     render_folder (or hand_maps_folder) on a folder of synthetic 1080p .jpg
+                                                     frames with 2 hands each (records made from seeded MANO parameters,
+                                                     synthetic:0 weights): frames/s of the whole call (decode, MANO, draw, copy
+                                                     back, encode).
 Each mode prints one JSON line."""
 import argparse
 import json
@@ -58,26 +63,37 @@ def _meshes(N, per_frame, seed=0, topology="surface"):
     return out
 
 
-def device(iters, topology):
+def _event_ms(fn, iters):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return round(e0.elapsed_time(e1) / iters, 4)
+
+
+def device(iters, topology, renderer="overlay"):
     N = 64
     frames = torch.stack([synth.frame_u8(H, W, seed=n) for n in range(N)]).cuda()
     K = np.array([[1000.0, 0, W / 2], [0, 1000.0, H / 2], [0, 0, 1]])
     meshes = _meshes(N, 4, topology=topology)
     out = torch.empty_like(frames)
-    for _ in range(3):
-        render.overlay_frames(frames, K, meshes, out=out)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        render.overlay_frames(frames, K, meshes, out=out)
-    e1.record()
-    torch.cuda.synchronize()
-    ms = e0.elapsed_time(e1) / iters
     frame_bytes = 2 * N * H * W * 3
-    print(json.dumps({"mode": "device", "topology": topology, "frames": N, "hands": len(meshes), "faces_per_hand": int(meshes[0]["faces"].shape[0]),
-                      "ms_per_call_events_incl_host_prep": round(ms, 4), "frame_bytes_read_written": frame_bytes,
-                      "hbm_floor_ms_at_8TBps": round(frame_bytes / 8e12 * 1e3, 4)}))
+    res = {"mode": "device", "renderer": renderer, "topology": topology, "frames": N, "hands": len(meshes),
+           "faces_per_hand": int(meshes[0]["faces"].shape[0]), "frame_bytes_read_written": frame_bytes,
+           "hbm_floor_ms_at_8TBps": round(frame_bytes / 8e12 * 1e3, 4)}
+    if renderer == "overlay":
+        res["ms_per_call_events_incl_host_prep"] = _event_ms(lambda: render.overlay_frames(frames, K, meshes, out=out), iters)
+    if renderer == "both":
+        res["overlay_shaded_ms_per_call"] = _event_ms(lambda: render.overlay_frames(frames, K, meshes, style="shaded", out=out), iters)
+    if renderer in ("zbuffer", "both"):
+        res["zbuffer_frames_out_ms_per_call"] = _event_ms(lambda: render.render_views(H, W, K, meshes, frames=frames, outputs=()), iters)
+        res["zbuffer_rgba_depth_id_ms_per_call"] = _event_ms(lambda: render.render_views(H, W, K, meshes, views=N), iters)
+    print(json.dumps(res))
 
 
 class _Cfg:
@@ -87,7 +103,7 @@ class _Cfg:
     onnx_path = None
 
 
-def folder(n_frames):
+def folder(n_frames, style="flat", hand_maps=False):
     from PIL import Image
     from hamer_yolo_amd.infer import hamer_inference
     hi = hamer_inference(_Cfg)
@@ -103,13 +119,17 @@ def folder(n_frames):
                 rec[t] = {"betas": rng.normal(0, 0.5, 10).astype(np.float32), "theta": np.concatenate([pg, ph]), "pose_hand": ph,
                           "pose_global": pg, "cam_t": np.array([x, 0.02, 0.6], np.float32), "is_right": t == "right"}
             np.save(os.path.join(npy, f"{i:06d}.npy"), rec)
-        render.render_folder(img, npy, out, hi, frames_per_pass=8)              # warm-up: code objects, workspace
+        if hand_maps:
+            run = lambda **kw: render.hand_maps_folder(img, npy, out, hi, **kw)
+        else:
+            run = lambda **kw: render.render_folder(img, npy, out, hi, style=style, **kw)
+        run(frames_per_pass=8)                                                  # warm-up: code objects, workspace
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        n = render.render_folder(img, npy, out, hi)
+        n = run()
         dt = time.perf_counter() - t0
-    print(json.dumps({"mode": "folder", "frames": n, "seconds": round(dt, 3), "frames_per_s": round(n / dt, 2),
-                      "threads": render._encode_threads()}))
+    print(json.dumps({"mode": "folder", "what": "hand_maps" if hand_maps else style, "frames": n, "seconds": round(dt, 3),
+                      "frames_per_s": round(n / dt, 2), "threads": render._encode_threads()}))
 
 
 if __name__ == "__main__":
@@ -118,5 +138,8 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--topology", choices=["surface", "synthetic"], default="surface")
+    ap.add_argument("--renderer", choices=["overlay", "zbuffer", "both"], default="overlay")
+    ap.add_argument("--style", choices=["flat", "shaded", "smooth"], default="flat")
+    ap.add_argument("--hand-maps", action="store_true")
     a = ap.parse_args()
-    device(a.iters, a.topology) if a.mode == "device" else folder(a.frames)
+    device(a.iters, a.topology, a.renderer) if a.mode == "device" else folder(a.frames, a.style, a.hand_maps)
