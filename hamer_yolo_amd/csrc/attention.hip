@@ -340,6 +340,15 @@ __global__ __launch_bounds__(64 * NWAVE, 3) void vit_attention_kernel(const type
   }
 }
 
+// The grid for `items` (crop, head) pairs planned for `n_cu` compute units (persistent: one workgroup per CU, every workgroup
+// the same number of items when items % CUs == 0).  HM_OPT_ATT_GRID (tests) replaces the device's count: few units make a
+// workgroup walk several items at any batch size.  Exported as hm_attention_grid for the tests.
+int att_grid_for(int items, int n_cu) {
+  if (const int v = hm_option(HM_OPT_ATT_GRID)) n_cu = v;
+  const int per = (items + n_cu - 1) / n_cu;
+  return (items + per - 1) / per;
+}
+
 template <class TT, bool MX8 = false, bool TOME = false>
 int launch_att(const void* qkv, void* out, int B, int heads, float scale, hipStream_t s, void* out_scales = nullptr,
                const float* size = nullptr, int Tn = T) {
@@ -350,14 +359,18 @@ int launch_att(const void* qkv, void* out, int B, int heads, float scale, hipStr
   const int n_cu = hm_device_cu_count();
   if (n_cu <= 0) return hm_set_error(HM_ERR_HIP, "hm_vit_attention: cannot query the device");
   const int items = B * heads;
-  // persistent: one workgroup per CU, every workgroup the same number of items when items % CUs == 0
-  const int per = (items + n_cu - 1) / n_cu, grid = (items + per - 1) / per;
+  const int grid = att_grid_for(items, n_cu);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NWAVE), LDS, s, (const typename TT::elem*)qkv,
                      (typename TT::elem*)out, heads, items, scale * 1.44269504088896340736f, (unsigned char*)out_scales, size, Tn);
   return hm_check_launch("hm_vit_attention");
 }
 
 }  // namespace
+
+extern "C" int hm_attention_grid(int items, int cus) {
+  if (items <= 0) return 0;
+  return att_grid_for(items, cus > 0 ? cus : 256);
+}
 
 // hm_tome_attention's MFMA path (tome.hip): tokens <= 192 per crop, head_dim 80, log(size) on the key axis
 int hm_attention_tome_launch(const void* qkv, const float* size, void* out, int B, int tokens, int heads, float scale, int dtype,

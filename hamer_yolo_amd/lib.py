@@ -22,7 +22,7 @@ HM_VERSION = 402      # include/hamer_hip.h: load() refuses a library built from
 OPTION_NAMES = ("HM_OPT_PX_GRID", "HM_OPT_FP8P_GRID", "HM_OPT_FP8_ONE_TILE", "HM_OPT_FP8P_RESID", "HM_OPT_TOME_NO_SPLITK",
                 "HM_OPT_TOME_SCALAR_ATTENTION", "HM_OPT_RESID_IN_EPILOGUE", "HM_OPT_CONV_TILE", "HM_OPT_CONV_SPLITK",
                 "HM_OPT_PX_LDS_EPILOGUE", "HM_OPT_CONV_DIRECT", "HM_OPT_GEMM_TILE_RULE", "HM_OPT_CONV_KGROUPS",
-                "HM_OPT_CONV_GENERAL_LOADER", "HM_OPT_CONV_STEM_PAIR")
+                "HM_OPT_CONV_GENERAL_LOADER", "HM_OPT_CONV_STEM_PAIR", "HM_OPT_ATT_GRID")
 globals().update({_n: _i for _i, _n in enumerate(OPTION_NAMES)})
 
 EXPORTS = [
@@ -38,6 +38,7 @@ EXPORTS = [
     "hm_gemm_f32", "hm_vit_attention_f32",
     "hm_dwconv7_ln", "hm_ln_patchify2", "hm_stem4_im2col", "hm_sar_saigb_ch",
     "hm_mesh_render_workspace_bytes", "hm_mesh_render",
+    "hm_attention_grid",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -211,6 +212,7 @@ def load() -> C.CDLL:
     lib.hm_get_option.argtypes = [i]
     lib.hm_option_count.argtypes = []
     lib.hm_gemm_px_grid.argtypes = [i, i]
+    lib.hm_attention_grid.argtypes = [i, i]
     lib.hm_mesh_overlay_workspace_bytes.argtypes = [i, i, i, i, i]
     lib.hm_mesh_overlay_workspace_bytes.restype = C.c_size_t
     lib.hm_mesh_overlay.argtypes = [vp, i, i, i, vp, vp, i, vp, i, C.POINTER(Mesh), i, i, d, vp, vp, C.c_size_t, vp]

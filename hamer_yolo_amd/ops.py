@@ -159,33 +159,48 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
     return out
 
 
-def vit_attention(qkv: torch.Tensor, B: int, tokens: int, heads: int, head_dim: int, scale: float) -> torch.Tensor:
-    _dev(qkv)
+def _out_rows(out: Optional[torch.Tensor], rows: int, cols: int, dtype, device) -> torch.Tensor:
+    """The caller's output buffer (its first `rows` rows are written; it may be longer) or a fresh one."""
+    if out is None:
+        return torch.empty(rows, cols, device=device, dtype=dtype)
+    assert out.dim() == 2 and out.shape[0] >= rows and out.shape[1] == cols and out.dtype == dtype and out.is_contiguous()
+    return out
+
+
+def vit_attention(qkv: torch.Tensor, B: int, tokens: int, heads: int, head_dim: int, scale: float,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out: optional (>= B*tokens, heads*head_dim) buffer of qkv's dtype to write into (returned as given)."""
+    _dev(qkv, out)
     assert qkv.shape == (B * tokens, 3 * heads * head_dim) and qkv.is_contiguous()
-    out = torch.empty(B * tokens, heads * head_dim, device=qkv.device, dtype=qkv.dtype)
+    out = _out_rows(out, B * tokens, heads * head_dim, qkv.dtype, qkv.device)
     L.check(L.load().hm_vit_attention(L.ptr(qkv), L.ptr(out), B, tokens, heads, head_dim, scale, _dt(qkv),
                                       L.current_stream()), "hm_vit_attention")
     return out
 
 
-def vit_attention_mx8(qkv: torch.Tensor, B: int, tokens: int, heads: int, head_dim: int, scale: float):
-    """Attention with MXFP8 output: (out8 (B*tokens, heads*96) uint8, scales (heads*3, B*tokens) uint8)."""
-    _dev(qkv)
+def vit_attention_mx8(qkv: torch.Tensor, B: int, tokens: int, heads: int, head_dim: int, scale: float,
+                      out8: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None):
+    """Attention with MXFP8 output: (out8 (B*tokens, heads*96) uint8, scales (heads*3, B*tokens) uint8).  out8 / scales:
+    optional buffers to write into (out8 may have more rows; the scale rows have pitch B*tokens, so `scales` is exact)."""
+    _dev(qkv, out8, scales)
     assert qkv.shape == (B * tokens, 3 * heads * head_dim) and qkv.is_contiguous() and qkv.dtype == torch.bfloat16
-    out8 = torch.empty(B * tokens, heads * 96, device=qkv.device, dtype=torch.uint8)
-    scales = torch.empty(heads * 3, B * tokens, device=qkv.device, dtype=torch.uint8)
+    out8 = _out_rows(out8, B * tokens, heads * 96, torch.uint8, qkv.device)
+    if scales is None:
+        scales = torch.empty(heads * 3, B * tokens, device=qkv.device, dtype=torch.uint8)
+    assert scales.shape == (heads * 3, B * tokens) and scales.dtype == torch.uint8 and scales.is_contiguous()
     L.check(L.load().hm_vit_attention_mx8(L.ptr(qkv), L.ptr(out8), L.ptr(scales), B, tokens, heads, head_dim, scale,
                                           L.current_stream()), "hm_vit_attention_mx8")
     return out8, scales
 
 
 def tome_attention(qkv: torch.Tensor, size: Optional[torch.Tensor], B: int, tokens: int, heads: int, head_dim: int,
-                   scale: float) -> torch.Tensor:
-    """ToMeAttention core: softmax(scale q k^T + log(size)) v for any tokens <= 192; size (B*tokens,) f32 or None."""
-    _dev(qkv, size)
+                   scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ToMeAttention core: softmax(scale q k^T + log(size)) v for any tokens <= 192; size (B*tokens,) f32 or None.
+    out: optional (>= B*tokens, heads*head_dim) buffer of qkv's dtype to write into (returned as given)."""
+    _dev(qkv, size, out)
     assert qkv.shape == (B * tokens, 3 * heads * head_dim) and qkv.is_contiguous()
     assert size is None or (size.shape == (B * tokens,) and size.dtype == torch.float32 and size.is_contiguous())
-    out = torch.empty(B * tokens, heads * head_dim, device=qkv.device, dtype=qkv.dtype)
+    out = _out_rows(out, B * tokens, heads * head_dim, qkv.dtype, qkv.device)
     L.check(L.load().hm_tome_attention(L.ptr(qkv), L.ptr(size), L.ptr(out), B, tokens, heads, head_dim, scale, _dt(qkv),
                                        L.current_stream()), "hm_tome_attention")
     return out
@@ -231,10 +246,12 @@ def linear_f32(x: torch.Tensor, w: torch.Tensor, bias=None, resid=None, act: int
 
 def cross_attention(q: torch.Tensor, kv: torch.Tensor, k_off: int, v_off: int, B: int, tokens: int, heads: int,
                     dim_head: int, scale: float) -> torch.Tensor:
+    """kv: 16-bit, or fp32 (the precise route: HM_DTYPE_F32)."""
     _dev(q, kv)
     out = torch.empty(B, heads * dim_head, device=q.device, dtype=torch.float32)
+    code = L.HM_DTYPE_F32 if kv.dtype == torch.float32 else _dt(kv)
     L.check(L.load().hm_cross_attention(L.ptr(q), L.ptr(kv), kv.stride(0), k_off, v_off, L.ptr(out), B, tokens, heads,
-                                        dim_head, scale, _dt(kv), L.current_stream()), "hm_cross_attention")
+                                        dim_head, scale, code, L.current_stream()), "hm_cross_attention")
     return out
 
 

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32) and the additive fp32 HaMeR entry points (hm_gemm_f32, hm_vit_attention_f32; hm_hamer_forward, hm_patch_im2col and hm_cross_attention take HM_DTYPE_F32) and the additive ConvNeXt SAR entry points (hm_dwconv7_ln, hm_ln_patchify2, hm_stem4_im2col, hm_sar_saigb_ch); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
+#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32) and the additive fp32 HaMeR entry points (hm_gemm_f32, hm_vit_attention_f32; hm_hamer_forward, hm_patch_im2col and hm_cross_attention take HM_DTYPE_F32) and the additive ConvNeXt SAR entry points (hm_dwconv7_ln, hm_ln_patchify2, hm_stem4_im2col, hm_sar_saigb_ch) and the additive attention test hook (hm_attention_grid, HM_OPT_ATT_GRID); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
 
 enum { HM_DTYPE_BF16 = 0, HM_DTYPE_F16 = 1,
        HM_DTYPE_F32 = 2 /* same value as HM_OUT_F32.  The fp32 YOLOv7 route (its section below) and the precise HaMeR route
@@ -105,7 +105,8 @@ enum {
   HM_OPT_CONV_KGROUPS = 12,         /* tuning: 1 = no K groups inside a convolution workgroup (small maps), 0 = automatic */
   HM_OPT_CONV_GENERAL_LOADER = 13,  /* tuning / tests: 1 = the implicit-GEMM convolution takes its general loader (per-lane tap arithmetic every K-step) even where the lean one applies (Cin % 64 == 0); 0 = automatic.  Same bytes either way */
   HM_OPT_CONV_STEM_PAIR = 14,       /* tuning / tests: 1 = hm_conv2d_stem_pair (and HM_OP_CONV_PAIR of hm_yolo_run) always runs its two convolutions as two launches; 0 = one launch where the fused kernel applies.  Same bytes either way */
-  HM_OPT_COUNT = 15
+  HM_OPT_ATT_GRID = 15,             /* tests: the number of compute units the persistent attention launches (hm_vit_attention, hm_vit_attention_mx8, the MFMA path of hm_tome_attention) plan for; 0 = the device's count.  Any value >= 1 (a grid that is no multiple of the 8 XCDs is wanted here): few units make every workgroup walk several (crop, head) items.  Same bytes at every value */
+  HM_OPT_COUNT = 16
 };
 int hm_set_option(int key, int value);
 int hm_get_option(int key);
@@ -114,6 +115,10 @@ int hm_option_count(void);
 /* Host-side query, no device work: the workgroup count the persistent 16-bit GEMM takes for `tiles` whole 256 x 256 tiles on a
  * chip of `cus` compute units (0: 256) under the current HM_OPT_PX_GRID -- tests check that the option is not sticky. */
 int hm_gemm_px_grid(int tiles, int cus);
+/* Host-side query, no device work: the workgroup count the persistent attention kernel takes for `items` (crop, head) pairs
+ * under the current HM_OPT_ATT_GRID; `cus` compute units (0: 256) apply when the option is 0.  Every workgroup then walks at most
+ * ceil(items / grid) items.  The launches call the same function, so a test that asserts its geometry cannot disagree with them. */
+int hm_attention_grid(int items, int cus);
 
 /* The fp8 flavour of hm_gemm for BASELINE configs[4] ("fp8 ViT-H weights on CDNA4 fp8 MFMA"): C = epilogue(X . W^T) on
  * v_mfma_scale_f32_16x16x128_f8f6f4 (2x the bf16 MFMA rate, half the operand bytes).
@@ -151,7 +156,9 @@ int hm_absmax16(const void* x, int ld, int M, int col0, int ncols, int dtype, fl
 
 /* Attention.forward core (vit.py:115-123): softmax(scale q k^T) v for `tokens`=192 keys.
  * qkv [B*tokens][3*heads*head_dim] 16-bit, column = which*H*d + head*d + i (reshape at
- * vit.py:112); out [B*tokens][heads*head_dim] 16-bit (head-major, vit.py:123). */
+ * vit.py:112); out [B*tokens][heads*head_dim] 16-bit (head-major, vit.py:123).
+ * One persistent kernel: hm_attention_grid(B*heads, CUs) workgroups walk the (crop, head) items; a (crop, head)'s bytes do not
+ * depend on the grid (HM_OPT_ATT_GRID, a test hook, makes a workgroup walk several items at any B). */
 int hm_vit_attention(const void* qkv, void* out, int B, int tokens, int heads, int head_dim, float scale,
                      int dtype, void* stream);
 

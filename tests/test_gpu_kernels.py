@@ -445,19 +445,35 @@ def test_linear_f32(M, N, K):
                                atol=3e-6 * math.sqrt(K), rtol=1e-5)
 
 
-@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16, torch.float32])
 def test_cross_attention(dt):
-    B, T, heads, dh, layers = 5, 192, 8, 64, 3
+    """One query per (hand, head) over T context tokens against a float64 softmax.  192 is the dense forward's context; token
+    merging feeds 146, 128, 15 and 1, and the other lengths put the `t < tokens` masks of the score pass (64 tokens per step)
+    and the tail of the 8-token output loop at every partial fill, up to the kernel's limit of 256.  fp32 kv is the precise
+    route (expf instead of __expf): at least as exact, same bound."""
+    B, heads, dh, layers = 5, 8, 64, 3
     inner = heads * dh
     q = _u("caq", (B, inner), 2.0, seed=1)
-    kv = _u("cakv", (B * T, layers * 2 * inner), 1.5, seed=2).to(dt)
     li = 1
-    out = ops.cross_attention(q.to(DEV), kv.to(DEV), li * 2 * inner, li * 2 * inner + inner, B, T, heads, dh, dh ** -0.5).cpu()
-    kvf = kv.float().reshape(B, T, layers, 2, heads, dh)
-    k, v = kvf[:, :, li, 0].permute(0, 2, 1, 3), kvf[:, :, li, 1].permute(0, 2, 1, 3)   # (B,h,T,dh)
-    a = ((q.reshape(B, heads, 1, dh) @ k.transpose(-1, -2)) * dh ** -0.5).softmax(-1)
-    ref = (a @ v).reshape(B, inner)
-    np.testing.assert_allclose(out.numpy(), ref.numpy(), atol=2e-5, rtol=1e-4)
+    for T in (192, 1, 7, 15, 64, 65, 128, 146, 193, 256):
+        kv = _u("cakv", (B * T, layers * 2 * inner), 1.5, seed=2).to(dt)
+        out = ops.cross_attention(q.to(DEV), kv.to(DEV), li * 2 * inner, li * 2 * inner + inner, B, T, heads, dh, dh ** -0.5).cpu()
+        kvf = kv.double().reshape(B, T, layers, 2, heads, dh)
+        k, v = kvf[:, :, li, 0].permute(0, 2, 1, 3), kvf[:, :, li, 1].permute(0, 2, 1, 3)   # (B,h,T,dh)
+        a = ((q.double().reshape(B, heads, 1, dh) @ k.transpose(-1, -2)) * dh ** -0.5).softmax(-1)
+        ref = (a @ v).reshape(B, inner)
+        assert torch.isfinite(out).all(), T
+        np.testing.assert_allclose(out.double().numpy(), ref.numpy(), atol=2e-5, rtol=1e-4, err_msg=f"tokens {T}")
+
+
+def test_cross_attention_rejects_token_counts_outside_1_to_256():
+    B, heads, dh = 2, 8, 64
+    q = _u("caq", (B, heads * dh), 2.0, seed=1).to(DEV)
+    kv = _u("cakv", (B * 256, 2 * heads * dh), 1.5, seed=2).half().to(DEV)
+    ops.cross_attention(q, kv, 0, heads * dh, B, 256, heads, dh, dh ** -0.5)          # the largest legal context
+    for tokens in (0, 257):
+        with pytest.raises(L.HipLibraryError):
+            ops.cross_attention(q, kv, 0, heads * dh, B, tokens, heads, dh, dh ** -0.5)
 
 
 # ------------------------------------------------------------------------------------ MANO tail

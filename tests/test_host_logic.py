@@ -58,6 +58,11 @@ def test_options_are_explicit_setters_not_environment_reads(monkeypatch):
     with L.option(L.HM_OPT_FP8P_GRID, 40):
         assert lib.hm_get_option(L.HM_OPT_FP8P_GRID) == 40
     assert lib.hm_get_option(L.HM_OPT_FP8P_GRID) == 0
+    for v in (1, 3, 12):                                  # the attention grid is wanted at values that are no multiple of 8
+        with L.option(L.HM_OPT_ATT_GRID, v):
+            assert lib.hm_get_option(L.HM_OPT_ATT_GRID) == v
+        assert lib.hm_get_option(L.HM_OPT_ATT_GRID) == 0
+    assert lib.hm_set_option(L.HM_OPT_ATT_GRID, -1) != 0 and lib.hm_get_option(L.HM_OPT_ATT_GRID) == 0
     src = "".join(open(os.path.join(ROOT, "hamer_yolo_amd", "csrc", f)).read() for f in os.listdir(os.path.join(ROOT, "hamer_yolo_amd", "csrc")))
     assert sorted(set(re.findall(r'getenv\("(\w+)"\)', src))) == ["HM_GEMM_VARIANT", "HM_PX_GRID"]
 
@@ -87,6 +92,24 @@ def test_persistent_grid_option_is_not_sticky():
     with L.option(L.HM_OPT_PX_GRID, 16):
         assert lib.hm_gemm_px_grid(720, 256) == 16
     assert lib.hm_get_option(L.HM_OPT_PX_GRID) == 0 and lib.hm_gemm_px_grid(720, 256) == 248
+
+
+def test_attention_grid_is_host_arithmetic_and_not_sticky():
+    """hm_attention_grid reports the workgroup count the persistent attention launches take (they call the same function):
+    per = ceil(items / CUs) items per workgroup, grid = ceil(items / per).  HM_OPT_ATT_GRID replaces the CU count while it is
+    set and leaves nothing behind."""
+    lib = L.load()
+    assert lib.hm_attention_grid(1024, 256) == 256        # 64 hands x 16 heads: 4 items each
+    assert lib.hm_attention_grid(640, 256) == 214         # 40 hands: per 3, a ragged last round (640 = 2 * 214 + 212)
+    assert lib.hm_attention_grid(48, 256) == 48           # fewer items than units: one each
+    assert lib.hm_attention_grid(48, 0) == 48 and lib.hm_attention_grid(1024, 0) == 256      # cus == 0 means 256
+    assert lib.hm_attention_grid(640, 304) == 214 and lib.hm_attention_grid(640, 64) == 64   # `cus` applies at option 0
+    with L.option(L.HM_OPT_ATT_GRID, 3):
+        assert lib.hm_attention_grid(20, 256) == 3        # per 7: 7 + 7 + 6
+    with L.option(L.HM_OPT_ATT_GRID, 12):
+        assert lib.hm_attention_grid(20, 256) == 10       # per 2: a grid above 8 that is no multiple of 8
+    assert lib.hm_get_option(L.HM_OPT_ATT_GRID) == 0 and lib.hm_attention_grid(20, 256) == 20
+    assert lib.hm_attention_grid(640, 256) == 214
 
 
 def test_library_is_loaded_behind_torchs_hip_runtime():
