@@ -14,6 +14,7 @@ class Config:
     onnx_path = os.path.join(root_dir, "hamer/_DATA/hamer_ckpts/onnx/hamer_inferpy.onnx")
     use_onnx = False      # the ONNX path is out of scope (BASELINE.json north_star): True raises
     precise = False       # True: the fp32 HaMeR route (the reference's fp32 arithmetic; --precise-hamer)
+    antialias = False     # True: the batched crop takes prepare_item's anti-alias prefilter (--antialias-crop)
 
 
 hamer_opt = Config()

@@ -72,10 +72,13 @@ def matrix_to_axis_angle(rot_mats) -> np.ndarray:
 
 
 class hamer_inference():
-    def __init__(self, cfg=hamer_opt, precise=None):
+    def __init__(self, cfg=hamer_opt, precise=None, antialias=None):
         """infer.py:118-146.  ``cfg.{ckpt_path, model_cfg, use_onnx, onnx_path}``.  precise: None reads
-        ``getattr(cfg, "precise", False)``; True loads HaMeR on the fp32 route (load_hamer(precise=True))."""
+        ``getattr(cfg, "precise", False)``; True loads HaMeR on the fp32 route (load_hamer(precise=True)).
+        antialias: None reads ``getattr(cfg, "antialias", False)``; True gives the batched crop (prepare_batch_bbox and all
+        that is built on it) the anti-alias prefilter of ``prepare_item`` -- another preprocessing, independent of ``precise``."""
         self.precise = bool(getattr(cfg, "precise", False) if precise is None else precise)
+        self.antialias = bool(getattr(cfg, "antialias", False) if antialias is None else antialias)
         self.use_onnx = bool(getattr(cfg, "use_onnx", False))
         if self.use_onnx:
             raise NotImplementedError("the ONNX Runtime path of the reference is out of scope (no ONNX export path)")
@@ -141,11 +144,13 @@ class hamer_inference():
             transs.append(gen_trans_from_patch_cv(center_x, center_y, final_bbox_size, final_bbox_size, P, P, 1.0, 0))
         return boxes, centers, sizes, flips, transs
 
-    def prepare_batch_frames(self, frames: List[torch.Tensor], dets_lists: List[List]) -> Dict[str, torch.Tensor]:
+    def prepare_batch_frames(self, frames: List[torch.Tensor], dets_lists: List[List], antialias=None) -> Dict[str, torch.Tensor]:
         """prepare_batch_bbox for the hands of SEVERAL frames at once: ``frames`` are (H,W,3) uint8 BGR device tensors,
         ``dets_lists[i]`` the boxes of frame i.  One hm_crop_batch launch per frame, all writing into one (sum B,3,P,P)
-        batch tensor, so one HaMeR forward serves every hand of every frame.  ``frame_index`` says which frame a hand is from."""
+        batch tensor, so one HaMeR forward serves every hand of every frame.  ``frame_index`` says which frame a hand is from.
+        ``antialias`` (None: ``self.antialias``): the launches are hm_crop_batch_aa, the crop rule of ``prepare_item``."""
         P = int(self.cfg.MODEL.IMAGE_SIZE)
+        aa = self.antialias if antialias is None else bool(antialias)
         boxes, centers, sizes, flips, transs, img_sizes, fidx = [], [], [], [], [], [], []
         counts = []
         for i, (fr, bboxs) in enumerate(zip(frames, dets_lists)):
@@ -160,14 +165,16 @@ class hamer_inference():
         # one upload for all hands, from page-locked memory and asynchronous: a pageable host -> device copy makes the host wait
         # for everything already queued on its stream -- with several HaMeR batches queued per stream that was a whole forward
         # (tools/probes/e2e_trace.py: the third batch of a pass could not be enqueued before the first had finished)
-        rec = self._up(ops.crop_boxes(boxes, P))
+        rec = self._up(ops.crop_boxes_aa(boxes, P) if aa else ops.crop_boxes(boxes, P))
         rsz = rec.numel() // n
         img = torch.empty(n, 3, P, P, device=self.device, dtype=torch.float32)
         off = 0
         for fr, k in zip(frames, counts):
-            if k:
+            if k and aa:
+                ops.crop_batch_aa(fr, rec, self.mean, self.std, P, out=img[off:off + k], first=off, count=k)
+            elif k:
                 ops.crop_batch(fr, rec[off * rsz:(off + k) * rsz], self.mean, self.std, P, out=img[off:off + k])
-                off += k
+            off += k
         trans = torch.tensor(np.stack(transs), dtype=torch.float32)
         return {
             'img': img,                                                               # (B,3,P,P) on device
@@ -193,6 +200,21 @@ class hamer_inference():
         batch = self.prepare_batch_frames([frame], [bboxs])
         del batch['frame_index']
         return batch
+
+    def prepare_item(self, img_0: np.ndarray, bbox) -> Dict:
+        """infer.py:263-352: ONE hand, cropped with the anti-alias prefilter whatever ``self.antialias`` says, and the
+        reference's item: ``img`` (1,3,P,P) -- here on the device --, ``box_center`` (1,2), ``box_size`` (1,1), ``img_size``
+        (1,2), ``inv_trans`` (1,2,3), ``do_flip`` (1,), and ``trans``, the 2x3 affine as a numpy array."""
+        if isinstance(bbox, list) and len(bbox) == 2:
+            coords = bbox[1]
+            if not (isinstance(coords, list) and len(coords) == 4):
+                raise ValueError(f"Invalid coordinates format: Expected [x1,y1,x2,y2], got {coords}")
+        else:
+            raise ValueError(f"Invalid bbox format: Expected [class, coords], got {bbox}")
+        frame = torch.from_numpy(np.ascontiguousarray(img_0)).to(self.device)
+        b = self.prepare_batch_frames([frame], [[bbox]], antialias=True)
+        return {'img': b['img'], 'box_center': b['box_center'], 'box_size': b['box_size'].view(1, 1), 'img_size': b['img_size'],
+                'inv_trans': b['inv_trans'], 'do_flip': b['do_flip'], 'trans': self._box_scalars([bbox])[4][0]}       # (trans: float64, as cv2 returns it)
 
     # ------------------------------------------------------------------ forward + camera maths
     @torch.no_grad()
@@ -1080,8 +1102,21 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument('--precise-detector', action='store_true',
                     help="run YOLOv7 in fp32 (the reference's CPU branch) instead of fp16: its boxes, at about twice the detector time")
     _precise_hamer_args(ap)
+    _antialias_args(ap)
     _render_args(ap)
     return ap
+
+
+def _antialias_args(ap: argparse.ArgumentParser) -> None:
+    ap.add_argument('--antialias-crop', action='store_true',
+                    help="blur the frame under a hand crop that is shrunk by more than 2.2x before it is sampled, as the reference's "
+                         "prepare_item does (upstream HaMeR's preprocessing); off: the reference's batched crop, no prefilter")
+
+
+def apply_antialias_args(args) -> None:
+    """``--antialias-crop`` -> ``hamer_opt.antialias``.  No precise switch implies it: it is another preprocessing, not a precision."""
+    if getattr(args, "antialias_crop", False):
+        hamer_opt.antialias = True
 
 
 def _precise_hamer_args(ap: argparse.ArgumentParser) -> None:
@@ -1126,6 +1161,7 @@ def main(argv=None):
         from .config.yolo_config import yolo_opt
         yolo_opt.weights = args.yolo_weights
     apply_precise_args(args)
+    apply_antialias_args(args)
     # under `python -m torch.distributed.run --nproc-per-node N -m hamer_yolo_amd.infer ...` every rank takes its share of
     # the folder on its own GPU (RANK / LOCAL_RANK / WORLD_SIZE from the environment); a plain launch is one process
     from . import shard

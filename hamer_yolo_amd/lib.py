@@ -39,6 +39,7 @@ EXPORTS = [
     "hm_dwconv7_ln", "hm_ln_patchify2", "hm_stem4_im2col", "hm_sar_saigb_ch",
     "hm_mesh_render_workspace_bytes", "hm_mesh_render",
     "hm_attention_grid",
+    "hm_crop_aa_box_from_bbox", "hm_crop_batch_aa",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -72,6 +73,15 @@ class ManoModel(C.Structure):
 class CropBox(C.Structure):
     _fields_ = [("m0", C.c_double), ("m4", C.c_double), ("x0", C.c_int32), ("y0", C.c_int32),
                 ("flip", C.c_int32), ("reserved", C.c_int32)]
+
+
+HM_CROP_AA_MAX_RADIUS = 48
+HM_CROP_AA_TAPS = HM_CROP_AA_MAX_RADIUS + 1
+
+
+class CropAaBox(C.Structure):
+    """hm_crop_aa_box: the CropBox fields, then the blur of the anti-aliased crop (sigma 0: the 8-bit rule)."""
+    _fields_ = CropBox._fields_ + [("sigma", C.c_float), ("radius", C.c_int32), ("pad", C.c_int32 * 2)]
 
 
 class VitBlock(C.Structure):
@@ -174,6 +184,8 @@ def load() -> C.CDLL:
     lib.hm_mano_forward.argtypes = [C.POINTER(ManoModel), vp, vp, vp, vp, vp, vp, vp, vp, i, f, f, vp]
     lib.hm_crop_box_from_bbox.argtypes = [d, d, d, i, i, C.POINTER(CropBox)]
     lib.hm_crop_batch.argtypes = [vp, i, i, vp, vp, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]
+    lib.hm_crop_aa_box_from_bbox.argtypes = [d, d, d, i, i, C.POINTER(CropAaBox), C.POINTER(C.c_float)]
+    lib.hm_crop_batch_aa.argtypes = [vp, i, i, vp, vp, vp, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]
     lib.hm_hamer_workspace_bytes.argtypes = [C.POINTER(HamerWeights), i]
     lib.hm_hamer_workspace_bytes.restype = C.c_size_t
     lib.hm_hamer_forward.argtypes = [C.POINTER(HamerWeights), vp, i, C.POINTER(HamerOutputs), vp, C.c_size_t, vp]

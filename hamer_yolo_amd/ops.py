@@ -301,3 +301,39 @@ def crop_batch(frame: torch.Tensor, boxes_rec: torch.Tensor, mean, std, P: int =
     L.check(L.load().hm_crop_batch(L.ptr(frame), H, W, L.ptr(boxes_rec), L.ptr(out), B, P, m3, s3, L.current_stream()),
             "hm_crop_batch")
     return out
+
+
+def crop_boxes_aa(boxes, P: int = 256) -> torch.Tensor:
+    """boxes: iterable of (cx, cy, size, flip) -> ONE uint8 host tensor for the anti-aliased crop: the n hm_crop_aa_box records,
+    then the n x 49 fp32 taps (one upload carries both).  Raises for a size whose blur exceeds sigma 12 (radius 48)."""
+    lib = L.load()
+    n = len(boxes)
+    arr = (L.CropAaBox * n)()
+    taps = (C.c_float * (n * L.HM_CROP_AA_TAPS))()
+    for i, (cx, cy, size, flip) in enumerate(boxes):
+        t = C.cast(C.byref(taps, i * L.HM_CROP_AA_TAPS * 4), C.POINTER(C.c_float))
+        L.check(lib.hm_crop_aa_box_from_bbox(float(cx), float(cy), float(size), int(bool(flip)), P, C.byref(arr[i]), t),
+                "hm_crop_aa_box_from_bbox")
+    return torch.frombuffer(bytearray(bytes(arr) + bytes(taps)), dtype=torch.uint8).clone()
+
+
+def crop_batch_aa(frame: torch.Tensor, rec: torch.Tensor, mean, std, P: int = 256, out: Optional[torch.Tensor] = None,
+                  first: int = 0, count: Optional[int] = None) -> torch.Tensor:
+    """hm_crop_batch_aa.  frame (H,W,3) uint8 BGR on device; rec: crop_boxes_aa's tensor on the device, n hands.  The launch
+    serves hands [first, first + count) of it (default: all) -- the hands of one frame among several frames' records.
+    ``out``: a contiguous (count,3,P,P) fp32 slice to fill."""
+    _dev(frame, rec, out)
+    H, W, _ = frame.shape
+    rsz, tsz = C.sizeof(L.CropAaBox), 4 * L.HM_CROP_AA_TAPS
+    n = rec.numel() // (rsz + tsz)
+    B = n - first if count is None else count
+    assert rec.dtype == torch.uint8 and rec.is_contiguous() and rec.numel() == n * (rsz + tsz) and 0 <= first and B > 0 and first + B <= n
+    if out is None:
+        out = torch.empty(B, 3, P, P, device=frame.device, dtype=torch.float32)
+    assert out.shape == (B, 3, P, P) and out.dtype == torch.float32 and out.is_contiguous() and frame.is_contiguous()
+    m3 = (C.c_float * 3)(*[float(v) for v in mean])
+    s3 = (C.c_float * 3)(*[float(v) for v in std])
+    base = rec.data_ptr()
+    L.check(L.load().hm_crop_batch_aa(L.ptr(frame), H, W, base + first * rsz, base + n * rsz + first * tsz, L.ptr(out), B, P,
+                                      m3, s3, L.current_stream()), "hm_crop_batch_aa")
+    return out

@@ -244,6 +244,37 @@ int hm_crop_box_from_bbox(double cx, double cy, double size, int flip, int P, hm
 int hm_crop_batch(const uint8_t* frame, int H, int W, const hm_crop_box* boxes, float* out, int B, int P,
                   const float* mean3_host, const float* std3_host, void* stream);
 
+/* The same crop with the anti-alias prefilter of prepare_item (infer.py:263-352): with df = (size / P) / 2 > 1.1 the frame
+ * is blurred by skimage.filters.gaussian(sigma = (df - 1) / 2, preserve_range) before it is sampled.  Per axis the blur is
+ * radius = int(4 sigma + 0.5) normalised taps exp(-k^2 / (2 sigma^2)) over replicated frame edges; the float image is then
+ * sampled at the SAME 1/32-px coordinates as the 8-bit crop with the weights (32-fx)(32-fy)/1024 ..., a tap outside the
+ * frame counting 0, and nothing is rounded to 8 bits.  df <= 1.1: the 8-bit rule of hm_crop_batch, same bytes. */
+#define HM_CROP_AA_MAX_SIGMA 12.0       /* a box inside a 3840 x 2160 frame at P = 256: size 12800 */
+#define HM_CROP_AA_MAX_RADIUS 48        /* int(4 * 12 + 0.5) */
+#define HM_CROP_AA_TAPS (HM_CROP_AA_MAX_RADIUS + 1)
+typedef struct hm_crop_aa_box {
+  double m0, m4;    /* the hm_crop_box fields, same arithmetic                       */
+  int32_t x0, y0;
+  int32_t flip;
+  int32_t reserved;
+  float sigma;      /* 0: df <= 1.1, the 8-bit rule (radius is 0 then)               */
+  int32_t radius;   /* 0 .. HM_CROP_AA_MAX_RADIUS; 0 with sigma > 0: float rule, no blur */
+  int32_t pad[2];
+} hm_crop_aa_box;
+
+/* HOST helper (no GPU work): hm_crop_box_from_bbox plus sigma, radius and the one-sided taps g[0 .. radius] (computed in
+ * double, stored as float; taps_out[radius + 1 .. 48] = 0; all 0 but g[0] = 1 on the 8-bit rule).  A size whose sigma
+ * exceeds HM_CROP_AA_MAX_SIGMA (so every radius above HM_CROP_AA_MAX_RADIUS) is HM_ERR_ARG, the message naming the size --
+ * it is not clamped. */
+int hm_crop_aa_box_from_bbox(double cx, double cy, double size, int flip, int P, hm_crop_aa_box* out, float* taps_out);
+
+/* hm_crop_batch over hm_crop_aa_box records: boxes [B] and taps [B][HM_CROP_AA_TAPS] on the device, as the helper wrote
+ * them.  One launch for all hands of the frame; no blurred frame and no per-hand copy exists in memory: every workgroup
+ * filters the source rows and columns of its own output row.  fp32 arithmetic; a hand's bytes do not depend on B or on its
+ * position.  A record whose radius is outside 0 .. HM_CROP_AA_MAX_RADIUS (not one the helper wrote) gets NaN pixels. */
+int hm_crop_batch_aa(const uint8_t* frame, int H, int W, const hm_crop_aa_box* boxes, const float* taps, float* out, int B,
+                     int P, const float* mean3_host, const float* std3_host, void* stream);
+
 /* Whole HAMER.forward_step (hamer.py:99-156) as one enqueue: see hm_hamer_forward below. */
 typedef struct hm_vit_block {
   const float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
