@@ -1051,6 +1051,23 @@ def mano_hand_vertices(hamer_instance, hands: List[Dict]) -> torch.Tensor:
     return ops.mano_forward(mpd, torch.cat(sixes), torch.cat(betas), cam)["verts"]
 
 
+def mano_hand_joints_vertices(hamer_instance, hands: List[Dict]):
+    """``mano_hand_vertices`` that also returns the 21 joints: (joints (B, 21, 3), vertices (B, V, 3)), fp32 on the device,
+    from ONE MANO forward for all hands (the kernel computes both; a hand's values do not depend on the batch)."""
+    device = hamer_instance.device
+    mpd = {k: v.to(device) for k, v in hamer_instance.mano.params.items() if v.dtype == torch.float32}
+    sixes, betas = [], []
+    for hd in hands:
+        betas.append(torch.tensor(np.atleast_2d(hd['betas']), dtype=torch.float32, device=device))
+        go = axis_angle_to_rotation_matrix_torch(torch.tensor(np.atleast_2d(hd['pose_global']), dtype=torch.float32, device=device))
+        hp = axis_angle_to_rotation_matrix_torch(torch.tensor(hd['pose_hand'].reshape(-1, 3), dtype=torch.float32, device=device))
+        R = torch.cat([go, hp], 0)
+        sixes.append(torch.cat([R[:, :, 0], R[:, :, 1]], dim=1).reshape(1, 96))
+    cam = torch.tensor([[1.0, 0.0, 0.0]], device=device).expand(len(hands), 3).contiguous()
+    o = ops.mano_forward(mpd, torch.cat(sixes), torch.cat(betas), cam)
+    return o["joints"], o["verts"]
+
+
 def reconstruct_and_save_obj_with_wrapper(npy_folder, output_obj_folder, hamer_instance):
     """infer.py:1321-1436: .npy (axis-angle) -> rotation matrices -> MANO -> 778-vertex mesh; left hands are
     mirrored (x := -x, face winding flipped); += cam_t; one OBJ per image."""

@@ -40,6 +40,7 @@ EXPORTS = [
     "hm_mesh_render_workspace_bytes", "hm_mesh_render",
     "hm_attention_grid",
     "hm_crop_aa_box_from_bbox", "hm_crop_batch_aa",
+    "hm_pose_eval",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -82,6 +83,12 @@ HM_CROP_AA_TAPS = HM_CROP_AA_MAX_RADIUS + 1
 class CropAaBox(C.Structure):
     """hm_crop_aa_box: the CropBox fields, then the blur of the anti-aliased crop (sigma 0: the 8-bit rule)."""
     _fields_ = CropBox._fields_ + [("sigma", C.c_float), ("radius", C.c_int32), ("pad", C.c_int32 * 2)]
+
+
+class PoseEvalArgs(C.Structure):
+    """hm_pose_eval_args: sel is a bit mask over the P points (all zero: every point); NULL outputs are not computed."""
+    _fields_ = [("pred", vp), ("gt", vp), ("B", C.c_int), ("P", C.c_int), ("gt_stride", C.c_int), ("root", C.c_int),
+                ("sel", C.c_uint64 * 16), ("err", vp), ("pa_err", vp), ("aligned", vp), ("transform", vp)]
 
 
 class VitBlock(C.Structure):
@@ -249,6 +256,7 @@ def load() -> C.CDLL:
     lib.hm_ln_patchify2.argtypes = [vp, vp, vp, vp, i, i, i, i, f, i, vp]
     lib.hm_stem4_im2col.argtypes = [vp, vp, i, i, i, i, vp]
     lib.hm_sar_saigb_ch.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
+    lib.hm_pose_eval.argtypes = [C.POINTER(PoseEvalArgs), vp]
     lib.hm_prof_begin.argtypes = [i]
     lib.hm_prof_collect.argtypes = [C.POINTER(ProfRecord), i]
     lib.hm_prof_end.argtypes = []

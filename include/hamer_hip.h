@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32) and the additive fp32 HaMeR entry points (hm_gemm_f32, hm_vit_attention_f32; hm_hamer_forward, hm_patch_im2col and hm_cross_attention take HM_DTYPE_F32) and the additive ConvNeXt SAR entry points (hm_dwconv7_ln, hm_ln_patchify2, hm_stem4_im2col, hm_sar_saigb_ch) and the additive attention test hook (hm_attention_grid, HM_OPT_ATT_GRID); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
+#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32) and the additive fp32 HaMeR entry points (hm_gemm_f32, hm_vit_attention_f32; hm_hamer_forward, hm_patch_im2col and hm_cross_attention take HM_DTYPE_F32) and the additive ConvNeXt SAR entry points (hm_dwconv7_ln, hm_ln_patchify2, hm_stem4_im2col, hm_sar_saigb_ch) and the additive attention test hook (hm_attention_grid, HM_OPT_ATT_GRID) and the additive hand-metric entry point (hm_pose_eval); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
 
 enum { HM_DTYPE_BF16 = 0, HM_DTYPE_F16 = 1,
        HM_DTYPE_F32 = 2 /* same value as HM_OUT_F32.  The fp32 YOLOv7 route (its section below) and the precise HaMeR route
@@ -681,6 +681,33 @@ int hm_ln_patchify2(const float* x, const float* gamma, const float* beta, void*
  * -> patches [B*(H/4)*(W/4)][64] 16-bit: 48 values in the weight's (c, ky, kx) order, then 16 zeros (hm_gemm: K % 64 == 0).
  * H % 4 == 0, W % 4 == 0. */
 int hm_stem4_im2col(const float* img, void* patches, int B, int H, int W, int dtype, void* stream);
+
+/* ---- Hand metrics (hamer/utils/pose_utils.py): MPJPE and Procrustes-aligned MPJPE of a batch in one launch.
+ * Restates compute_similarity_transform (pose_utils.py:9-58: centroids, var1, K = X1 X2^T, R = V Z U^T with
+ * Z = diag(1, 1, sign det(U V^T)), scale = trace(R K) / var1, t = mu2 - scale R mu1, S1_hat = scale R S1 + t),
+ * reconstruction_error (:60-71), the two means of eval_pose (:83, :86; metres here, eval_pose multiplies by 1000) and the root
+ * subtraction and keypoint selection of Evaluator.__call__ (:163-168).  fp32 in, every sum over points and the 3 x 3 solve in
+ * fp64, one rounding to fp32 at the store.  One wave per hand; a hand's bytes do not depend on B or on its place in the batch.
+ * var1 == 0 (one selected point, coincident predictions): pa_err, aligned and transform of that hand are NaN, err is not.
+ * Coincident gt points (K = 0, var1 > 0) are finite as in the reference: R = I, scale = 0, S1_hat = mu2.  A non-finite input
+ * makes every output of that hand that depends on it non-finite, and no other hand's. */
+typedef struct hm_pose_eval_args {
+  const float* pred;      /* [B][P][3] f32 */
+  const float* gt;        /* [B][P][gt_stride] f32, the first 3 of each point are read; gt_stride 3 or 4
+                             (batch['keypoints_3d'] is (B, 21, 4)) */
+  int B, P, gt_stride;    /* P in 1..1024 */
+  int root;               /* index into P or -1: pred[b][root] / gt[b][root] are subtracted from every point of hand b first
+                             (Evaluator's pelvis_ind, :163-165), before the selection */
+  uint64_t sel[16];       /* bit p set = point p takes part (Evaluator's keypoint_list); all zero = all P points */
+  float* err;             /* [B] mean over the selected points of |pred - gt|, metres (MPJPE)              or NULL */
+  float* pa_err;          /* [B] the same after the similarity alignment of pred onto gt (PA-MPJPE)        or NULL */
+  float* aligned;         /* [B][n_sel][3] S1_hat, the selected points in ascending index order            or NULL */
+  float* transform;       /* [B][13]: scale, R row-major (9), t (3), with S1_hat = scale * R * x + t, x a point of pred
+                             after the root subtraction                                                    or NULL */
+} hm_pose_eval_args;
+/* All checks run on the host before the launch (HM_ERR_ARG): null args / pred / gt, B <= 0, P outside 1..1024, gt_stride not 3
+ * or 4, root outside -1..P-1, a bit of sel at or past P, all four outputs NULL, pred or gt not 4-byte aligned. */
+int hm_pose_eval(const hm_pose_eval_args* args, void* stream);
 
 /* Optional per-launch timing (HIP events on the launch stream); kinds below. */
 enum { HM_K_GEMM = 0, HM_K_LAYERNORM = 1, HM_K_ATTENTION = 2, HM_K_IM2COL = 3, HM_K_LINEAR_F32 = 4,
