@@ -23,6 +23,15 @@
 namespace {
 
 constexpr int BK_DEFAULT = 64;
+// HM_OPT_GEMM_STAGGER: 0 = each kernel's default below, 1 = lockstep everywhere, 2 = staggered wherever the shape allows;
+// tuning: 3 = only the persistent kernel staggered, 4 = only the in-loop-residual kernel.  Both defaults are the staggered
+// form: in the interleaved two-in-flight whole-forward A/B each of them alone, and both together, was faster than lockstep
+// in every round (profiles/r05_stagger_model_ab.log).
+constexpr bool HM_STAGGER_DEFAULT_PX = true, HM_STAGGER_DEFAULT_X3R = true;
+static bool stagger_on(bool dflt, int only) {
+  const int v = hm_option(HM_OPT_GEMM_STAGGER);
+  return v == 0 ? dflt : (v == 2 || v == only);
+}
 int g_px_grid = -2;    // workgroups of gemm_px_kernel: -2 read HM_PX_GRID on first use, -1 default
 
 struct KArgs {                                    // kernel-side view of either entry point
@@ -980,8 +989,34 @@ int launch_rs(const KArgs& g, hipStream_t s) {
 //   (tests/test_isa_audit.py checks the emitted ISA).
 //   The 18 steps that issue or consume residual pieces are unrolled (the piece index selects accumulator registers); steps
 //   18.. run in a loop.  Requires whole tiles, K >= 20 x 64, resid_mod == 0, 32-bit residual offsets (launcher: rin_ok).
-template <class T>
-__global__ __launch_bounds__(512, 2) void gemm_x3r_kernel(const KArgs g) {
+//   Staggered form (STAG; gemm_x3rs_kernel).  In the lockstep form the two waves of a SIMD (wave i and wave i + 4) leave every
+//   barrier together, read their fragments together while the MFMA pipe idles and multiply together while the LDS idles.
+//   With STAG the role is wave-uniform: waves 0-3 LEAD and run the program above unchanged; waves 4-7 LAG by one sub-step.
+//   A lagging wave keeps the fragments of sub-step 1 in the registers that hold them, carries them across the barrier and
+//   multiplies them first in the next interval:
+//       lead, interval t:  wait  barrier  read(t,0) mma(t,0)  copies  read(t,1) mma(t,1)
+//       lag,  interval t:  wait  barrier  copies  mma(t-1,1)  read(t,0) mma(t,0)  read(t,1)
+//   so that a SIMD's partners multiply and read alternately.  Interval 0 of a lagging wave has no pending mma; after the
+//   last interval one is left over and runs behind the post-loop barrier.  Ring, copies and epilogue are the lockstep ones.
+//   (1) Barriers: both roles execute nk (one per step) + 2 (post-loop, bias vector) = nk + 2 s_barrier on every path; the
+//       role branch is taken once, in front of step 0, and both arms contain the same sequence of barriers.
+//   (2) vmcnt: a wave's vector-memory operations keep their order -- W(t+1) [4], X(t+2) [4], R(t) [2] once per interval,
+//       then the epilogue's stores (the lagging role issues the copies first behind the barrier: gemm_px_body has the
+//       measurement); MFMAs and LDS reads do not count.  Every wait sits at the same place of that sequence as in the
+//       leading role, so each count above holds for the lagging role as derived there: vmcnt(6) behind a step that
+//       issued R, vmcnt(4) otherwise, vmcnt(0) at the last step.
+//   (3) Carried reads: read(t,1) of a lagging wave comes from slots X t % 3 and W t & 1, which the copies issued behind
+//       barrier t+1 (W(t+2), X(t+3)) overwrite.  The lagging wave therefore waits lgkmcnt(0) BEFORE it signals barrier t+1
+//       (the statement names the twelve fragment registers: the reads cannot sink below it, no second set can appear).
+//   (4) Every read of step t's slots sits behind barrier t, which follows the wait that covers W(t), X(t) in every wave.
+//   (5) Bit identity: an accumulator sees mma(t+1,1), then + R(t), then mma(t+2,0) in the leading role.  The lagging role
+//       waits for R(t) in the same statement in front of barrier t+2 (it names the two registers) and adds the piece behind
+//       its pending mma(t+1,1), in front of mma(t+2,0): the same sequence of fp32 operations, equal bytes.
+//   (6) No scratch: one fragment set per wave.  A scheduling fence between the pending MFMAs and read(t,0), and the X-first
+//       fence inside the reads, keep hipcc from hoisting reads into a second set (tests/test_isa_audit_stagger.py: private
+//       segment 0).
+template <class T, bool STAG>
+__device__ __forceinline__ void gemm_x3r_body(const KArgs& g) {
   constexpr int WN = 2, MI = 4, NI = 8, NW = 8, BN = 256, BK = 64, ROWB = 128;
   constexpr int TILE_BYTES = 256 * ROWB;
   constexpr int XRING = 0, WRING = 3 * TILE_BYTES;
@@ -1009,13 +1044,13 @@ __global__ __launch_bounds__(512, 2) void gemm_x3r_kernel(const KArgs g) {
     const char* base = X + (size_t)kt * ROWB;
     const unsigned l = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem + XRING + slot * TILE_BYTES + wave * XI * 1024);
 #pragma unroll
-    for (int i = 0; i < XI; ++i) glds16_lean_s(base, xoff[i], l + i * 1024);
+    for (int i = 0; i < XI; ++i) glds16_lean_s(base + (STAG ? (size_t)i * 8 * g.ldx * 2 : 0), xoff[STAG ? 0 : i], l + i * 1024);
   };
   auto dma_w = [&](int slot, int kt) {
     const char* base = W + (size_t)kt * ROWB;
     const unsigned l = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem + WRING + slot * TILE_BYTES + wave * WI * 1024);
 #pragma unroll
-    for (int i = 0; i < WI; ++i) glds16_lean_s(base, woff[i], l + i * 1024);
+    for (int i = 0; i < WI; ++i) glds16_lean_s(base + (STAG ? (size_t)i * 8 * g.ldw * 2 : 0), woff[STAG ? 0 : i], l + i * 1024);
   };
   // residual piece (ni, mi) of this wave: rows mb + 16 mi + (lane & 15), columns nb + 16 ni + 4 (lane >> 4) .. + 3
   const int mb = m0 + wr * 16 * MI, nb = n0 + wc * 16 * NI;
@@ -1023,6 +1058,8 @@ __global__ __launch_bounds__(512, 2) void gemm_x3r_kernel(const KArgs g) {
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) roff[mi] = (unsigned)(mb + mi * 16 + (lane & 15)) * (unsigned)(g.ldr * 4) + (unsigned)(nb + 4 * (lane >> 4)) * 4;
   const char* rbase = (const char*)g.resid;
+  // (STAG: the lagging role has a fragment set live at every point, so the row step of copy i / piece mi rides in the scalar base
+  //  and one lane offset serves all four -- 9 VGPRs; the lockstep form keeps its per-row lane offsets)
 
   f32x4_t acc[NI][MI];
 #pragma unroll
@@ -1048,6 +1085,34 @@ __global__ __launch_bounds__(512, 2) void gemm_x3r_kernel(const KArgs g) {
     __builtin_amdgcn_s_setprio(0);
   };
 
+  // the lagging role's fragment set, carried across barriers (STAG only)
+  vec8 cwf[NI], cxf[MI];
+  auto rd = [&](int xslot, int wslot, int ks) {
+    const char* lx = smem + XRING + xslot * TILE_BYTES;
+    const char* lw = smem + WRING + wslot * TILE_BYTES;
+    const int coff = ((ks * 4 + fch) ^ fsw) * 16;
+#pragma unroll
+    for (int i = 0; i < MI; ++i) cxf[i] = *(const vec8*)(lx + (wr * 16 * MI + i * 16 + frow) * ROWB + coff);
+    __builtin_amdgcn_sched_barrier(0);                 // X fragments first, as in substep
+#pragma unroll
+    for (int i = 0; i < NI; ++i) cwf[i] = *(const vec8*)(lw + (wc * 16 * NI + i * 16 + frow) * ROWB + coff);
+  };
+  auto mm = [&]() {
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = T::mfma(cwf[ni], cxf[mi], acc[ni][mi]);
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);                 // rule 6: no read of the next fragments above these MFMAs
+  };
+  // rule 3: the carried reads have retired before this wave signals the barrier
+  auto carry_fence = [&]() {
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(cxf[0]), "+v"(cxf[1]), "+v"(cxf[2]), "+v"(cxf[3]), "+v"(cwf[0]), "+v"(cwf[1]), "+v"(cwf[2]), "+v"(cwf[3]),
+                   "+v"(cwf[4]), "+v"(cwf[5]), "+v"(cwf[6]), "+v"(cwf[7]) :: "memory");
+  };
+
   const int nk = g.K / BK;                              // launcher: nk >= RSTEPS + 4
   dma_x(0, 0);
   dma_w(0, 0);
@@ -1058,9 +1123,23 @@ __global__ __launch_bounds__(512, 2) void gemm_x3r_kernel(const KArgs g) {
   else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
 
   f32x4_t rq[3][2];                                     // residual pieces in flight: issued in step t, consumed in step t + 2
-  // One unrolled step.  T_ = step index (compile time): issues R(T_) when T_ < RSTEPS, consumes R(T_ - 2) when 2 <= T_ < RSTEPS + 2.
-  auto ustep = [&](auto TC) {
+  // the vector-memory operations of unrolled step t
+  auto ucopies = [&](auto TC) {
     constexpr int t = decltype(TC)::value;
+    const unsigned* ro = roff; const char* rb = rbase; const size_t rstep = (size_t)16 * g.ldr * 4;   // (named here: captured)
+    dma_w((t + 1) & 1, t + 1);                         // W first, then X, then the residual pieces: the counted waits rely on this order
+    dma_x((t + 2) % 3, t + 2);
+    if constexpr (t < RSTEPS) {
+      constexpr int ni0 = 2 * (t / 4), mi = t % 4;
+      f32x4_t (&r)[2] = rq[t % 3];
+      asm volatile("global_load_dwordx4 %0, %2, %3\n\tglobal_load_dwordx4 %1, %2, %3 offset:64"
+                   : "=&v"(r[0]), "=&v"(r[1]) : "v"(ro[STAG ? 0 : mi]), "s"(rb + ni0 * 64 + (STAG ? mi * rstep : 0)) : "memory");
+    }
+  };
+  // One unrolled step.  T_ = step index (compile time): issues R(T_) when T_ < RSTEPS, consumes R(T_ - 2) when 2 <= T_ < RSTEPS + 2.
+  auto ustep = [&](auto TC, auto LAGC) {
+    constexpr int t = decltype(TC)::value;
+    constexpr bool LAG = decltype(LAGC)::value;
     constexpr bool CONSUME = t >= 2 && t < RSTEPS + 2;
     constexpr bool PREV_ISSUED = t >= 1 && t - 1 < RSTEPS;           // step t - 1 put 2 residual loads behind its copies
     if constexpr (t >= 1) {
@@ -1069,45 +1148,70 @@ __global__ __launch_bounds__(512, 2) void gemm_x3r_kernel(const KArgs g) {
         if constexpr (PREV_ISSUED) asm volatile("s_waitcnt vmcnt(6)" : "+v"(r[0]), "+v"(r[1]) :: "memory");
         else asm volatile("s_waitcnt vmcnt(4)" : "+v"(r[0]), "+v"(r[1]) :: "memory");
         constexpr int p = t - 2, ni0 = 2 * (p / 4), mi = p % 4;
-        acc[ni0][mi] += r[0];                           // (before the barrier: this wave would be waiting for the others anyway)
-        acc[ni0 + 1][mi] += r[1];
+        if constexpr (!LAG) {
+          acc[ni0][mi] += r[0];                         // (before the barrier: this wave would be waiting for the others anyway)
+          acc[ni0 + 1][mi] += r[1];
+        }
       } else {
         if constexpr (PREV_ISSUED) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       }
     }
+    if constexpr (LAG && t >= 1) carry_fence();
     __builtin_amdgcn_s_barrier();                      // step t complete in LDS; everyone is done reading step t-1's slots
-    constexpr int xs = t % 3, xs2 = (t + 2) % 3;
-    substep(xs, t & 1, 0);
-    dma_w((t + 1) & 1, t + 1);                         // W first, then X, then the residual pieces: the counted waits rely on this order
-    dma_x(xs2, t + 2);
-    if constexpr (t < RSTEPS) {
-      constexpr int ni0 = 2 * (t / 4), mi = t % 4;
-      f32x4_t (&r)[2] = rq[t % 3];
-      asm volatile("global_load_dwordx4 %0, %2, %3\n\tglobal_load_dwordx4 %1, %2, %3 offset:64"
-                   : "=&v"(r[0]), "=&v"(r[1]) : "v"(roff[mi]), "s"(rbase + ni0 * 64) : "memory");
+    constexpr int xs = t % 3;
+    if constexpr (LAG) {
+      ucopies(TC);                                      // first behind the barrier (R(t) goes to the set R(t-3) left at step t-1)
+      if constexpr (t >= 1) mm();                       // mma(t-1, 1) on the carried fragments
+      if constexpr (CONSUME) {                          // rule 5: R(t-2) behind mma(t-1, 1), in front of mma(t, 0)
+        f32x4_t (&r)[2] = rq[(t - 2) % 3];
+        constexpr int p = t - 2, ni0 = 2 * (p / 4), mi = p % 4;
+        acc[ni0][mi] += r[0];
+        acc[ni0 + 1][mi] += r[1];
+      }
+      rd(xs, t & 1, 0);
+      mm();
+      rd(xs, t & 1, 1);
+    } else {
+      substep(xs, t & 1, 0);
+      ucopies(TC);
+      substep(xs, t & 1, 1);
     }
-    substep(xs, t & 1, 1);
   };
-#define HM_USTEP(n) ustep(std::integral_constant<int, n>{})
-  HM_USTEP(0); HM_USTEP(1); HM_USTEP(2); HM_USTEP(3); HM_USTEP(4); HM_USTEP(5); HM_USTEP(6); HM_USTEP(7); HM_USTEP(8);
-  HM_USTEP(9); HM_USTEP(10); HM_USTEP(11); HM_USTEP(12); HM_USTEP(13); HM_USTEP(14); HM_USTEP(15); HM_USTEP(16); HM_USTEP(17);
+  // all K-steps in one role; both roles execute nk barriers here
+  auto ksteps = [&](auto LAGC) {
+    constexpr bool LAG = decltype(LAGC)::value;
+#define HM_USTEP(n) ustep(std::integral_constant<int, n>{}, LAGC)
+    HM_USTEP(0); HM_USTEP(1); HM_USTEP(2); HM_USTEP(3); HM_USTEP(4); HM_USTEP(5); HM_USTEP(6); HM_USTEP(7); HM_USTEP(8);
+    HM_USTEP(9); HM_USTEP(10); HM_USTEP(11); HM_USTEP(12); HM_USTEP(13); HM_USTEP(14); HM_USTEP(15); HM_USTEP(16); HM_USTEP(17);
 #undef HM_USTEP
-  static_assert(RSTEPS + 2 == 18 && 18 % 3 == 0, "the loop below starts at step 18 with X slot 0");
-  int xs = 0;
-  for (int kt = RSTEPS + 2; kt < nk; ++kt) {
-    if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    const int xs2 = xs == 0 ? 2 : xs - 1;
-    substep(xs, kt & 1, 0);
-    if (kt + 1 < nk) dma_w((kt + 1) & 1, kt + 1);
-    if (kt + 2 < nk) dma_x(xs2, kt + 2);
-    substep(xs, kt & 1, 1);
-    xs = xs == 2 ? 0 : xs + 1;
+    static_assert(RSTEPS + 2 == 18 && 18 % 3 == 0, "the loop below starts at step 18 with X slot 0");
+    int xs = 0;
+    for (int kt = RSTEPS + 2; kt < nk; ++kt) {
+      if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if constexpr (LAG) carry_fence();
+      __builtin_amdgcn_s_barrier();
+      const int xs2 = xs == 0 ? 2 : xs - 1;
+      auto copies = [&]() {
+        if (kt + 1 < nk) dma_w((kt + 1) & 1, kt + 1);
+        if (kt + 2 < nk) dma_x(xs2, kt + 2);
+      };
+      if constexpr (LAG) { copies(); mm(); rd(xs, kt & 1, 0); mm(); rd(xs, kt & 1, 1); }
+      else { substep(xs, kt & 1, 0); copies(); substep(xs, kt & 1, 1); }
+      xs = xs == 2 ? 0 : xs + 1;
+    }
+    if constexpr (LAG) carry_fence();
+    __builtin_amdgcn_s_barrier();                      // the ring is free: per-column vectors, then epilogue staging
+    if constexpr (LAG) mm();                           // the left-over mma(nk-1, 1): its fragments are in registers
+  };
+  if constexpr (STAG) {
+    if (wave >= 4) ksteps(std::true_type{});
+    else ksteps(std::false_type{});
+  } else {
+    ksteps(std::false_type{});
   }
 
-  __builtin_amdgcn_s_barrier();                        // the ring is free: per-column vectors, then epilogue staging
   constexpr int EPI_BYTES = NW * epi_stage_bytes(MI, NI);
   float2* rowstat = (float2*)(smem + EPI_BYTES);       // unused by this epilogue
   float* colvec = (float*)(rowstat + 256);
@@ -1116,6 +1220,11 @@ __global__ __launch_bounds__(512, 2) void gemm_x3r_kernel(const KArgs g) {
   epilogue<T, HM_EPI_F32, MI, NI>(g, acc, mb, nb, lane, smem + wave * epi_stage_bytes(MI, NI),
                                   rowstat + wr * 16 * MI, colvec + wc * 16 * NI, colvec + BN + wc * 16 * NI, 0);
 }
+
+template <class T>
+__global__ __launch_bounds__(512, 2) void gemm_x3r_kernel(const KArgs g) { gemm_x3r_body<T, false>(g); }
+template <class T>
+__global__ __launch_bounds__(512, 2) void gemm_x3rs_kernel(const KArgs g) { gemm_x3r_body<T, true>(g); }
 
 // what gemm_x3r_kernel requires: whole 256 x 256 tiles, the 18 unrolled steps plus at least two more (so that every copy the
 // unrolled steps issue exists), a plain residual (no row modulus), 32-bit residual offsets, 16-byte residual rows
@@ -1127,9 +1236,10 @@ bool rin_ok(const KArgs& g) {
 template <class T>
 int launch_rin(const KArgs& g, hipStream_t s) {
   constexpr int LDS = 5 * 256 * 128;
-  auto kern = gemm_x3r_kernel<T>;
-  static HmLdsOnce lds_once;
-  if (const int rc = lds_once.ensure((const void*)kern, LDS, "gemm: cannot raise the dynamic LDS limit")) return rc;
+  const bool stag = stagger_on(HM_STAGGER_DEFAULT_X3R, 4);
+  auto kern = stag ? gemm_x3rs_kernel<T> : gemm_x3r_kernel<T>;
+  static HmLdsOnce lds_once[2];      // one per form
+  if (const int rc = lds_once[stag ? 1 : 0].ensure((const void*)kern, LDS, "gemm: cannot raise the dynamic LDS limit")) return rc;
   hipLaunchKernelGGL(kern, dim3((g.M >> 8) * (g.N >> 8)), dim3(512), LDS, s, g);
   return hm_check_launch("hm_gemm");
 }
@@ -1158,8 +1268,31 @@ int launch_rin(const KArgs& g, hipStream_t s) {
 //   issue behind five reads instead of nine and the remaining W reads retire under them: -1.6 % per ViT block
 //   (profiles/r04_gemm_xfirst_ab.log).  The MFMA runs are raised with s_setprio.  DESIGN.md section 4 has the alternatives
 //   measured against these.
-template <class T, int EPI, bool DIRECT = true>
-__global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) {
+//   Staggered form (STAG; gemm_pxs_kernel): waves 0-3 lead and run the program above unchanged, waves 4-7 lag by one sub-step
+//   (the roles, the reason and rules (3), (4), (6) are derived at gemm_x3r_body; the wave-uniform branch is taken once, in
+//   front of the tile loop):
+//       lead, step gs:  wait  barrier  read(gs,0) mma(gs,0)  copies  read(gs,1) mma(gs,1)
+//       lag,  step gs:  wait  barrier  copies  mma(gs-1,1)  read(gs,0) mma(gs,0)  read(gs,1)
+//   The lagging role issues its copies first behind the barrier (they target the slots its carried reads came from, which
+//   retired in front of the barrier).  Issued where the leaders issue theirs -- behind mma(gs,0), half an interval later in
+//   this role -- W(gs+1) had a third of a step to arrive and every barrier waited for it: 8-16 % slower than lockstep on the
+//   persistent shapes in the first A/B of this kernel (qkv 115.8 -> 134.0 us, fc1 155.2 -> 173.7, kv 161.8 -> 177.3; that run's
+//   log was not kept, DESIGN.md section 4 repeats the figures as unrecorded).
+//   A lagging wave's first step of a TILE has no pending mma: the one left over from the previous tile's last step runs behind
+//   that tile's post-loop barrier, in front of its epilogue.  That barrier protects LDS only (the staging slots), the carried
+//   fragments are in registers (lgkmcnt(0) in front of the barrier), so the lagging wave signals first and multiplies behind it
+//   while the leaders' epilogue runs beside those MFMAs.
+//   Both roles raise their MFMA runs with s_setprio 1 .. 0.  Measured against it under the stagger (whole forwards, staggered
+//   over lockstep in one process): no priority in the lagging role 0.979 serial / 0.984 two in flight, the lagging role at
+//   priority 1 for its whole K loop 0.972 / 0.995, around the runs 0.953 / 0.975 (profiles/r05_stagger_prio_ab.log).
+//   (1) Barriers: both roles execute nk + 1 s_barrier per tile (one per step, one post-loop), my * (nk + 1) in all; a workgroup
+//       with my == 0 returns as a whole in front of the first one.  Tile hand-over adds none.
+//   (2) vmcnt: per wave the order bias pair [2], then per step W(gs+1) [4], X(gs+2) [4] (no other vector-memory operation in a step), then
+//       the 16 stores is the leading role's order, MFMAs and LDS reads do not count, and every wait sits at the same place of
+//       it: vmcnt(22) at a tile's first step (16 stores + X(gs+1) [4] + the bias pair may stay), vmcnt(4) inside a tile (X(gs+1)),
+//       vmcnt(0) at the very last step, vmcnt(12) as the bias fence behind the post-loop barrier (never stalls).
+template <class T, int EPI, bool DIRECT, bool STAG>
+__device__ __forceinline__ void gemm_px_body(const KArgs& g) {
   static_assert(EPI == HM_EPI_STORE || EPI == HM_EPI_GELU || EPI == HM_EPI_SILU, "16-bit store epilogues only");
   constexpr int WN = 2, MI = 4, NI = 8, ROWB = 128;
   constexpr int TILE_BYTES = 256 * ROWB;                               // 32 KB
@@ -1198,12 +1331,13 @@ __global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) {
   auto dma_x = [&](int slot, const char* base) {
     const unsigned d = __builtin_amdgcn_readfirstlane(XRING + slot * TILE_BYTES + wave * XI * 1024 + lds_base);
 #pragma unroll
-    for (int i = 0; i < XI; ++i) glds16_lean_s(base, xoff[i], d + i * 1024);
+    for (int i = 0; i < XI; ++i) glds16_lean_s(base + (STAG ? (size_t)i * 8 * g.ldx * 2 : 0), xoff[STAG ? 0 : i], d + i * 1024);
   };
+  // (STAG: the row step of copy i rides in the scalar base and one lane offset serves all four, as in gemm_x3r_body)
   auto dma_w = [&](int slot, const char* base) {
     const unsigned d = __builtin_amdgcn_readfirstlane(WRING + slot * TILE_BYTES + wave * WI * 1024 + lds_base);
 #pragma unroll
-    for (int i = 0; i < WI; ++i) glds16_lean_s(base, woff[i], d + i * 1024);
+    for (int i = 0; i < WI; ++i) glds16_lean_s(base + (STAG ? (size_t)i * 8 * g.ldw * 2 : 0), woff[STAG ? 0 : i], d + i * 1024);
   };
   // cursors over the concatenated step sequence: X runs two steps ahead of the MFMAs, W one
   int xti = 0, xkt = 0, wti = 0, wkt = 0, m0, n0;
@@ -1243,6 +1377,34 @@ __global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) {
     __builtin_amdgcn_s_setprio(0);
   };
 
+  // the lagging role's fragment set, carried across barriers (STAG only)
+  vec8 cwf[NI], cxf[MI];
+  auto rd = [&](int xslot, int wslot, int ks) {
+    const char* lx = smem + XRING + xslot * TILE_BYTES;
+    const char* lw = smem + WRING + wslot * TILE_BYTES;
+    const int coff = ((ks * 4 + fch) ^ fsw) * 16;
+#pragma unroll
+    for (int i = 0; i < MI; ++i) cxf[i] = *(const vec8*)(lx + (wr * 16 * MI + i * 16 + frow) * ROWB + coff);
+    __builtin_amdgcn_sched_barrier(0);                 // X fragments first, as in substep
+#pragma unroll
+    for (int i = 0; i < NI; ++i) cwf[i] = *(const vec8*)(lw + (wc * 16 * NI + i * 16 + frow) * ROWB + coff);
+  };
+  auto mm = [&]() {
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) acc[ni][mi] = T::mfma(cwf[ni], cxf[mi], acc[ni][mi]);
+    __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_sched_barrier(0);                 // no read of the next fragments above these MFMAs
+  };
+  // the carried reads have retired before this wave signals the barrier (the statement names the twelve fragment registers)
+  auto carry_fence = [&]() {
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(cxf[0]), "+v"(cxf[1]), "+v"(cxf[2]), "+v"(cxf[3]), "+v"(cwf[0]), "+v"(cwf[1]), "+v"(cwf[2]), "+v"(cwf[3]),
+                   "+v"(cwf[4]), "+v"(cwf[5]), "+v"(cwf[6]), "+v"(cwf[7]) :: "memory");
+  };
+
   // prologue: X(0), W(0), X(1) (nk >= 2)
   dma_x(0, xbase); next_x();
   dma_w(0, wbase); next_w();
@@ -1250,6 +1412,8 @@ __global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) {
   asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
 
   int gs = 0, xs = 0;                                  // global step, its X slot (gs % 3); W slot = gs & 1
+  auto run_tiles = [&](auto LAGC) {
+  constexpr bool LAG = decltype(LAGC)::value;
   for (int ti = 0; ti < my; ++ti) {
     if (ti > 0) origin(ti, m0, n0);
     // this wave's 128 bias values, two per lane, requested now and moved to LDS after the loop.  Issued from asm so that
@@ -1269,22 +1433,44 @@ __global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) {
 #pragma unroll
       for (int b = 0; b < MI; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     int xs_last = 0, ws_last = 0;
-    for (int kt = 0; kt < nk; ++kt, ++gs) {
+    auto step = [&](int kt) {
       if (gs > 0) {
         if (kt == 0) asm volatile("s_waitcnt vmcnt(22)" ::: "memory");   // 16 epilogue stores + X(gs+1) + the 2 bias loads may stay in flight
         else if (gs + 1 < S) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // X(gs+1)
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
+      if constexpr (LAG) { if (kt > 0) carry_fence(); }
       __builtin_amdgcn_s_barrier();                    // step gs complete in LDS; everyone is done with step gs-1's slots (and epilogue)
       const int ws = gs & 1, xs2 = xs == 0 ? 2 : xs - 1;
-      substep(xs, ws, 0);
-      if (gs + 1 < S) { dma_w(ws ^ 1, wbase + (size_t)wkt * ROWB); next_w(); }   // W first, then X: the counted waits rely on this order
-      if (gs + 2 < S) { dma_x(xs2, xbase + (size_t)xkt * ROWB); next_x(); }
-      substep(xs, ws, 1);
+      auto copies = [&]() {
+        if (gs + 1 < S) { dma_w(ws ^ 1, wbase + (size_t)wkt * ROWB); next_w(); }   // W first, then X: the counted waits rely on this order
+        if (gs + 2 < S) { dma_x(xs2, xbase + (size_t)xkt * ROWB); next_x(); }
+      };
+      if constexpr (LAG) {
+        copies();                                      // (first behind the barrier: see the header)
+        if (kt > 0) mm();                              // mma(gs-1, 1) on the carried fragments
+        rd(xs, ws, 0);
+        mm();
+        rd(xs, ws, 1);
+      } else {
+        substep(xs, ws, 0);
+        copies();
+        substep(xs, ws, 1);
+      }
       xs_last = xs; ws_last = ws;
       xs = xs == 2 ? 0 : xs + 1;
+      ++gs;
+    };
+    if constexpr (LAG) {
+      // (step 0 apart: the fragments a lagging wave carries are then defined in every tile, and none is live across an epilogue)
+      step(0);
+      for (int kt = 1; kt < nk; ++kt) step(kt);
+    } else {
+      for (int kt = 0; kt < nk; ++kt) step(kt);
     }
+    if constexpr (LAG) carry_fence();
     __builtin_amdgcn_s_barrier();                      // the last step's two slots are free: epilogue staging
+    if constexpr (LAG) mm();                           // the left-over mma of the tile's last step, behind the barrier
     // The bias pair landed long ago (the wait of step kt == 1 retired it; >= 16 copies were issued behind it).  This statement
     // is its fence: at most 12 operations are in flight here (X(gs+1), W(gs+1), X(gs+2)), so it never stalls, and it names the
     // two registers as read-write operands -- no use, copy or spill of them can be scheduled above it.
@@ -1373,7 +1559,19 @@ __global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) {
       }
     }
   }
+  };
+  if constexpr (STAG) {
+    if (wave >= 4) run_tiles(std::true_type{});
+    else run_tiles(std::false_type{});
+  } else {
+    run_tiles(std::false_type{});
+  }
 }
+
+template <class T, int EPI, bool DIRECT = true>
+__global__ __launch_bounds__(512, 2) void gemm_px_kernel(const KArgs g) { gemm_px_body<T, EPI, DIRECT, false>(g); }
+template <class T, int EPI, bool DIRECT = true>
+__global__ __launch_bounds__(512, 2) void gemm_pxs_kernel(const KArgs g) { gemm_px_body<T, EPI, DIRECT, true>(g); }
 
 // Default persistent grid: one workgroup per CU on all but ONE CU of every XCD (248 of 256; see launch_px), unless all 256 save
 // a whole round of tiles (1020 tiles = fc1 at 68 hands: 4 rounds instead of 5).
@@ -1415,9 +1613,11 @@ int launch_px(const KArgs& g, hipStream_t s) {
   // HM_OPT_PX_LDS_EPILOGUE: 0 = that choice, 1 = always through LDS, 2 = always lane swaps.
   const int form = hm_option(HM_OPT_PX_LDS_EPILOGUE);
   const bool staged = form == 1 || (form == 0 && EPI != HM_EPI_GELU && EPI != HM_EPI_SILU);
-  auto kern = staged ? gemm_px_kernel<T, EPI, false> : gemm_px_kernel<T, EPI, true>;
-  static HmLdsOnce lds_once[2];      // (per instantiation of this launcher: one pair per (T, EPI))
-  if (const int rc = lds_once[staged ? 1 : 0].ensure((const void*)kern, LDS, "gemm: cannot raise the dynamic LDS limit")) return rc;
+  const bool stag = stagger_on(HM_STAGGER_DEFAULT_PX, 3);
+  auto kern = stag ? (staged ? gemm_pxs_kernel<T, EPI, false> : gemm_pxs_kernel<T, EPI, true>)
+                   : (staged ? gemm_px_kernel<T, EPI, false> : gemm_px_kernel<T, EPI, true>);
+  static HmLdsOnce lds_once[4];      // (per instantiation of this launcher: one per form and (T, EPI))
+  if (const int rc = lds_once[(stag ? 2 : 0) + (staged ? 1 : 0)].ensure((const void*)kern, LDS, "gemm: cannot raise the dynamic LDS limit")) return rc;
   const int tiles = (g.M >> 8) * (g.N >> 8);
   int cus = hm_device_cu_count();
   if (cus <= 0) cus = 256;

@@ -45,6 +45,8 @@ extern "C" int hm_set_option(int key, int value) {
   if (value < 0) return hm_set_error(HM_ERR_ARG, "hm_set_option: value must be >= 0");
   if ((key == HM_OPT_PX_GRID || key == HM_OPT_FP8P_GRID) && value != 0 && (value < 8 || value % 8 != 0))
     return hm_set_error(HM_ERR_ARG, "hm_set_option: a persistent grid is 0 (default) or a multiple of the 8 XCDs");
+  if (key == HM_OPT_GEMM_STAGGER && value > 4)
+    return hm_set_error(HM_ERR_ARG, "hm_set_option: HM_OPT_GEMM_STAGGER is 0 (default), 1 (lockstep), 2 (staggered), 3 or 4 (one kernel staggered)");
   g_opts[key].store(value, std::memory_order_relaxed);
   return HM_OK;
 }

@@ -22,7 +22,7 @@ HM_VERSION = 402      # include/hamer_hip.h: load() refuses a library built from
 OPTION_NAMES = ("HM_OPT_PX_GRID", "HM_OPT_FP8P_GRID", "HM_OPT_FP8_ONE_TILE", "HM_OPT_FP8P_RESID", "HM_OPT_TOME_NO_SPLITK",
                 "HM_OPT_TOME_SCALAR_ATTENTION", "HM_OPT_RESID_IN_EPILOGUE", "HM_OPT_CONV_TILE", "HM_OPT_CONV_SPLITK",
                 "HM_OPT_PX_LDS_EPILOGUE", "HM_OPT_CONV_DIRECT", "HM_OPT_GEMM_TILE_RULE", "HM_OPT_CONV_KGROUPS",
-                "HM_OPT_CONV_GENERAL_LOADER", "HM_OPT_CONV_STEM_PAIR", "HM_OPT_ATT_GRID")
+                "HM_OPT_CONV_GENERAL_LOADER", "HM_OPT_CONV_STEM_PAIR", "HM_OPT_ATT_GRID", "HM_OPT_GEMM_STAGGER")
 globals().update({_n: _i for _i, _n in enumerate(OPTION_NAMES)})
 
 EXPORTS = [

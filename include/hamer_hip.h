@@ -106,7 +106,8 @@ enum {
   HM_OPT_CONV_GENERAL_LOADER = 13,  /* tuning / tests: 1 = the implicit-GEMM convolution takes its general loader (per-lane tap arithmetic every K-step) even where the lean one applies (Cin % 64 == 0); 0 = automatic.  Same bytes either way */
   HM_OPT_CONV_STEM_PAIR = 14,       /* tuning / tests: 1 = hm_conv2d_stem_pair (and HM_OP_CONV_PAIR of hm_yolo_run) always runs its two convolutions as two launches; 0 = one launch where the fused kernel applies.  Same bytes either way */
   HM_OPT_ATT_GRID = 15,             /* tests: the number of compute units the persistent attention launches (hm_vit_attention, hm_vit_attention_mx8, the MFMA path of hm_tome_attention) plan for; 0 = the device's count.  Any value >= 1 (a grid that is no multiple of the 8 XCDs is wanted here): few units make every workgroup walk several (crop, head) items.  Same bytes at every value */
-  HM_OPT_COUNT = 16
+  HM_OPT_GEMM_STAGGER = 16,         /* 256x256 GEMM K loops (persistent 16-bit store kernel, in-loop fp32-residual kernel): 0 = each kernel's default, 1 = lockstep (all eight waves in one phase), 2 = staggered wherever the shape allows (waves 4-7 one sub-step behind waves 0-3); tuning: 3 = persistent kernel only, 4 = residual kernel only; hm_set_option refuses any other value.  Same bytes at every value */
+  HM_OPT_COUNT = 17
 };
 int hm_set_option(int key, int value);
 int hm_get_option(int key);

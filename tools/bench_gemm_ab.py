@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Interleaved A/B of GEMM tile variants on the ViT-H shapes (random data): ROUNDS rounds, every round runs
 every variant REPS times per shape; reports the median over all launches of a variant (200 / 201: the default tile with
-the fp32 residual fetched in the epilogue / inside the K loop; >= 100 otherwise: default tile with group_m = v - 100).  One process, one
+the fp32 residual fetched in the epilogue / inside the K loop; 203 / 204: the default tile with HM_OPT_GEMM_STAGGER = 1 / 2, the
+lockstep / the staggered K loop of the 256 x 256 kernels; >= 100 otherwise: default tile with group_m = v - 100).  One process, one
 device, variants interleaved so clock drift hits them equally.  Env: VARIANTS=0,10,24,26 ROUNDS=6 REPS=5"""
 import os
 import sys
@@ -36,7 +37,8 @@ res = {}
 def setv(v):
     L.check(lib.hm_set_option(L.HM_OPT_RESID_IN_EPILOGUE, 1 if v == 200 else 0))
     L.check(lib.hm_set_option(L.HM_OPT_PX_LDS_EPILOGUE, 1 if v == 202 else (2 if v == 201 else 0)))     # 202 / 201: persistent GEMM epilogue through LDS / by lane swaps
-    if v in (200, 201, 202):             # 200 / 201: default tile with the fp32 residual fetched in the epilogue (round 2) / inside the K loop (round 3)
+    L.check(lib.hm_set_option(L.HM_OPT_GEMM_STAGGER, 1 if v == 203 else (2 if v == 204 else 0)))         # 203 / 204: lockstep / staggered K loop
+    if v in (200, 201, 202, 203, 204):   # 200 / 201: default tile with the fp32 residual fetched in the epilogue (round 2) / inside the K loop (round 3)
         L.check(lib.hm_gemm_set_variant(-1)); L.check(lib.hm_gemm_set_group_m(8))
     elif v >= 100:
         L.check(lib.hm_gemm_set_variant(-1)); L.check(lib.hm_gemm_set_group_m(v - 100))

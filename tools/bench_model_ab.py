@@ -2,7 +2,7 @@
 """Interleaved A/B of WHOLE forwards (BASELINE configs[1]: B = 64 crops resident in HBM) under different library switches, in
 one process on one device: ROUNDS rounds, every round times STEPS steps of every configuration (wall clock around a
 synchronised region, the bench.py protocol).  Box-to-box noise is +-2 %; only numbers from one process compare.
-Configurations: CONFIGS="name:in_flight:opt=val,opt=val;..." with opt in {resid_epi, variant, px_grid, px_lds_epi, fold_ln}.
+Configurations: CONFIGS="name:in_flight:opt=val,opt=val;..." with opt in {resid_epi, variant, px_grid, px_lds_epi, fold_ln, stagger}.
 Default: serial and two-in-flight, residual in the epilogue (round 2) vs inside the K loop (round 3)."""
 import os
 import sys
@@ -50,6 +50,7 @@ def apply(o):
     L.check(lib.hm_set_option(L.HM_OPT_RESID_IN_EPILOGUE, int(o.get("resid_epi", 0))))
     L.check(lib.hm_set_option(L.HM_OPT_PX_GRID, int(o.get("px_grid", 0))))
     L.check(lib.hm_set_option(L.HM_OPT_PX_LDS_EPILOGUE, int(o.get("px_lds_epi", 0))))
+    L.check(lib.hm_set_option(L.HM_OPT_GEMM_STAGGER, int(o.get("stagger", 0))))
     L.check(lib.hm_gemm_set_variant(int(o.get("variant", -1))))
 
 
@@ -77,4 +78,5 @@ apply({})
 for name, *_ in configs:
     t = sorted(times[name])
     med = t[len(t) // 2]
-    print(f"{name:14s} median {med:7.3f} ms/step  min {t[0]:7.3f}  {B / med * 1e3:7.1f} hands/s  {B / med * 1e3 * 251.03e9 / 2.5e15 * 100:5.2f} % of peak", flush=True)
+    print(f"{name:14s} median {med:7.3f} ms/step  min {t[0]:7.3f}  {B / med * 1e3:7.1f} hands/s  {B / med * 1e3 * 251.03e9 / 2.5e15 * 100:5.2f} % of peak   rounds " +
+          " ".join(f"{v:.3f}" for v in times[name]), flush=True)
