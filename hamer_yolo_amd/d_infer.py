@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from .infer import *  # noqa: F401,F403
-from .infer import (FRAMES_PER_STEP, _default_models, _detection_list, _imread_bgr, _list_images, _antialias_args, _precise_hamer_args, _record_from, _render_args, apply_antialias_args, apply_precise_args, hamer_inference,  # noqa: F401
+from .infer import (FRAMES_PER_STEP, _default_models, _detection_list, _imread_bgr, _list_images, _antialias_args, _precise_hamer_args, _record_from, _render_args, render_keypoint_args, apply_antialias_args, apply_precise_args, hamer_inference,  # noqa: F401
                     hamer_opt, hand_record, iter_folder_results, load_intrinsics, reconstruct_and_save_obj_with_wrapper)
 from .rootnet.Model_RGB import get_model  # noqa: F401
 
@@ -68,7 +68,9 @@ def apply_rootnet_backbone(args) -> None:
 
 def main(argv=None):
     """``python -m hamer_yolo_amd.d_infer --input <RGB_dir> --output <out_dir> --intrinsics <cam_K.txt>``."""
-    args = _parser().parse_args(argv)
+    ap = _parser()
+    args = ap.parse_args(argv)
+    keypoint_kw = render_keypoint_args(ap, args)
     apply_precise_args(args)
     apply_antialias_args(args)
     apply_rootnet_backbone(args)
@@ -81,7 +83,8 @@ def main(argv=None):
         from .infer import _rank_world
         from .render import render_folder
         rank, world = _rank_world(None, None)
-        render_folder(args.input, args.output, args.render, hamer, k_real, style=args.render_style, rank=rank, world=world)
+        render_folder(args.input, args.output, args.render, hamer, k_real, style=args.render_style, rank=rank, world=world,
+                      **keypoint_kw)
     if args.hand_maps:
         from .infer import _rank_world
         from .render import hand_maps_folder

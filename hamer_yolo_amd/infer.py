@@ -1162,15 +1162,37 @@ def _render_args(ap: argparse.ArgumentParser) -> None:
     ap.add_argument('--render-style', type=str, default="flat", choices=["flat", "shaded", "smooth"],
                     help="flat: the reference's 0.6 green blend (reconstruct.py); shaded: opaque normal-shaded meshes; "
                          "smooth: z-buffered per pixel, smooth-shaded (the MeshRenderer look)")
+    ap.add_argument('--render-keypoints', type=str, default=None, choices=["over", "only"],
+                    help="with --render: draw the hands' 21 joints as skeletons over the mesh overlay (over) or onto the plain "
+                         "frames instead of it (only); off by default")
+    ap.add_argument('--keypoint-style', type=str, default="hamer", choices=["sar", "hamer", "openpose"],
+                    help="colours, order and default radii of the skeletons (default hamer: draw_2d_skeleton.py's)")
+    ap.add_argument('--keypoint-line-radius', type=int, default=None, help="bone half-width in pixels, 0..32 (default: by style)")
+    ap.add_argument('--keypoint-joint-radius', type=int, default=None, help="joint disc radius in pixels, 0..32 (default: by style)")
     ap.add_argument('--hand-maps', type=str, default=None, metavar="DIR",
                     help="after the records are written, write per frame into DIR the label mask <name>.npy (uint8, --hand-label on "
                          "hand pixels) and <name>_maps.npz (depth in metres, index of the covering hand)")
     ap.add_argument('--hand-label', type=int, default=3, help="the label --hand-maps writes on hand pixels (default 3)")
 
 
+def render_keypoint_args(ap: argparse.ArgumentParser, args) -> Dict:
+    """The keypoint arguments of ``render_folder`` the parsed flags stand for; ``--render-keypoints`` without ``--render`` is a
+    usage error."""
+    if args.render_keypoints and not args.render:
+        ap.error("--render-keypoints needs --render DIR")
+    for name in ("keypoint_line_radius", "keypoint_joint_radius"):
+        v = getattr(args, name)
+        if v is not None and not 0 <= v <= 32:
+            ap.error(f"--{name.replace('_', '-')} must be in 0..32")
+    return {"keypoints": args.render_keypoints, "keypoint_style": args.keypoint_style,
+            "line_radius": args.keypoint_line_radius, "joint_radius": args.keypoint_joint_radius}
+
+
 def main(argv=None):
     """CLI of infer.py:1479-1536: ``python -m hamer_yolo_amd.infer --input <RGB_dir> --output <out_dir>``."""
-    args = _parser().parse_args(argv)
+    ap = _parser()
+    args = ap.parse_args(argv)
+    keypoint_kw = render_keypoint_args(ap, args)
     k_real = load_intrinsics(args.intrinsics) if args.intrinsics else None
     if args.ckpt:
         hamer_opt.ckpt_path = args.ckpt
@@ -1197,7 +1219,8 @@ def main(argv=None):
         reconstruct_and_save_obj_with_wrapper(args.output, args.obj, hamer)
     if args.render:
         from .render import render_folder
-        n = render_folder(args.input, args.output, args.render, hamer, k_real, style=args.render_style, rank=rank, world=world)
+        n = render_folder(args.input, args.output, args.render, hamer, k_real, style=args.render_style, rank=rank, world=world,
+                          **keypoint_kw)
         print(f"{n} overlays written to {args.render}" + (f" (rank {rank})" if world > 1 else ""))
     if args.hand_maps:
         from .render import hand_maps_folder

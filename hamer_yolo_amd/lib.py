@@ -41,6 +41,7 @@ EXPORTS = [
     "hm_attention_grid",
     "hm_crop_aa_box_from_bbox", "hm_crop_batch_aa",
     "hm_pose_eval",
+    "hm_skeleton_overlay_workspace_bytes", "hm_skeleton_overlay",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -137,6 +138,14 @@ HM_STYLE_FLAT, HM_STYLE_SHADED = 0, 1      # hm_mesh_overlay styles
 
 class Mesh(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("frame", "v0", "nv", "f0", "nf")] + [("color_bgr", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+HM_SKEL_INTERLEAVED, HM_SKEL_BONES_FIRST = 0, 1      # hm_skeleton_overlay orders
+
+
+class Skeleton(C.Structure):
+    """hm_skeleton: one hand of hm_skeleton_overlay."""
+    _fields_ = [("image", C.c_int32), ("line_radius", C.c_int32), ("joint_radius", C.c_int32), ("threshold", C.c_float)]
 
 
 class SarHand(C.Structure):
@@ -257,6 +266,9 @@ def load() -> C.CDLL:
     lib.hm_stem4_im2col.argtypes = [vp, vp, i, i, i, i, vp]
     lib.hm_sar_saigb_ch.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
     lib.hm_pose_eval.argtypes = [C.POINTER(PoseEvalArgs), vp]
+    lib.hm_skeleton_overlay_workspace_bytes.argtypes = [i, i, i, i]
+    lib.hm_skeleton_overlay_workspace_bytes.restype = C.c_size_t
+    lib.hm_skeleton_overlay.argtypes = [vp, i, i, i, vp, i, C.POINTER(Skeleton), i, C.POINTER(C.c_uint8), i, vp, vp, C.c_size_t, vp]
     lib.hm_prof_begin.argtypes = [i]
     lib.hm_prof_collect.argtypes = [C.POINTER(ProfRecord), i]
     lib.hm_prof_end.argtypes = []
@@ -265,7 +277,8 @@ def load() -> C.CDLL:
             raise HipLibraryError(f"{LIB_PATH} does not export {name}")
         fn = getattr(lib, name)
         if name not in ("hm_version", "hm_last_error_string", "hm_hamer_workspace_bytes", "hm_nms_workspace_bytes", "hm_tome_index_bytes", "hm_conv_splitk_bytes",
-                        "hm_mesh_overlay_workspace_bytes", "hm_mesh_render_workspace_bytes"):
+                        "hm_mesh_overlay_workspace_bytes", "hm_mesh_render_workspace_bytes",
+                        "hm_skeleton_overlay_workspace_bytes"):
             fn.restype = i
     if lib.hm_version() != HM_VERSION:
         raise HipLibraryError(f"{LIB_PATH} reports HM_VERSION {lib.hm_version()}, this binding is written for {HM_VERSION}: "

@@ -6,6 +6,8 @@ style and per pixel by ``render_views``).  The drawing rule is stated in include
 * ``render_views``: meshes -> per view RGBA, depth and mesh-label maps resolved per pixel by a z-buffer (hm_mesh_render, DESIGN.md
   section 8.1; reference utils/mesh_renderer.py:243-320), optionally drawn over frames: what ``MeshRenderer``, ``get_image``,
   the ``smooth`` folder style and ``hand_maps_folder`` (``--hand-maps``: label mask, depth and hand index per frame) stand on.
+* ``skeleton_frames``: device images + device keypoints -> the 21-joint hand skeletons drawn onto them, one hm_skeleton_overlay
+  call; ``openpose_radii`` restates the reference's OpenPose thickness arithmetic on the host.
 * ``render_folder``: the ``.npy`` records of a folder job -> one overlay image per frame with hands, a batched MANO forward per
   pass of equally sized frames, PIL encoding on a small thread pool."""
 from __future__ import annotations
@@ -179,6 +181,146 @@ def render_views(H: int, W: int, K, meshes: Sequence[dict], *, frames: Optional[
     return res
 
 
+# ------------------------------------------------------------------------------------------------ hand skeletons (section 8.2)
+# hamer/utils/draw_2d_skeleton.py:9-14 (0..1; its index finger differs from vis_tool's COLOR_HAND_JOINTS)
+COLOR_HAND_JOINTS_HAMER = [[1.0, 0.0, 0.0],
+                           [0.0, 0.4, 0.0], [0.0, 0.6, 0.0], [0.0, 0.8, 0.0], [0.0, 1.0, 0.0],
+                           [0.0, 0.0, 0.4], [0.0, 0.0, 0.6], [0.0, 0.0, 0.8], [0.0, 0.0, 1.0],
+                           [0.0, 0.4, 0.4], [0.0, 0.6, 0.6], [0.0, 0.8, 0.8], [0.0, 1.0, 1.0],
+                           [0.4, 0.4, 0.0], [0.6, 0.6, 0.0], [0.8, 0.8, 0.0], [1.0, 1.0, 0.0],
+                           [0.4, 0.0, 0.4], [0.6, 0.0, 0.6], [0.8, 0.0, 0.8], [1.0, 0.0, 1.0]]
+# hamer/utils/render_openpose.py:105-125 (0..255)
+COLOR_OPENPOSE_HAND = [[100, 100, 100],
+                       [100, 0, 0], [150, 0, 0], [200, 0, 0], [255, 0, 0],
+                       [100, 100, 0], [150, 150, 0], [200, 200, 0], [255, 255, 0],
+                       [0, 100, 50], [0, 150, 75], [0, 200, 100], [0, 255, 125],
+                       [0, 50, 100], [0, 75, 150], [0, 100, 200], [0, 125, 255],
+                       [100, 0, 100], [150, 0, 150], [200, 0, 200], [255, 0, 255]]
+# style -> (order, default line_radius, default joint_radius).  'sar': vis_tool's line width 1 / radius 2 (the host rule of
+# rootnet/Model_RGB.py draw_2d_skeleton); 'hamer': draw_2d_skeleton.py's line_wd 2 / marker_sz 3; 'openpose': openpose_radii
+SKELETON_STYLES = {"sar": (L.HM_SKEL_INTERLEAVED, 0, 2), "hamer": (L.HM_SKEL_INTERLEAVED, 1, 3),
+                   "openpose": (L.HM_SKEL_BONES_FIRST, None, None)}
+
+
+def skeleton_palette(style: str) -> np.ndarray:
+    """(21, 3) uint8: colour j of bone j and joint j, its bytes going to channels 0, 1, 2 of the image as it is stored."""
+    if style == "sar":
+        from .rootnet.Model_RGB import COLOR_HAND_JOINTS
+        return np.round(np.array(COLOR_HAND_JOINTS) * 255).astype(np.uint8)
+    if style == "hamer":
+        return np.round(np.array(COLOR_HAND_JOINTS_HAMER) * 255).astype(np.uint8)
+    if style == "openpose":
+        return np.array(COLOR_OPENPOSE_HAND, np.uint8)
+    raise ValueError(f"style must be one of {sorted(SKELETON_STYLES)}, got {style!r}")
+
+
+def openpose_radii(H: int, W: int, keypoints_host) -> Optional[tuple]:
+    """(line_radius, joint_radius) of one hand drawn as render_hand_keypoints does, or None when it draws nothing.
+    Restates render_keypoints (render_openpose.py:56-71) with thickness_circle_ratio 1/50, line ratio 0.75, pose scale 1 and
+    the rectangle threshold 0.1 -- including its quirk: ``width, height = img.shape[1], img.shape[2]``, so the "height" is
+    the channel count 3 whatever ``H`` is.  keypoints_host (21, 2 | 3): without a confidence column every joint counts.
+    cv2 then draws rings ``circle(radius R, thickness T)`` and lines of thickness T; OUR mapping to the rule's filled
+    primitives is joint_radius = R + T // 2 (the ring's outer edge) and line_radius = T // 2."""
+    kp = np.asarray(keypoints_host)
+    kp = (kp if kp.dtype.kind == "f" else kp.astype(np.float64)).reshape(21, -1)
+    valid = kp[:, 2] > 0.1 if kp.shape[1] >= 3 else np.ones(21, bool)        # compared in the keypoints' own precision
+    if not valid.any():
+        return None
+    xy = kp[valid, :2].astype(np.float64)
+    pw, ph = xy[:, 0].max() - xy[:, 0].min(), xy[:, 1].max() - xy[:, 1].min()
+    if not pw * ph > 0:
+        return None
+    width, height = float(W), 3.0
+    ratio = min(1.0, max(pw / width, ph / height))
+    thickness_ratio = max(np.round(np.sqrt(width * height) * (1.0 / 50) * ratio), 2.0)
+    thickness_circle = max(1.0, thickness_ratio if ratio > 0.05 else -1.0)
+    thickness_line = max(1.0, np.round(thickness_ratio * 0.75))
+    R, Tc, Tl = int(round(thickness_ratio / 2)), int(round(thickness_circle)), int(round(thickness_line))
+    return Tl // 2, R + Tc // 2
+
+
+def _per_hand(value, default, n: int, what: str) -> List[int]:
+    if value is None:
+        value = default
+    if value is None:
+        raise ValueError(f"style 'openpose' takes its {what} from openpose_radii(H, W, keypoints on the host): pass {what} "
+                         "(one int or one per hand), or host keypoints")
+    v = [int(value)] * n if np.ndim(value) == 0 else [int(x) for x in value]
+    if len(v) != n:
+        raise ValueError(f"{what}: {len(v)} values for {n} hands")
+    if any(not 0 <= x <= 32 for x in v):
+        raise ValueError(f"{what} must be in 0..32, got {value}")
+    return v
+
+
+def skeleton_frames(images_dev: torch.Tensor, keypoints, image_index: Sequence[int], style: str = "hamer", line_radius=None,
+                    joint_radius=None, threshold: float = 0.1, out: Optional[torch.Tensor] = None,
+                    inplace: bool = False) -> torch.Tensor:
+    """Draw hand skeletons (hm_skeleton_overlay; the rule is in include/hamer_hip.h and DESIGN.md section 8.2).  images_dev
+    (N,H,W,3) uint8 on the GPU; keypoints (n,21,2) pixels or (n,21,3) with a confidence (a joint is drawn if conf >
+    ``threshold``), a device tensor (never read back) or a host array; image_index: per hand the image it is drawn into, in
+    drawing order (a later hand goes over an earlier one).  Non-finite or out-of-range joints are left out with their bones.
+    style: 'sar' (vis_tool's colours), 'hamer' (draw_2d_skeleton.py's), 'openpose' (render_openpose.py's, bones first);
+    colours go to channels 0, 1, 2 as the image stores them.  line_radius / joint_radius: one int or one per hand, default by
+    style; for 'openpose' the default is ``openpose_radii`` per hand, which needs HOST keypoints (hands it would not draw are
+    left out).  Returns a new tensor, or ``out``, or with ``inplace`` images_dev itself (only the hands' boxes are touched).
+    One call, enqueued on the current stream, no synchronisation."""
+    if style not in SKELETON_STYLES:
+        raise ValueError(f"style must be one of {sorted(SKELETON_STYLES)}, got {style!r}")
+    if not (torch.is_tensor(images_dev) and images_dev.is_cuda and images_dev.dtype == torch.uint8 and images_dev.dim() == 4
+            and images_dev.shape[3] == 3):
+        raise ValueError("images_dev must be a (N,H,W,3) uint8 GPU tensor")
+    if inplace and not images_dev.is_contiguous():
+        raise ValueError("inplace needs contiguous images")
+    if inplace and out is not None:
+        raise ValueError("give out or inplace, not both")
+    images_dev = images_dev.contiguous()
+    dev = images_dev.device
+    N, H, W, _ = images_dev.shape
+    order, d_line, d_joint = SKELETON_STYLES[style]
+    image_index = [int(i) for i in image_index]
+    n = len(image_index)
+    host_kp = None if torch.is_tensor(keypoints) and keypoints.is_cuda else np.asarray(
+        keypoints.cpu() if torch.is_tensor(keypoints) else keypoints, np.float32)
+    if style == "openpose" and host_kp is not None and n and (line_radius is None or joint_radius is None):
+        radii = [openpose_radii(H, W, k) for k in host_kp.reshape(n, 21, -1)]
+        keep = [i for i, r in enumerate(radii) if r is not None]
+        if line_radius is None:
+            line_radius = [radii[i][0] for i in keep]
+        elif np.ndim(line_radius):
+            line_radius = [line_radius[i] for i in keep]
+        if joint_radius is None:
+            joint_radius = [radii[i][1] for i in keep]
+        elif np.ndim(joint_radius):
+            joint_radius = [joint_radius[i] for i in keep]
+        host_kp, image_index, n = host_kp.reshape(n, 21, -1)[keep], [image_index[i] for i in keep], len(keep)
+    kd = (torch.from_numpy(np.ascontiguousarray(host_kp)).to(dev) if host_kp is not None else keypoints.to(dev)).to(torch.float32)
+    if n and (kd.dim() != 3 or kd.shape[0] != n or kd.shape[1] != 21 or kd.shape[2] not in (2, 3)):
+        raise ValueError(f"keypoints must be ({n},21,2) or ({n},21,3), got {tuple(kd.shape)}")
+    kd = kd.contiguous()
+    lr, jr = _per_hand(line_radius, d_line, n, "line_radius"), _per_hand(joint_radius, d_joint, n, "joint_radius")
+    table = (L.Skeleton * max(n, 1))()
+    for i in range(n):
+        if not 0 <= image_index[i] < N:
+            raise ValueError(f"hand {i}: image {image_index[i]} outside the batch of {N}")
+        table[i].image, table[i].line_radius, table[i].joint_radius, table[i].threshold = image_index[i], lr[i], jr[i], float(threshold)
+    if inplace:
+        out = images_dev
+    elif out is None:
+        out = torch.empty_like(images_dev)
+    elif not (out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == tuple(images_dev.shape) and out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape {tuple(images_dev.shape)} on {dev}")
+    pal = np.ascontiguousarray(skeleton_palette(style))
+    lib = L.load()
+    need = lib.hm_skeleton_overlay_workspace_bytes(N, H, W, n)
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=dev)      # the call zeroes what it reads; freed in stream order
+        L.check(lib.hm_skeleton_overlay(L.ptr(images_dev), N, H, W, L.ptr(kd) if n else None, int(kd.shape[2]) if n else 2,
+                                        table, n, pal.ctypes.data_as(C.POINTER(C.c_uint8)), order, L.ptr(out), L.ptr(ws),
+                                        ws.numel(), L.current_stream()), "hm_skeleton_overlay")
+    return out
+
+
 def default_camera(H: int, W: int, cfg) -> np.ndarray:
     """The camera the records were made with when no intrinsics are given (infer.py _estimate, no-intrinsics branch):
     fx = fy = EXTRA.FOCAL_LENGTH / MODEL.IMAGE_SIZE * max(H, W), principal point at the frame centre."""
@@ -195,6 +337,32 @@ def camera_vertices(hamer, hands: List[dict]) -> torch.Tensor:
     sign = torch.tensor([[1.0, 1.0, 1.0] if h["is_right"] else [-1.0, 1.0, 1.0] for h in hands], device=dev)
     cam_t = torch.tensor(np.stack([np.asarray(h["cam_t"], np.float32).reshape(3) for h in hands]), device=dev)
     return verts * sign[:, None, :] + cam_t[:, None, :]
+
+
+def camera_joints_vertices(hamer, hands: List[dict]):
+    """``camera_vertices`` with the 21 MANO joints placed the same way: (joints (B, 21, 3), vertices (B, V, 3)) fp32 in the
+    camera frame, from one MANO forward."""
+    from .infer import mano_hand_joints_vertices
+    dev = hamer.device
+    joints, verts = mano_hand_joints_vertices(hamer, hands)
+    sign = torch.tensor([[1.0, 1.0, 1.0] if h["is_right"] else [-1.0, 1.0, 1.0] for h in hands], device=dev)
+    cam_t = torch.tensor(np.stack([np.asarray(h["cam_t"], np.float32).reshape(3) for h in hands]), device=dev)
+    return joints * sign[:, None, :] + cam_t[:, None, :], verts * sign[:, None, :] + cam_t[:, None, :]
+
+
+def project_points(points: torch.Tensor, K) -> torch.Tensor:
+    """Camera-frame points (..., 3) on the device -> pixels (..., 2) fp32 by section 8's rule, in fp64 with plain torch ops
+    (one rounding each, left to right): z == 0 -> 1e-5, w = K20*x + K21*y + K22*z, u = (K00*x + K01*y + K02*z) / w,
+    v = (K10*x + K11*y + K12*z) / w, rounded once to fp32.  Points with z <= 0 become NaN (the skeleton rule leaves them out)."""
+    k = np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float64)
+    p = points.to(torch.float64)
+    x, y, z0 = p[..., 0], p[..., 1], p[..., 2]
+    z = torch.where(z0 == 0.0, torch.full_like(z0, 1e-5), z0)
+    w = float(k[2, 0]) * x + float(k[2, 1]) * y + float(k[2, 2]) * z
+    u = (float(k[0, 0]) * x + float(k[0, 1]) * y + float(k[0, 2]) * z) / w
+    v = (float(k[1, 0]) * x + float(k[1, 1]) * y + float(k[1, 2]) * z) / w
+    uv = torch.stack([u, v], dim=-1)
+    return torch.where((z0 > 0.0)[..., None], uv, torch.full_like(uv, float("nan"))).to(torch.float32)
 
 
 def _encode_threads() -> int:
@@ -266,7 +434,8 @@ def decode_pass(pool, paths: Sequence[str], hw: tuple):
 
 
 def render_folder(image_folder, npy_folder, out_folder, hamer, k_real=None, style: str = "flat", rank: int = 0, world: int = 1,
-                  ext: str = ".jpg", frames_per_pass: int = FRAMES_PER_PASS) -> int:
+                  ext: str = ".jpg", frames_per_pass: int = FRAMES_PER_PASS, keypoints: Optional[str] = None,
+                  keypoint_style: str = "hamer", line_radius=None, joint_radius=None) -> int:
     """Draw the hands of every ``<name>.npy`` record of ``npy_folder`` onto ``image_folder``'s ``<name>.*`` frame and write
     ``out_folder/<name><ext>`` (``.jpg`` as the reference; any extension PIL writes).  Frames are grouped by the size their
     headers give and drawn in passes of ``frames_per_pass``: per pass the frames are decoded, ONE MANO forward runs for all its
@@ -274,7 +443,14 @@ def render_folder(image_folder, npy_folder, out_folder, hamer, k_real=None, styl
     ``overlay_frames``; "smooth": the z-buffered ``render_views``), one copy back, and the encodes go to
     a ``PassWriter`` -- host memory stays bounded by a few passes whatever the folder's length.  ``k_real`` None: the camera
     the records were made with (``default_camera``).  ``rank`` / ``world``: this process draws ``shard_paths(records, rank,
-    world)``.  Returns the number of images written; the overlay workspaces are released at the end."""
+    world)``.  ``keypoints``: None, or 'over' / 'only' to draw the hands' 21 MANO joints as skeletons (``skeleton_frames``,
+    ``keypoint_style`` and radii as there) over the mesh overlay / onto the decoded frames instead of it: the joints of the
+    pass's MANO forward, mirrored and translated like the vertices, projected on the device (``project_points``), one call in
+    place.  Returns the number of images written; the overlay workspaces are released at the end."""
+    if keypoints not in (None, "over", "only"):
+        raise ValueError(f"keypoints must be None, 'over' or 'only', got {keypoints!r}")
+    if keypoints and keypoint_style not in SKELETON_STYLES:
+        raise ValueError(f"keypoint_style must be one of {sorted(SKELETON_STYLES)}, got {keypoint_style!r}")
     os.makedirs(out_folder, exist_ok=True)
     jobs = _record_jobs(image_folder, npy_folder, rank, world, keep_empty=False)
     dev = hamer.device
@@ -292,13 +468,24 @@ def render_folder(image_folder, npy_folder, out_folder, hamer, k_real=None, styl
                 part = [part[k] for k in ok]
                 K = np.asarray(k_real, np.float64) if k_real is not None else default_camera(H, W, hamer.cfg)
                 hands = [(n, h) for n, i in enumerate(part) for h in jobs[i][2]]
-                verts = camera_vertices(hamer, [h for _, h in hands])
+                if keypoints:
+                    joints, verts = camera_joints_vertices(hamer, [h for _, h in hands])
+                else:
+                    verts = camera_vertices(hamer, [h for _, h in hands])
                 meshes = [{"frame": n, "vertices": verts[j], "faces": faces, "is_right": bool(h["is_right"])}
                           for j, (n, h) in enumerate(hands)]
-                if style == "smooth":
+                if keypoints == "only":
+                    out = torch.from_numpy(batch).to(dev)
+                elif style == "smooth":
                     out = render_views(H, W, K, meshes, frames=torch.from_numpy(batch).to(dev), outputs=())["out"]
                 else:
                     out = overlay_frames(torch.from_numpy(batch).to(dev), K, meshes, style=style)
+                if keypoints:
+                    kp = project_points(joints, K)
+                    if keypoint_style == "openpose" and (line_radius is None or joint_radius is None):
+                        kp = kp.cpu().numpy()                          # the OpenPose thickness is host arithmetic on the keypoints
+                    skeleton_frames(out, kp, [n for n, _ in hands], style=keypoint_style, line_radius=line_radius,
+                                    joint_radius=joint_radius, inplace=True)
                 res = out.cpu().numpy()
                 writer.submit([(os.path.join(out_folder, jobs[i][0] + ext), res[n]) for n, i in enumerate(part)])
             return writer.close()

@@ -307,22 +307,36 @@ class EstimateRGB:
         return (inv_trans @ uv1.transpose(-1, -2)).transpose(-1, -2)
 
     @torch.no_grad()
-    def run_frames(self, frames, K, dets_lists):
+    def run_frames(self, frames, K, dets_lists, draw=False):
         """run() for ALL hands of several device-resident frames ((H, W, 3) uint8 BGR tensors): one backbone pass, one head,
         one RootNet and one post-process launch.  dets_lists: per frame [[hand_type, [x1, y1, x2, y2]], ...] (every box must
         have a patch: filter with valid_boxes).  K: 3x3 camera.  Returns {pose_uvd (n, 21, 3), mesh_uvd (n, 778, 3),
-        pose_xyz, mesh_xyz} fp32 device tensors, hands in dets_lists order; the same numbers as run() hand by hand (no
-        images are drawn)."""
+        pose_xyz, mesh_xyz} fp32 device tensors, hands in dets_lists order; the same numbers as run() hand by hand.
+        draw=True adds run()'s two images per hand, made on the device: crop_img_rgb (n, P, P, 3) uint8, the patch by
+        _crop_u8's arithmetic, and pose_img_rgb, the patch with the skeleton drawn by hm_skeleton_overlay at
+        (coords[:, NV:, :2] + 0.5) * P (render.skeleton_frames, style 'sar': the bytes of draw_2d_skeleton)."""
+        P = int(self.cfg.input_img_shape[0])
         hands = []
         for fi, (fr, dets) in enumerate(zip(frames, dets_lists)):
             for label, box in dets:
                 hands.append((fi, self._processed_box(box, int(fr.shape[1]), int(fr.shape[0])), label == "left", -1))
         if not hands:
             e = torch.empty(0, 21, 3, device=self.device)
-            return {'pose_uvd': e, 'mesh_uvd': torch.empty(0, NV, 3, device=self.device), 'pose_xyz': e.clone(),
-                    'mesh_xyz': torch.empty(0, NV, 3, device=self.device)}
-        uvd, xyz = self._sar_batch(frames, hands, K)[:2]
-        return {'pose_uvd': uvd[:, NV:], 'mesh_uvd': uvd[:, :NV], 'pose_xyz': xyz[:, NV:], 'mesh_xyz': xyz[:, :NV]}
+            res = {'pose_uvd': e, 'mesh_uvd': torch.empty(0, NV, 3, device=self.device), 'pose_xyz': e.clone(),
+                   'mesh_xyz': torch.empty(0, NV, 3, device=self.device)}
+            if draw:
+                res['crop_img_rgb'] = torch.empty(0, P, P, 3, dtype=torch.uint8, device=self.device)
+                res['pose_img_rgb'] = res['crop_img_rgb'].clone()
+            return res
+        uvd, xyz, raw, _, coords = self._sar_batch(frames, hands, K)
+        res = {'pose_uvd': uvd[:, NV:], 'mesh_uvd': uvd[:, :NV], 'pose_xyz': xyz[:, NV:], 'mesh_xyz': xyz[:, :NV]}
+        if draw:
+            from ..render import skeleton_frames
+            crop = raw.flip(1).permute(0, 2, 3, 1).round().clamp(0, 255).to(torch.uint8).contiguous()     # _crop_u8, batched
+            pose_crop_uv = (coords[:, NV:, :2].to(torch.float32) + 0.5) * float(P)                       # coord_uvd_crop (:438)
+            res['crop_img_rgb'] = crop
+            res['pose_img_rgb'] = skeleton_frames(crop, pose_crop_uv, range(len(hands)), style='sar')
+        return res
 
 
 def get_model():

@@ -572,6 +572,47 @@ int hm_mesh_render(int N, int H, int W, const double* K_host, const double* vert
                    double znear, const uint8_t* frames, uint8_t* out, uint8_t* rgba, float* depth, int32_t* mesh_id,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* Hand skeletons (rootnet/vis_tool.py draw_2d_skeleton, :602-640; hamer/utils/draw_2d_skeleton.py; hamer/utils/render_openpose.py
+ * render_keypoints, :56-91): the 20 bones and 21 joint discs of every hand drawn opaquely onto its image.
+ * The drawing rule, bit-exact (tests/skeleton_rule.py restates it in numpy as a sequential painter); it generalises
+ * rootnet/Model_RGB.py draw_2d_skeleton, which it equals at line_radius 0, joint_radius 2:
+ *  - joints: joint j of a hand is the point p_j = (trunc(u), trunc(v)), truncated toward zero to int32.  A joint is ABSENT if u
+ *    or v is not finite, if |u| or |v| >= 32768, or, with kp_stride 3, if `conf > threshold` is false (render_openpose.py:76,85).
+ *    An absent joint draws no disc, and no bone that touches it is drawn (a deviation: the host rule is undefined for
+ *    non-finite and out-of-range inputs);
+ *  - bone j (j = 1..20) runs a -> b with a = p_parent(j), b = p_j, parent(j) = 0 if j % 4 == 1 else j - 1.  dx = bx - ax,
+ *    dy = by - ay, m = max(|dx|, |dy|).  Its samples are s_i = (rint(ax + t_i*dx), rint(ay + t_i*dy)), i = 0..m, with
+ *    t_i = i * (1.0 / m) for i < m and t_m = 1.0 (m = 0: the one sample a), all in fp64 without contraction, rint half-to-even
+ *    (numpy's linspace(0, 1, m + 1), then np.rint).  The bone covers pixel (x, y) iff some sample has
+ *    (x - sx)^2 + (y - sy)^2 <= line_radius^2;
+ *  - disc j covers (x, y) iff (x - px)^2 + (y - py)^2 <= joint_radius^2.  Radii are integers in 0..32;
+ *  - order, per hand: HM_SKEL_INTERLEAVED: for j = 0..20 bone j (j > 0), then disc j; HM_SKEL_BONES_FIRST
+ *    (render_keypoints:74-91): bones 1..20, then discs 0..20.  Bone j and disc j have colour palette[j].  Hands are drawn in
+ *    table order, a later hand over an earlier one: a pixel gets the colour of the covering primitive with the largest
+ *    (hand index, draw index), opaque, its three bytes to channels 0, 1, 2 as the image stores them; uncovered pixels keep
+ *    their bytes.  The result does not depend on scheduling.
+ * cv2.line / cv2.circle pixels and the reference's LINE_AA are not reproduced: the bytes are exact to this rule, unpinned
+ * against cv2. */
+enum { HM_SKEL_INTERLEAVED = 0, HM_SKEL_BONES_FIRST = 1 };
+typedef struct hm_skeleton {
+  int32_t image;                      /* image of the batch the hand is drawn into; its keypoints are row i of kp    */
+  int32_t line_radius, joint_radius;  /* 0..32                                                                       */
+  float threshold;                    /* kp_stride 3: a joint is drawn if conf > threshold                           */
+} hm_skeleton;
+/* 0 when n_hands <= 0 (no workspace is needed then) or the sizes are invalid. */
+size_t hm_skeleton_overlay_workspace_bytes(int N, int H, int W, int n_hands);
+/* images [N][H][W][3] u8 (device), kp [n_hands][21][kp_stride] f32 (device, never read back; kp_stride 2: u v, 3: u v conf),
+ * hands_host [n_hands] and palette_host [21][3] u8 (HOST, read before return), out [N][H][W][3] u8 (device): out == images is
+ * the in-place form, which touches only 16 x 16 tiles inside some hand's box; otherwise out must not overlap images and gets
+ * one device-to-device copy first.  One memset of the workspace's counters, a setup launch per 128 hands and one raster launch;
+ * no host synchronisation.  n_hands == 0 is valid (the copy alone; kp, the tables and the workspace may be NULL).  HM_ERR_ARG
+ * before any device work: N, H or W <= 0, H or W > 16384, kp_stride not 2 or 3, an unknown order, a radius outside 0..32, an
+ * image outside 0..N-1, a null pointer with n_hands > 0 (images and out always), out partly overlapping images, a workspace
+ * smaller than hm_skeleton_overlay_workspace_bytes.  Alignment: kp 4 bytes, workspace 8 bytes. */
+int hm_skeleton_overlay(const uint8_t* images, int N, int H, int W, const float* kp, int kp_stride,
+                        const hm_skeleton* hands_host, int n_hands, const uint8_t* palette_host, int order, uint8_t* out,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- SAR hand-mesh head of the RootNet checkpoint (rootnet/Model_RGB.py:76-177 SoftHeatmap / GraphConv / SAIGB / GBBMR,
  * :198-222 SARhead, :428-480 post_processing, :500-570 EstimateRGB.run).  f16 operands, fp32 accumulation; activations are
  * node-major across the batch, [778][B][C].  No split-K and no batch-dependent reduction order: a hand's numbers are the

@@ -8,6 +8,12 @@
                                                      `rocprofv3 --kernel-trace --stats -- python tools/bench_render.py device`
                                                      for the per-kernel device time (overlay_setup / raster / compose,
                                                      zrender_normals / setup / raster / resolve).
+  python tools/bench_render.py device --skeleton [--iters 20]
+                                                     64 synthetic 1080p frames x 4 hand skeletons (style 'hamer') through
+                                                     hm_skeleton_overlay: the device time (the library's
+                                                     own events around its launches, median) of the in-place and of the copying
+                                                     form, next to hm_mesh_overlay's compose pass alone (a call without meshes)
+                                                     and a device-to-device copy of the same frames, all from this run.
   python tools/bench_render.py folder [--frames 64] [--style flat|shaded|smooth] [--hand-maps]
                                                      render_folder (or hand_maps_folder) on a folder of synthetic 1080p .jpg
                                                      frames with 2 hands each (records made from seeded MANO parameters,
@@ -96,6 +102,47 @@ def device(iters, topology, renderer="overlay"):
     print(json.dumps(res))
 
 
+def _library_ms(fn, iters):
+    """Median device time of the library call(s) inside fn: the events the library records around its own launches."""
+    from hamer_yolo_amd import lib as L
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    with L.profile() as p:
+        for _ in range(iters):
+            fn()
+    return round(float(np.median([r[5] for r in p.records])), 4)
+
+
+def skeleton(iters):
+    N, per_frame = 64, 4
+    frames = torch.stack([synth.frame_u8(H, W, seed=n) for n in range(N)]).cuda()
+    rng = np.random.default_rng(0)
+    kp = np.empty((N * per_frame, 21, 2), np.float32)
+    for i in range(N * per_frame):                              # a hand about 250 px across, anywhere in the frame
+        cx, cy = rng.uniform(0.1, 0.9) * W, rng.uniform(0.1, 0.9) * H
+        kp[i] = rng.uniform([cx - 125, cy - 125], [cx + 125, cy + 125], (21, 2))
+    kpd = torch.from_numpy(kp).cuda()
+    index = [i // per_frame for i in range(N * per_frame)]
+    out, work = torch.empty_like(frames), frames.clone()
+    K = np.array([[1000.0, 0, W / 2], [0, 1000.0, H / 2], [0, 0, 1]])
+    res = {"mode": "device", "what": "skeleton", "style": "hamer", "frames": N, "hands": len(index),
+           "frame_bytes": N * H * W * 3, "iters": iters,
+           "skeleton_in_place_ms": _library_ms(lambda: render.skeleton_frames(work, kpd, index, inplace=True), iters),
+           "skeleton_copying_ms": _library_ms(lambda: render.skeleton_frames(frames, kpd, index, out=out), iters),
+           "mesh_overlay_compose_only_ms": _library_ms(lambda: render.overlay_frames(frames, K, [], out=out), iters)}
+    times = []
+    for _ in range(iters + 3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); out.copy_(frames); e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1))
+    res["device_to_device_copy_ms"] = round(float(np.median(times[3:])), 4)
+    touched = (work != frames).any(-1).sum().item()
+    res["pixels_drawn_fraction"] = round(touched / (N * H * W), 5)
+    print(json.dumps(res))
+
+
 class _Cfg:
     ckpt_path = "synthetic:0"
     model_cfg = None
@@ -141,5 +188,9 @@ if __name__ == "__main__":
     ap.add_argument("--renderer", choices=["overlay", "zbuffer", "both"], default="overlay")
     ap.add_argument("--style", choices=["flat", "shaded", "smooth"], default="flat")
     ap.add_argument("--hand-maps", action="store_true")
+    ap.add_argument("--skeleton", action="store_true", help="device mode: measure hm_skeleton_overlay instead of the mesh renderers")
     a = ap.parse_args()
-    device(a.iters, a.topology, a.renderer) if a.mode == "device" else folder(a.frames, a.style, a.hand_maps)
+    if a.mode == "device" and a.skeleton:
+        skeleton(a.iters)
+    else:
+        device(a.iters, a.topology, a.renderer) if a.mode == "device" else folder(a.frames, a.style, a.hand_maps)
