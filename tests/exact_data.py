@@ -8,6 +8,11 @@ kernel that reads the wrong element along that axis pass.  So every operand here
 tests/test_exact_data_host.py applies a catalogue of index faults to the operands of the torch reference, at every shape
 listed below, and requires each fault to change more than half of the outputs.
 
+The LayerNorm kernels get the same treatment with other data (section "LayerNorm" below): rows whose mean is a small integer,
+whose centred values are +-0.5 and whose rstd is exactly 1, so that y = sigma * gamma / 2 + beta is exact in fp32, bf16 and fp16
+and the MXFP8 bytes and scales are those of the oracle quantiser; and a set of hostile rows with a per-row error bound for the
+accuracy test.
+
 Plain helper module (imported like sar_rule.py); torch-CPU only, nothing here touches the compiled library.
 """
 import torch
@@ -100,7 +105,161 @@ def fp8_reference(xi, xs, wi, ws):
     return xd @ (wi.double() * ws.double()[:, None]).t()
 
 
+# ------------------------------------------------------------------------------------------------ LayerNorm
+# Rows whose LayerNorm is exact in fp32 whatever the order of the two reductions.  x[r, c] = m_r + sigma(r, c) / 2 with a small
+# hashed integer m_r and a hashed sign sigma whose second half-row is the negation of the first: every partial sum of the row is
+# a small multiple of 0.5, the row sum is D * m_r and the mean m_r; every centred value is +-0.5, the variance 0.25, and with
+# eps = 0.75 rstd = 1 / sqrt(1) = 1.  So y = sigma * gamma / 2 + beta, exact for small dyadic gamma and beta.
+LN_EPS = 0.75
+# Goes into every seed.  The smallest cases hold a handful of hashed values (3 x 4: six free signs, 1 x 64: two scale bytes) and
+# can come out degenerate by chance; tests/test_exact_data_host.py demands its fault fractions at every shape, and this is the
+# first salt under which all of them hold.
+LN_SALT = 6
+LN_PEAK_GAMMA, LN_PEAK_BETA = 15, 8      # |y| of a peak column is 15.5 or 0.5 by the row's sign; elsewhere |y| <= (7 + 6) / 2 = 6.5
+
+
+def _ln_params(D, sd):
+    """gamma (odd integer with a sign, 1..7) and beta (integer, -3..3), both times 2^-3..2^3 per 32-column block.  One hashed
+    column of every block is a peak, gamma = +-15 and beta = +-8: the block's largest |y| is 15.5 * 2^k in the rows where
+    sigma * gamma and beta agree in sign and at most 6.5 * 2^k in the others, so the E8M0 byte of the block (the exponent of
+    amax / 448, rounded up: 15.5 and 6.5 lie on two sides of 14 = 448 / 32) depends on the row as well as on the block."""
+    nblk = (D + 31) // 32
+    blk = torch.arange(D, dtype=torch.int64) // 32
+    g = (2 * ints("exact.ln.gamma", (D,), 0, 3, sd) + 1) * (2 * ints("exact.ln.gsign", (D,), 0, 1, sd) - 1)
+    b = ints("exact.ln.beta", (D,), -3, 3, sd)
+    width = torch.clamp(D - 32 * torch.arange(nblk, dtype=torch.int64), max=32)
+    peak = 32 * torch.arange(nblk, dtype=torch.int64) + ints("exact.ln.peak", (nblk,), 0, 31, sd).long() % width
+    g[peak] = LN_PEAK_GAMMA * (2 * ints("exact.ln.pgsign", (nblk,), 0, 1, sd) - 1)
+    b[peak] = LN_PEAK_BETA * (2 * ints("exact.ln.pbsign", (nblk,), 0, 1, sd) - 1)
+    scale = torch.ldexp(torch.ones(nblk), ints("exact.ln.pow", (nblk,), -3, 3, sd).to(torch.int32))[blk]
+    return g * scale, b * scale
+
+
+def ln_emulate(x, gamma, beta, eps):
+    """The kernels' arithmetic in torch fp32: two-pass mean and variance (fp32 sums), 1 / sqrt(var + eps), one multiply-add chain."""
+    x = x.float()
+    D = x.shape[1]
+    mean = x.sum(1, keepdim=True) / D
+    d = x - mean
+    rstd = 1.0 / torch.sqrt((d * d).sum(1, keepdim=True) / D + eps)
+    return d * rstd * gamma.float() + beta.float(), mean, rstd
+
+
+def ln_reference(x, gamma, beta, eps):
+    """Plain LayerNorm over the last dimension in fp64."""
+    x = x.double()
+    mean = x.mean(1, keepdim=True)
+    d = x - mean
+    return d / torch.sqrt((d * d).mean(1, keepdim=True) + eps) * gamma.double() + beta.double()
+
+
+def ln_case(M, D):
+    """x (M, D), gamma (D,), beta (D,) fp32 and y (M, D) fp64, the closed form sigma * gamma / 2 + beta of LayerNorm(x) at
+    eps = LN_EPS.  Asserts what makes y the exact answer of an fp32 kernel: balanced rows, mean m_r and rstd 1 bit for bit
+    under ln_emulate, the emulation and the fp64 LayerNorm equal to the closed form, y unchanged by bf16 and fp16."""
+    assert D % 4 == 0 and D >= 4
+    sd = _shape_seed(M, D, LN_SALT)
+    m = ints("exact.ln.mean", (M, 1), -6, 6, sd)
+    h = 2 * ints("exact.ln.sigma", (M, D // 2), 0, 1, sd) - 1
+    sigma = torch.cat([h, -h], 1)
+    x = m + 0.5 * sigma
+    gamma, beta = _ln_params(D, sd)
+    y = sigma.double() * (gamma.double() / 2) + beta.double()
+    assert torch.equal(x.sum(1, keepdim=True), D * m) and torch.equal(x.double().sum(1, keepdim=True), D * m.double())
+    emu, mean, rstd = ln_emulate(x, gamma, beta, LN_EPS)
+    assert torch.equal(mean, m) and torch.equal(rstd, torch.ones(M, 1)), (M, D)
+    assert torch.equal(emu.double(), y) and torch.equal(ln_reference(x, gamma, beta, LN_EPS), y), (M, D)
+    yf = y.float()
+    assert torch.equal(yf.to(torch.bfloat16).double(), y) and torch.equal(yf.to(torch.float16).double(), y), (M, D)
+    return x, gamma, beta, y
+
+
+def ln_accum_case(M, D, S, bias=True):
+    """Operands of hm_layernorm_accum whose sum is ln_case(M, D)'s x: x0 (M, D), parts (S, M, D) and bias (D,) or None, all
+    hashed multiples of 0.5 (so every partial sum is exact in fp32), the last slab carrying the remainder.
+    Returns x0, parts, bias, x, gamma, beta, y."""
+    x, gamma, beta, y = ln_case(M, D)
+    sd = _shape_seed(M, D, S)
+    x0 = ints("exact.lnacc.x0", (M, D), -8, 8, sd) / 2
+    b = ints("exact.lnacc.bias", (D,), -6, 6, sd) / 2 if bias else None
+    parts = ints("exact.lnacc.part", (S, M, D), -8, 8, sd) / 2
+    parts[S - 1] = x - x0 - parts[:S - 1].sum(0) - (b if bias else 0.0)
+    total = x0.double() + parts.double().sum(0) + (b.double() if bias else 0.0)
+    assert torch.equal(total, x.double()) and torch.equal(parts * 2, (parts * 2).round())
+    assert (float(x0.abs().max()) + float(parts.abs().sum(0).max()) + _amax(b)) * 2 < EXACT_LIMIT
+    return x0, parts, b, x, gamma, beta, y
+
+
+# Rows for the accuracy test of the LayerNorm kernels against fp64: ordinary ones and the ones a careless kernel gets wrong.
+LN_HOSTILE_KINDS = ("uniform", "mean_1000", "mean_-3000", "var_eps", "var_1e-3_eps", "outlier", "zero")
+LN_ROWS_PER_KIND = 6
+# Largest error of ln_emulate against fp64 per kind of row, in units of ln_error_unit, over D in LN_HOSTILE_D and both eps
+# (measured by tests/test_exact_data_host.py::test_ln_error_multiples_are_the_measured_ones, which fails if one is exceeded or
+# is more than twice what is measured); a kernel gets LN_KERNEL_MARGIN times that, because its reduction order differs.
+LN_HOSTILE_D = [96, 320, 1280, 2048]
+LN_HOSTILE_EPS = [1e-6, 1e-5]
+LN_MULTIPLES = {"uniform": 1.6, "mean_1000": 1.0, "mean_-3000": 0.9, "var_eps": 1.7, "var_1e-3_eps": 2.3, "outlier": 1.9, "zero": 0.0}
+LN_KERNEL_MARGIN = 4.0
+
+
+def ln_hostile_rows(D, eps):
+    """x (7 * LN_ROWS_PER_KIND, D), gamma, beta, kind index per row.  |x| <= 1e4: overflow of the squares is out of scope."""
+    R = LN_ROWS_PER_KIND
+    u = lambda tag, hw, center=0.0: synth.uniform("ln.hostile." + tag, (R, D), hw, center, seed=D)      # noqa: E731
+    outlier = u("outlier", 3.0 ** 0.5)
+    outlier[torch.arange(R), ints("ln.hostile.at", (R,), 0, D - 1, D).long()] = 1e4
+    rows = [u("uniform", 3.0, 0.5), u("mean1000", 3.0 ** 0.5, 1000.0), u("mean-3000", 0.1 * 3.0 ** 0.5, -3000.0),
+            u("vareps", (3.0 * eps) ** 0.5), u("var1e-3eps", (3.0e-3 * eps) ** 0.5), outlier, torch.zeros(R, D)]
+    kind = torch.arange(len(rows)).repeat_interleave(R)
+    gamma = synth.uniform("ln.hostile.gamma", (D,), 0.1, 1.0, seed=1)
+    beta = synth.uniform("ln.hostile.beta", (D,), 0.1, 0.0, seed=2)
+    return torch.cat(rows, 0), gamma, beta, kind
+
+
+def ln_error_unit(x, gamma, eps):
+    """(rows, 1) fp64: 2^-23 * (max|x - mean| / sqrt(var + eps) * max|gamma| + |mean| / sqrt(var + eps)), the size of one fp32
+    rounding of the largest normalised value plus the share of one rounding of the mean."""
+    x = x.double()
+    mean = x.mean(1, keepdim=True)
+    d = x - mean
+    sd = torch.sqrt((d * d).mean(1, keepdim=True) + eps)
+    return 2.0 ** -23 * (d.abs().amax(1, keepdim=True) / sd * float(gamma.abs().max()) + mean.abs() / sd)
+
+
+def ln_error_bound(x, gamma, eps, kind, margin=LN_KERNEL_MARGIN):
+    """(rows, 1) fp64 bound on |kernel - fp64| for fp32 output: margin * LN_MULTIPLES[kind of the row] * ln_error_unit."""
+    mult = torch.tensor([LN_MULTIPLES[k] for k in LN_HOSTILE_KINDS], dtype=torch.float64)[kind][:, None]
+    return margin * mult * ln_error_unit(x, gamma, eps)
+
+
+def ulp16(ref, dtype):
+    """One step of the 16-bit format at |ref|, from above: 2^-8 |ref| for bf16 (8 significant bits), 2^-11 |ref| for fp16 and
+    never less than 2^-24, the spacing of fp16's subnormals."""
+    return ref.abs() * 2.0 ** -8 if dtype == torch.bfloat16 else torch.clamp(ref.abs() * 2.0 ** -11, min=2.0 ** -24)
+
+
 # ------------------------------------------------------------------------------------------------ the shapes of the GPU tests
+# hm_layernorm: every D selects one width class of the row kernel on its unpaired or its paired ("full", D = MAXJ * 256) store
+# path; the small M run one row per wave, the large ones 2, 3 and 3 (ln_large_m: 16 CUs + 1, 32 CUs + 5 ragged, 48 CUs whole)
+LN_D = [4, 96, 252, 256, 260, 320, 512, 516, 768, 1024, 1028, 1276, 1280, 1284, 1536, 2044, 2048]
+LN_M = [1, 3, 5, 197]
+LN_LARGE_M_D = [96, 256, 512, 1280, 2048]
+LN_HOST_CUS = 256                        # the CU count the host catalogue builds the large M with
+LN_ACCUM_D = [4, 320, 512, 1280, 1284, 2048]
+LN_ACCUM_M = [1, 5, 197]
+LN_ACCUM_S = [1, 4, 5, 10]
+LN_MX8_D = [32, 64, 256, 288, 512, 544, 1280, 1312, 1536, 2048]
+LN_MX8_M = [1, 5, 197, 520]
+
+
+def ln_large_m(cus):
+    return [16 * cus + 1, 32 * cus + 5, 48 * cus]
+
+
+def ln_shapes(cus=LN_HOST_CUS):
+    return [(M, D) for D in LN_D for M in LN_M] + [(M, D) for D in LN_LARGE_M_D for M in ln_large_m(cus)]
+
+
 # hm_gemm, (M, N, K)
 GEMM_ASYMMETRIC = [(192, 256, 128)]
 GEMM_TILE_VARIANTS = [(300, 260, 64), (513, 388, 128), (1000, 1284, 448), (700, 516, 192), (257, 260, 1280)]

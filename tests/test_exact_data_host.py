@@ -6,6 +6,11 @@ REFERENCE and the reference recomputed.  A fault must change more than half of t
 none (operands constant or periodic along the axis) lets a kernel with that very mistake pass torch.equal.  Nothing here
 imports, runs or emulates the compiled library; the catalogue acts on reference operands only.
 
+The LayerNorm data (ED.ln_case, ED.ln_accum_case) has a catalogue of its own: rows, columns, 256-column pieces and lane pairs
+of the row kernels, slabs and bias of the accumulating one, layout and neighbours of the MXFP8 scales.  Its row dependence is
+one sign per element, so a fault changes about half of what it moves: the bar is 40 % of the values and 20 % of the scale bytes.
+The error bound of the GPU accuracy test is measured and checked against wrong formulas here as well.
+
 Large problems are checked on a 256 x 256 subset of the output spread evenly over the rows and columns (so over every tile);
 a fault is an index map, applied to the full operand's indices before the subset is taken.  A fault that is the identity
 map at a shape (a rotation of K-tiles when K is one tile, a flip of a 1 x 1 kernel) is no fault there and is passed over;
@@ -272,6 +277,228 @@ def test_conv_data_sees_every_fault(name, shapes):
     if all(k == 1 for (_, _, _, k, _, _, _) in shapes):
         expect -= {"conv W: kh flipped", "conv W: kw flipped"}
     assert met == expect, expect - met
+
+
+# ------------------------------------------------------------------------------------------------ LayerNorm
+VALUE_FAULT, SCALE_FAULT = 0.40, 0.20        # row dependence of the LayerNorm data is one sign: about 0.5 is the ceiling
+
+
+def _ln_nwaves(M, cus=ED.LN_HOST_CUS):
+    """Row stride of the production row kernel: the waves of its grid (rows per wave ceil(M / (16 CUs)), four waves a workgroup)."""
+    rpw = -(-M // (16 * cus))
+    return -(-(-(-M // rpw)) // 4) * 4
+
+
+def pieces_0_1_swapped(D):                     # two 256-column pieces change places
+    c = _ar(D)
+    return torch.where(c < 256, c + 256, torch.where(c < 512, c - 256, c)) if D >= 512 else c
+
+
+def pair_swap_lost(D):
+    """The 16-byte store without the exchange inside lane pairs: columns 4l+4..4l+7 of piece j (the odd lane's) change places
+    with columns 4l..4l+3 of piece j+1 (the even lane's), l even, for every pair of whole pieces j, j+1 (j even)."""
+    c = _ar(D)
+    piece, lane, e = c // 256, (c % 256) // 4, c % 4
+    paired = (piece // 2 * 2 + 1) * 256 + 255 < D
+    up = paired & (piece % 2 == 0) & (lane % 2 == 1)          # (j, odd lane) takes (j+1, lane - 1)
+    down = paired & (piece % 2 == 1) & (lane % 2 == 0)        # (j+1, even lane) takes (j, lane + 1)
+    return torch.where(up, (piece + 1) * 256 + (lane - 1) * 4 + e, torch.where(down, (piece - 1) * 256 + (lane + 1) * 4 + e, c))
+
+
+# (name, where it acts: "x" = the rows / columns the kernel loads, "y" = where it stores; axis; map taking (size, M))
+LN_FAULTS = [
+    ("row r takes row r - 1", "y", 0, lambda n, M: rotated(-1)(n)),
+    ("row r takes row r - nwaves", "y", 0, lambda n, M: rotated(-_ln_nwaves(M))(n)),
+    ("loaded columns shifted by 4", "x", 1, lambda n, M: rotated(4)(n)),
+    ("stored columns shifted by 4", "y", 1, lambda n, M: rotated(4)(n)),
+    ("loaded 256-column pieces 0 and 1 exchanged", "x", 1, lambda n, M: pieces_0_1_swapped(n)),
+    ("stored 256-column pieces 0 and 1 exchanged", "y", 1, lambda n, M: pieces_0_1_swapped(n)),
+    ("lane-pair swap of the 16-byte store lost", "y", 1, lambda n, M: pair_swap_lost(n)),
+]
+
+
+def _ln_value_catalogue(M, D):
+    x, gamma, beta, y = ED.ln_case(M, D)
+    seen, low = set(), []
+    for name, op, axis, fn in LN_FAULTS:
+        m = fn((M, D)[axis], M)
+        if _is_identity(m):
+            continue
+        if op == "y":
+            bad = y.index_select(axis, m)
+        elif M * D <= 1 << 20:
+            bad = ED.ln_reference(x.index_select(axis, m), gamma, beta, ED.LN_EPS)
+        else:                                   # a permutation of a row's columns keeps mean and variance: the closed form holds
+            bad = (x.index_select(axis, m) - x.mean(1, keepdim=True)).double() * gamma.double() + beta.double()
+        moved = (m != _ar(m.numel())).nonzero()[:, 0]         # the fraction is taken over the rows / columns the fault moves
+        frac = float((bad != y).index_select(axis, moved).float().mean())
+        seen.add(name)
+        if not frac >= VALUE_FAULT:
+            low.append((name, round(frac, 4)))
+    return seen, low
+
+
+def test_ln_data_sees_every_fault():
+    """Every row, column, piece and lane-pair fault changes at least 40 % of the LayerNorm outputs it moves at every (M, D) the
+    exact GPU test runs (the builder itself asserts balance, mean, rstd = 1 and the 16-bit exactness of y at each of them)."""
+    met, bad = set(), []
+    for (M, D) in ED.ln_shapes():
+        seen, low = _ln_value_catalogue(M, D)
+        met |= seen
+        if low:
+            bad.append(((M, D), low))
+    assert not bad, bad
+    assert met == {f[0] for f in LN_FAULTS}
+
+
+def test_ln_data_properties():
+    """Rows balanced; rstd exactly 1 and y the closed form under the fp32 emulation; y exact in bf16 and fp16; a constant row
+    gives beta bit for bit; F.layer_norm is NOT the reference (it is not bit-exact on this data at every D)."""
+    for (M, D) in [(5, 4), (5, 96), (197, 256), (197, 1280), (7, 2048)]:
+        x, gamma, beta, y = ED.ln_case(M, D)
+        pair = x[:, :D // 2] + x[:, D // 2:]                       # column c and column c + D / 2 are m_r +- 0.5
+        assert torch.equal(pair, pair[:, :1].expand_as(pair)) and torch.equal(pair[:, :1] / 2, x.mean(1, keepdim=True))
+        assert torch.equal((x - pair[:, :1] / 2).abs(), torch.full((M, D), 0.5))
+        emu, mean, rstd = ED.ln_emulate(x, gamma, beta, ED.LN_EPS)
+        assert torch.equal(rstd, torch.ones(M, 1)) and torch.equal(emu.double(), y)
+        assert torch.equal(y.float().bfloat16().double(), y) and torch.equal(y.float().half().double(), y)
+        n = y * 16                                                 # an odd integer of at most 5 bits times 2^(k + 3), k = -3..3
+        assert torch.equal(n, n.round()) and float(y.abs().max()) <= 15.5 * 8 and float(y.abs().min()) >= 0.5 / 8
+        xc = x.clone()
+        xc[M // 2] = 3.0
+        assert torch.equal(ED.ln_emulate(xc, gamma, beta, ED.LN_EPS)[0][M // 2], beta)
+        assert torch.equal(ED.ln_reference(xc, gamma, beta, ED.LN_EPS)[M // 2], beta.double())
+    # the data is a pure function of the shape, and differs between shapes
+    assert torch.equal(ED.ln_case(5, 96)[0], ED.ln_case(5, 96)[0]) and not torch.equal(ED.ln_case(5, 96)[0][:3], ED.ln_case(3, 96)[0])
+
+
+def test_ln_accum_data_sees_every_fault():
+    """A slab dropped or added twice and the bias dropped change at least 40 % of the accumulated x and of its LayerNorm, at
+    every (M, D, S) of the exact hm_layernorm_accum test; the operands are multiples of 0.5 whose sum is the ln_case row."""
+    for D in ED.LN_ACCUM_D:
+        for M in ED.LN_ACCUM_M:
+            for S in ED.LN_ACCUM_S:
+                for bias in (True, False):
+                    x0, parts, b, x, gamma, beta, y = ED.ln_accum_case(M, D, S, bias)
+                    assert parts.shape == (S, M, D) and (b is None) == (not bias)
+                    for t in (x0, parts) + ((b,) if bias else ()):
+                        assert torch.equal(t * 2, (t * 2).round())
+                    bsum = b if bias else torch.zeros(D)
+                    assert torch.equal(x0 + (bsum + parts.sum(0)), x)              # in fp32, in the kernel's grouping
+                    faults = [("first slab dropped", x - parts[0]), ("last slab dropped", x - parts[S - 1]),
+                              ("first slab added twice", x + parts[0]), ("last slab added twice", x + parts[S - 1])]
+                    if bias:
+                        faults.append(("bias dropped", x - b))
+                    for name, xf in faults:
+                        fx = float((xf != x).float().mean())
+                        fy = float((ED.ln_reference(xf, gamma, beta, ED.LN_EPS) != y).float().mean())
+                        assert fx >= VALUE_FAULT and fy >= VALUE_FAULT, ((M, D, S, bias), name, fx, fy)
+
+
+def test_ln_mx8_scales_see_every_fault():
+    """The E8M0 bytes of the quantised closed form depend on the block AND on the row: written [M][D/32], or taken from the
+    neighbouring block or row, at least 20 % of them change; with more than one block and more than two rows they take two
+    values along the rows of some block and min(3, blocks) values along the blocks of some row."""
+    from oracle import fp8_ref as Q
+    met, lo, hi = set(), 255, 0
+    for D in ED.LN_MX8_D:
+        for M in ED.LN_MX8_M:
+            y = ED.ln_case(M, D)[3].float()
+            q, sc = Q.mx8_quantize(y)
+            nblk = D // 32
+            assert sc.shape == (nblk, M)
+            lo, hi = min(lo, int(sc.min())), max(hi, int(sc.max()))
+            assert torch.equal(Q.mx8_quantize(y)[0], q)
+            faults = [("scales written [M][D/32]", sc.t().contiguous().view(nblk, M), nblk > 1 and M > 1),
+                      ("scale of the neighbouring block", sc.roll(1, 0), nblk > 1),
+                      ("scale of the neighbouring row", sc.roll(1, 1), M > 1)]
+            for name, bad, applies in faults:
+                if not applies:
+                    continue
+                met.add(name)
+                frac = float((bad != sc).float().mean())
+                assert frac >= SCALE_FAULT, ((M, D), name, frac)
+            if nblk > 1 and M > 2:
+                assert max(len(set(r.tolist())) for r in sc) >= 2, (M, D)
+                assert max(len(set(c.tolist())) for c in sc.t()) >= min(3, nblk), (M, D)
+            if M >= 197:
+                assert all(len(set(r.tolist())) >= 2 for r in sc), (M, D)
+    assert len(met) == 3 and 116 <= lo and hi <= 126 and hi - lo >= 8, (lo, hi)
+
+
+def _ln_one_pass(x, gamma, beta, eps):
+    D = x.shape[1]
+    mean = x.sum(1, keepdim=True) / D
+    return (x - mean) / torch.sqrt((x * x).sum(1, keepdim=True) / D - mean * mean + eps) * gamma + beta
+
+
+def _ln_two_pass(x, gamma, beta, eps, rstd):
+    D = x.shape[1]
+    d = x - x.sum(1, keepdim=True) / D
+    return d * rstd((d * d).sum(1, keepdim=True) / D, eps) * gamma + beta
+
+
+def _hostile(D, eps):
+    x, gamma, beta, kind = ED.ln_hostile_rows(D, eps)
+    return x, gamma, beta, kind, ED.ln_reference(x, gamma, beta, eps)
+
+
+def _row_err(got, ref):
+    return torch.nan_to_num((got.double() - ref).abs().amax(1, keepdim=True), nan=float("inf"))
+
+
+def test_ln_error_multiples_are_the_measured_ones():
+    """ED.LN_MULTIPLES states, per kind of row, the largest error of the fp32 two-pass emulation against fp64 in units of
+    ED.ln_error_unit.  Measured here over D in {96, 320, 1280, 2048} and eps in {1e-6, 1e-5}: uniform 1.52, mean 1000 0.95,
+    mean -3000 0.80, variance = eps 1.69, variance = 1e-3 eps 2.28, one outlier of 1e4 1.86, all-zero row 0 (error 0).  The table
+    holds them rounded up; it may neither be exceeded nor be twice what is measured."""
+    worst = torch.zeros(len(ED.LN_HOSTILE_KINDS), dtype=torch.float64)
+    for D in ED.LN_HOSTILE_D:
+        for eps in ED.LN_HOSTILE_EPS:
+            x, gamma, beta, kind, ref = _hostile(D, eps)
+            assert float(x.abs().max()) <= 1e4
+            err = _row_err(ED.ln_emulate(x, gamma, beta, eps)[0], ref)
+            unit = ED.ln_error_unit(x, gamma, eps)
+            zero = kind == ED.LN_HOSTILE_KINDS.index("zero")
+            assert float(err[zero].max()) == 0.0 and float(unit[zero].max()) == 0.0
+            assert (err <= ED.ln_error_bound(x, gamma, eps, kind, margin=1.0)).all(), (D, eps)
+            ratio = torch.where(zero[:, None], torch.zeros_like(err), err / unit.clamp_min(1e-300))
+            worst = torch.maximum(worst, torch.stack([ratio[kind == i].max() for i in range(len(worst))]))
+    for i, k in enumerate(ED.LN_HOSTILE_KINDS):
+        assert float(worst[i]) <= ED.LN_MULTIPLES[k] <= 2 * float(worst[i]), (k, float(worst[i]))
+    assert ED.LN_KERNEL_MARGIN == 4.0
+
+
+def test_ln_error_bound_separates_wrong_formulas():
+    """The bound the GPU accuracy test gives the kernels (4 x the measured multiples) against three wrong LayerNorms, on the
+    CPU in fp32: a one-pass E[x^2] - mean^2 variance misses it by >= 100 x on the worst row of each large-mean kind, and an
+    eps added outside the square root, or left out, by >= 100 x on EVERY row whose variance is eps or 1e-3 eps."""
+    kinds = ED.LN_HOSTILE_KINDS
+    for D in ED.LN_HOSTILE_D:
+        for eps in ED.LN_HOSTILE_EPS:
+            x, gamma, beta, kind, ref = _hostile(D, eps)
+            bound = ED.ln_error_bound(x, gamma, eps, kind)
+            over = _row_err(_ln_one_pass(x, gamma, beta, eps), ref) / bound
+            for k in ("mean_1000", "mean_-3000"):
+                assert float(over[kind == kinds.index(k)].max()) >= 100, (D, eps, k)
+            outside = _ln_two_pass(x, gamma, beta, eps, lambda var, e: 1.0 / (torch.sqrt(var) + e))
+            dropped = _ln_two_pass(x, gamma, beta, eps, lambda var, e: 1.0 / torch.sqrt(var))
+            for got in (outside, dropped):
+                over = _row_err(got, ref) / bound
+                for k in ("var_eps", "var_1e-3_eps"):
+                    assert float(over[kind == kinds.index(k)].min()) >= 100, (D, eps, k)
+            right = _ln_two_pass(x, gamma, beta, eps, lambda var, e: 1.0 / torch.sqrt(var + e))
+            assert (_row_err(right, ref) <= bound / ED.LN_KERNEL_MARGIN).all()
+
+
+def test_ln_builders_refuse_data_that_is_not_exact(monkeypatch):
+    monkeypatch.setattr(ED, "LN_EPS", 0.5)                       # rstd = 1 / sqrt(0.75): the closed form no longer holds
+    with pytest.raises(AssertionError):
+        ED.ln_case(5, 96)
+    monkeypatch.setattr(ED, "LN_EPS", 0.75)
+    monkeypatch.setattr(ED, "LN_PEAK_GAMMA", 4097)               # y needs more bits than bf16 has
+    with pytest.raises(AssertionError):
+        ED.ln_case(5, 96)
 
 
 # ------------------------------------------------------------------------------------------------ the data and the report

@@ -75,7 +75,7 @@ def test_gemm_fp8_epilogues(M, N, K):
     assert (err == 0).float().mean().item() > 0.99
 
 
-@pytest.mark.parametrize("D", [1280, 320])
+@pytest.mark.parametrize("D", [1280, 320, 32, 768, 1536, 2048])      # MAXJ 5, 2, 2 (one 8-lane group), 5, 8, 8
 def test_layernorm_mx8(D):
     M = 520
     x = _u("lx", (M, D), 2.0, seed=D) + _u("lxr", (M, 1), 3.0, seed=D + 1)

@@ -132,6 +132,19 @@ def test_abi_rejects_bad_arguments_without_gpu():
     assert lib.hm_hamer_workspace_bytes(None, 4) == 0
 
 
+def test_norm_entry_points_reject_bad_arguments_without_gpu():
+    """The width and count checks of csrc/norm.hip come before any launch: D % 32 and D <= 2048 for the MXFP8 LayerNorm, a slab
+    count above 0 and D <= 2048 for the accumulating one, and a column window inside the leading dimension for hm_absmax16."""
+    lib = L.load()
+    assert lib.hm_layernorm_mx8(16, 16, 16, 16, 16, 4, 48, 1e-6, None) != 0 and b"D % 32" in lib.hm_last_error_string()
+    assert lib.hm_layernorm_mx8(16, 16, 16, 16, 16, 4, 2080, 1e-6, None) != 0 and b"2048" in lib.hm_last_error_string()
+    assert lib.hm_layernorm_accum(16, 16, 0, 16, 16, 16, 16, 0, 4, 256, 1e-6, None) != 0
+    assert b"hm_layernorm_accum" in lib.hm_last_error_string()
+    assert lib.hm_layernorm_accum(16, 16, 1, 16, 16, 16, 16, 0, 4, 2052, 1e-6, None) != 0 and b"2048" in lib.hm_last_error_string()
+    assert lib.hm_absmax16(16, 8, 4, 5, 4, L.HM_DTYPE_BF16, 16, None) != 0 and b"hm_absmax16" in lib.hm_last_error_string()
+    assert lib.hm_absmax16(16, 8, 4, 0, 9, L.HM_DTYPE_F16, 16, None) != 0 and lib.hm_absmax16(16, 8, 4, -1, 4, L.HM_DTYPE_F16, 16, None) != 0
+
+
 def test_host_tensor_is_refused():
     from hamer_yolo_amd import ops
     with pytest.raises(L.HipLibraryError):
