@@ -42,6 +42,7 @@ EXPORTS = [
     "hm_crop_aa_box_from_bbox", "hm_crop_batch_aa",
     "hm_pose_eval",
     "hm_skeleton_overlay_workspace_bytes", "hm_skeleton_overlay",
+    "hm_det_match", "hm_det_ap_workspace_bytes", "hm_det_ap", "hm_det_ap_curve",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -269,6 +270,11 @@ def load() -> C.CDLL:
     lib.hm_skeleton_overlay_workspace_bytes.argtypes = [i, i, i, i]
     lib.hm_skeleton_overlay_workspace_bytes.restype = C.c_size_t
     lib.hm_skeleton_overlay.argtypes = [vp, i, i, i, vp, i, C.POINTER(Skeleton), i, C.POINTER(C.c_uint8), i, vp, vp, C.c_size_t, vp]
+    lib.hm_det_match.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, vp, vp, vp, vp]
+    lib.hm_det_ap_workspace_bytes.argtypes = [i, i, i]
+    lib.hm_det_ap_workspace_bytes.restype = C.c_size_t
+    lib.hm_det_ap.argtypes = [vp, vp, vp, i, vp, vp, i, i, vp, vp, i, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.hm_det_ap_curve.argtypes = [vp, vp, i, vp, i, vp, vp, vp, vp]
     lib.hm_prof_begin.argtypes = [i]
     lib.hm_prof_collect.argtypes = [C.POINTER(ProfRecord), i]
     lib.hm_prof_end.argtypes = []
@@ -278,7 +284,7 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         if name not in ("hm_version", "hm_last_error_string", "hm_hamer_workspace_bytes", "hm_nms_workspace_bytes", "hm_tome_index_bytes", "hm_conv_splitk_bytes",
                         "hm_mesh_overlay_workspace_bytes", "hm_mesh_render_workspace_bytes",
-                        "hm_skeleton_overlay_workspace_bytes"):
+                        "hm_skeleton_overlay_workspace_bytes", "hm_det_ap_workspace_bytes"):
             fn.restype = i
     if lib.hm_version() != HM_VERSION:
         raise HipLibraryError(f"{LIB_PATH} reports HM_VERSION {lib.hm_version()}, this binding is written for {HM_VERSION}: "

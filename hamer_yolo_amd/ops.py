@@ -337,3 +337,73 @@ def crop_batch_aa(frame: torch.Tensor, rec: torch.Tensor, mean, std, P: int = 25
     L.check(L.load().hm_crop_batch_aa(L.ptr(frame), H, W, base + first * rsz, base + n * rsz + first * tsz, L.ptr(out), B, P,
                                       m3, s3, L.current_stream()), "hm_crop_batch_aa")
     return out
+
+
+def _chk(t: torch.Tensor, dtype, shape, what: str) -> None:
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous {dtype} tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+
+def det_match(pred: torch.Tensor, pred_count: torch.Tensor, labels: torch.Tensor, label_count: torch.Tensor,
+              iouv: torch.Tensor):
+    """hm_det_match.  pred (N, stride, 6) fp32 [xyxy, conf, cls], pred_count (N,) int32, labels (N, lmax, 5) fp32 [cls, xyxy],
+    label_count (N,) int32, iouv (niou,) fp32, all contiguous device tensors -> correct (N, stride, niou) uint8,
+    best_iou (N, stride) fp32, matched (N, stride) int32.  Asynchronous on the current stream."""
+    _dev(pred, pred_count, labels, label_count, iouv)
+    if pred.dim() != 3 or labels.dim() != 3:
+        raise ValueError(f"det_match: pred {tuple(pred.shape)} / labels {tuple(labels.shape)}: expected (N, stride, 6) and (N, lmax, 5)")
+    N, stride, lmax, niou = int(pred.shape[0]), int(pred.shape[1]), int(labels.shape[1]), int(iouv.numel())
+    _chk(pred, torch.float32, (N, stride, 6), "det_match pred")
+    _chk(labels, torch.float32, (N, lmax, 5), "det_match labels")
+    _chk(pred_count, torch.int32, (N,), "det_match pred_count")
+    _chk(label_count, torch.int32, (N,), "det_match label_count")
+    _chk(iouv, torch.float32, (niou,), "det_match iouv")
+    correct = torch.empty(N, stride, niou, dtype=torch.uint8, device=pred.device)
+    best_iou = torch.empty(N, stride, dtype=torch.float32, device=pred.device)
+    matched = torch.empty(N, stride, dtype=torch.int32, device=pred.device)
+    L.check(L.load().hm_det_match(L.ptr(pred), L.ptr(pred_count), L.ptr(labels), L.ptr(label_count), L.ptr(iouv), N, stride,
+                                  lmax, niou, L.ptr(correct), L.ptr(best_iou), L.ptr(matched), L.current_stream()), "hm_det_match")
+    return correct, best_iou, matched
+
+
+def det_ap(tp: torch.Tensor, conf: torch.Tensor, pred_cls: torch.Tensor, classes: torch.Tensor, n_labels: torch.Tensor,
+           x101: torch.Tensor, px: torch.Tensor, v5_metric: bool = False):
+    """hm_det_ap.  tp (P, niou) uint8, conf (P,) fp32, pred_cls (P,) fp32, ALREADY sorted by descending confidence;
+    classes (nc,) fp32, n_labels (nc,) int32; x101 (101,) and px (1000,) fp64 -> ap (nc, niou), p (nc, 1000), r (nc, 1000)
+    fp64.  Asynchronous on the current stream."""
+    _dev(tp, conf, pred_cls, classes, n_labels, x101, px)
+    if tp.dim() != 2:
+        raise ValueError(f"det_ap: tp {tuple(tp.shape)}: expected (P, niou)")
+    P, niou, nc = int(tp.shape[0]), int(tp.shape[1]), int(classes.numel())
+    _chk(tp, torch.uint8, (P, niou), "det_ap tp")
+    _chk(conf, torch.float32, (P,), "det_ap conf")
+    _chk(pred_cls, torch.float32, (P,), "det_ap pred_cls")
+    _chk(classes, torch.float32, (nc,), "det_ap classes")
+    _chk(n_labels, torch.int32, (nc,), "det_ap n_labels")
+    _chk(x101, torch.float64, (101,), "det_ap x101")
+    _chk(px, torch.float64, (1000,), "det_ap px")
+    lib = L.load()
+    ap = torch.empty(nc, niou, dtype=torch.float64, device=tp.device)
+    p = torch.empty(nc, 1000, dtype=torch.float64, device=tp.device)
+    r = torch.empty(nc, 1000, dtype=torch.float64, device=tp.device)
+    nbytes = int(lib.hm_det_ap_workspace_bytes(P, nc, niou))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=tp.device) if nbytes else None
+    L.check(lib.hm_det_ap(L.ptr(tp) if P else None, L.ptr(conf) if P else None, L.ptr(pred_cls) if P else None, P,
+                          L.ptr(classes), L.ptr(n_labels), nc, niou, L.ptr(x101), L.ptr(px), int(bool(v5_metric)), L.ptr(ap),
+                          L.ptr(p), L.ptr(r), L.ptr(ws), nbytes, L.current_stream()), "hm_det_ap")
+    return ap, p, r
+
+
+def det_ap_curve(recall: torch.Tensor, precision: torch.Tensor, x101: torch.Tensor, v5_metric: bool = False):
+    """hm_det_ap_curve.  recall, precision (n,) fp64 device tensors -> ap (1,), mpre (n + 2,), mrec (n + 2,) fp64."""
+    _dev(recall, precision, x101)
+    n = int(recall.numel())
+    _chk(recall, torch.float64, (n,), "det_ap_curve recall")
+    _chk(precision, torch.float64, (n,), "det_ap_curve precision")
+    _chk(x101, torch.float64, (101,), "det_ap_curve x101")
+    ap = torch.empty(1, dtype=torch.float64, device=recall.device)
+    mpre = torch.empty(n + 2, dtype=torch.float64, device=recall.device)
+    mrec = torch.empty(n + 2, dtype=torch.float64, device=recall.device)
+    L.check(L.load().hm_det_ap_curve(L.ptr(recall), L.ptr(precision), n, L.ptr(x101), int(bool(v5_metric)), L.ptr(ap),
+                                     L.ptr(mpre), L.ptr(mrec), L.current_stream()), "hm_det_ap_curve")
+    return ap, mpre, mrec

@@ -751,6 +751,53 @@ typedef struct hm_pose_eval_args {
  * or 4, root outside -1..P-1, a bit of sel at or past P, all four outputs NULL, pred or gt not 4-byte aligned. */
 int hm_pose_eval(const hm_pose_eval_args* args, void* stream);
 
+/* ---- Detector evaluation (yolo/yolov7/test.py and utils/metrics.py): csrc/det_eval.hip.  The caller owns every buffer, the
+ * calls are asynchronous on `stream`, nothing synchronises or allocates, argument errors return HM_ERR_ARG before any device
+ * work.  All fp32 / fp64 arithmetic is plain IEEE in the order written (no FMA contraction, no fast-math).
+ *
+ * hm_det_match: test.py:178-209 for N images in one launch (one wave per image), IoU as box_iou of general.py:447-469 in fp32:
+ * inter = clamp(min(x2) - max(x1), 0) * clamp(min(y2) - max(y1), 0), iou = inter / (area1 + area2 - inter).
+ *   pred [N][stride][6] f32 (xyxy, conf, cls: the layout of hm_yolo_nms's dets), pred_count [N] i32,
+ *   labels [N][lmax][5] f32 (cls, xyxy, the predictions' units), label_count [N] i32, iouv [niou] f32 (test.py:78);
+ *   correct [N][stride][niou] u8, best_iou [N][stride] f32, matched [N][stride] i32 (the target's index in its image or -1).
+ * Per image: the label classes in ascending order and, within a class, its predictions in stored order (:191-202); a
+ * prediction takes its best-IoU target of that class, the lowest index on a tie (:198); a NaN IoU in its row leaves it
+ * unmatched with best_iou NaN (torch.max hands a NaN on); it is assigned only when iou > iouv[0], strictly, and that target
+ * is still free, and then correct = iou > iouv (:202-207); a prediction whose best target is taken does NOT fall back to its
+ * second best; the walk stops once every label of the image is taken (:208).  best_iou is the row maximum whether or not the
+ * prediction was assigned, 0 when no label has its class.  Rows at or past pred_count[i] are written 0 / 0 / -1 and rows of
+ * labels at or past label_count[i] are never read into a result.  Counts are clamped to [0, stride] and [0, lmax] in the
+ * kernel.  An image's output bytes depend on that image alone, not on N or its place.
+ * HM_ERR_ARG: a null pointer, N < 1, stride outside 1..4096, lmax outside 1..1024, niou outside 1..16. */
+int hm_det_match(const float* pred, const int* pred_count, const float* labels, const int* label_count, const float* iouv,
+                 int N, int stride, int lmax, int niou, uint8_t* correct, float* best_iou, int* matched, void* stream);
+
+/* hm_det_ap: ap_per_class (metrics.py:18-78) with compute_ap (:81-110) for every (class, threshold) pair, one workgroup each.
+ *   tp [P][niou] u8, conf [P] f32, pred_cls [P] f32: the predictions ALREADY sorted by descending confidence (:33-34);
+ *   classes [nc] f32: the sorted unique target classes (:37), n_labels [nc] i32 (:45);
+ *   x101 [101] f64 and px [1000] f64: the abscissae of :104 and :41, passed in so that they are np.linspace's bits;
+ *   ap [nc][niou], p [nc][1000], r [nc][1000] f64 (p and r from threshold 0, :57-60).
+ * A class with no prediction or no label leaves zeros (:48-49).  Cumulative counts are integers; recall = tpc / (n_l + 1e-16),
+ * precision = tpc / (tpc + fpc) in fp64; the envelope is a reverse running maximum (:99); the sentinels are :93-96
+ * (mrec ends at recall[-1] + 0.01, or 1.0 with v5_metric); the area is np.trapz over x101 (:105).  Interpolation is np.interp:
+ * for x the right-most knot j with xp[j] <= x gives fp[j] + (x - xp[j]) * ((fp[j+1] - fp[j]) / (xp[j+1] - xp[j])),
+ * x >= xp[-1] gives fp[-1], x < xp[0] gives `left` (0 for r, 1 for p).  tp counts of a class are expected not to exceed its
+ * n_labels (with v5_metric a recall above 1 would make mrec decrease, which np.interp leaves undefined too).
+ * 0 <= P <= 2^30 (1073741824: counts and indices are int32 with a bit to spare); 1 <= nc <= 65535; 1 <= niou <= 16.  The
+ * kernel keeps no curve, so hm_det_ap_workspace_bytes is 0 for every legal size today and workspace may be NULL; callers
+ * that size and pass it stay correct if that changes.  HM_ERR_ARG: P < 0 or > 2^30, nc or niou outside their ranges, a null
+ * pointer (tp, conf and pred_cls may be NULL when P == 0). */
+size_t hm_det_ap_workspace_bytes(int P, int nc, int niou);
+int hm_det_ap(const uint8_t* tp, const float* conf, const float* pred_cls, int P, const float* classes, const int* n_labels,
+              int nc, int niou, const double* x101, const double* px, int v5_metric, double* ap, double* p, double* r,
+              void* workspace, size_t workspace_bytes, void* stream);
+
+/* hm_det_ap_curve: compute_ap (metrics.py:81-110) of one given curve, recall [n] (non-decreasing) and precision [n] f64,
+ * 1 <= n <= 2^30: ap [1], mpre [n + 2], mrec [n + 2] f64.  The interpolation and the trapezoid are the device code of
+ * hm_det_ap.  HM_ERR_ARG: a null pointer, n outside its range. */
+int hm_det_ap_curve(const double* recall, const double* precision, int n, const double* x101, int v5_metric, double* ap,
+                    double* mpre, double* mrec, void* stream);
+
 /* Optional per-launch timing (HIP events on the launch stream); kinds below. */
 enum { HM_K_GEMM = 0, HM_K_LAYERNORM = 1, HM_K_ATTENTION = 2, HM_K_IM2COL = 3, HM_K_LINEAR_F32 = 4,
        HM_K_CROSS_ATTN = 5, HM_K_MANO = 6, HM_K_CROP = 7, HM_K_CONV = 8, HM_K_OTHER = 9 };
