@@ -2,6 +2,7 @@
 
     python -m hamer_yolo_amd.evaluate_det --pred DIR --labels DIR [--size W H] [--json out.json]
     python -m hamer_yolo_amd.evaluate_det --images DIR --labels DIR [--weights W] [--precise-detector]
+                                          [--protocol {deployed,test}] [--multi-label]
                                           [--conf-thres C] [--iou-thres I] [--save-txt DIR [--save-conf]]
                                           [--det-frames N] [--json out.json]
 
@@ -15,9 +16,14 @@ scored on the device from the plan's ``dets`` / ``count`` (hm_det_match), with n
 
 An image without a label file has zero labels.  A label file without an image is reported and skipped.
 
-The thresholds default to the deployed ones (config/yolo_config.py: conf 0.25, IoU 0.35), NOT to test.py's 0.001 / 0.65: a PR
-curve cut at conf 0.25 ends early, so the mAP printed here is lower than the one test.py's defaults would give for the same
-weights.  The table says which thresholds it was made with.
+``--protocol deployed`` (the default) scores at the deployed thresholds (config/yolo_config.py: conf 0.25, IoU 0.35, best class
+only, NMS as configured there).  A PR curve cut at conf 0.25 ends early, so that mAP is lower than the one test.py prints for
+the same weights.  ``--protocol test`` is test.py's own (test.py:125): conf 0.001, IoU 0.65, multi-label candidates, class-aware
+NMS over all classes, 300 boxes per image, then the same matching and AP; the whole pass goes through one hm_yolo_nms_batch
+call.  An explicit ``--conf-thres`` / ``--iou-thres`` still wins, and ``--multi-label`` alone adds the multi-label branch to the
+deployed thresholds.  Not reproduced from test.py: its dataloader's letterbox (``rect``, pad 0.5) -- the detector's own
+letterbox is used -- ``--augment``, ``--single-cls``, ``--save-hybrid`` and the COCO JSON.  The table says which protocol and
+thresholds it was made with.
 """
 from __future__ import annotations
 
@@ -100,10 +106,13 @@ def score_folders(pred_dir: str, label_dir: str, size=None, json_path: Optional[
 
 
 def score_images(image_dir: str, label_dir: str, detector, save_txt: Optional[str] = None, save_conf: bool = False,
-                 json_path: Optional[str] = None, det_frames: int = DET_FRAMES) -> Dict:
+                 json_path: Optional[str] = None, det_frames: int = DET_FRAMES, multi_label: bool = False,
+                 agnostic: Optional[bool] = None, protocol: str = "deployed") -> Dict:
     """Run ``detector`` over the images of ``image_dir`` in batched passes (runs of consecutive equally sized frames, up to
     ``det_frames``) and score every pass on the device against the label files of ``label_dir``.  ``save_txt``: also write the
-    predictions, one file per image, in the label format (this copies each pass's boxes to the host)."""
+    predictions, one file per image, in the label format (this copies each pass's boxes to the host).  ``multi_label``: the
+    reference's multi-label NMS branch (the pass then goes through one hm_yolo_nms_batch call); ``agnostic``: None reads
+    ``detector.opt.agnostic_nms``; ``protocol`` is recorded in the result."""
     import torch
     from .infer import _imread_bgr, _list_images
     from .yolo import metrics as M
@@ -113,6 +122,7 @@ def score_images(image_dir: str, label_dir: str, detector, save_txt: Optional[st
     only_labels = [s for s in sorted(labels) if s not in set(stems)]
     opt, eng = detector.opt, detector.engine
     ev = M.DetEvaluator(eng.nc)
+    agnostic = bool(opt.agnostic_nms) if agnostic is None else bool(agnostic)
     if save_txt:
         os.makedirs(save_txt, exist_ok=True)
     unreadable = []
@@ -139,7 +149,7 @@ def score_images(image_dir: str, label_dir: str, detector, save_txt: Optional[st
         H, W = run[0][1].shape[:2]
         frames = torch.from_numpy(np.stack([im for _, im in run])).to(detector.device)
         p = eng.forward(list(frames))
-        eng.nms_enqueue(p, opt.conf_thres, opt.iou_thres, opt.classes, opt.agnostic_nms, scale=True)
+        eng.nms_enqueue(p, opt.conf_thres, opt.iou_thres, opt.classes, agnostic, scale=True, multi_label=bool(multi_label))
         g = np.array([W, H, W, H], np.float32)
         T = [M.load_label_file(labels[s]) if s in labels else np.zeros((0, 5), np.float32) for s, _ in run]
         for t in T:
@@ -156,7 +166,8 @@ def score_images(image_dir: str, label_dir: str, detector, save_txt: Optional[st
                 M.save_label_file(os.path.join(save_txt, s + ".txt"), host[k, :int(counts[k])], size=(W, H), conf=save_conf)
     result = _result_dict(ev.result(), list(eng.names),
                           {"only_labels": only_labels, "unreadable": unreadable, "conf_thres": float(opt.conf_thres),
-                           "iou_thres": float(opt.iou_thres), "precise": bool(detector.precise)})
+                           "iou_thres": float(opt.iou_thres), "precise": bool(detector.precise), "protocol": str(protocol),
+                           "multi_label": bool(multi_label), "agnostic": agnostic})
     if json_path:
         with open(json_path, "w") as f:
             json.dump(result, f, indent=1)
@@ -171,8 +182,12 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument('--size', type=int, nargs=2, metavar=('W', 'H'), default=None, help="--pred: scale both sides to pixels of this frame size")
     ap.add_argument('--weights', type=str, default=None, help="--images: checkpoint or synthetic:<seed> (default: config/yolo_config.py)")
     ap.add_argument('--precise-detector', action='store_true', help="--images: the fp32 detector route")
-    ap.add_argument('--conf-thres', type=float, default=None, help="--images: default the deployed yolo_opt.conf_thres, not test.py's 0.001")
-    ap.add_argument('--iou-thres', type=float, default=None, help="--images: NMS IoU, default the deployed yolo_opt.iou_thres, not test.py's 0.65")
+    ap.add_argument('--protocol', choices=('deployed', 'test'), default='deployed',
+                    help="--images: deployed = the thresholds and NMS of config/yolo_config.py; test = test.py's: conf 0.001, IoU 0.65, "
+                         "multi-label, class-aware, all classes")
+    ap.add_argument('--multi-label', action='store_true', help="--images: one candidate per (box, class) above the threshold (implied by --protocol test)")
+    ap.add_argument('--conf-thres', type=float, default=None, help="--images: default the protocol's (deployed: yolo_opt.conf_thres; test: 0.001)")
+    ap.add_argument('--iou-thres', type=float, default=None, help="--images: NMS IoU, default the protocol's (deployed: yolo_opt.iou_thres; test: 0.65)")
     ap.add_argument('--save-txt', type=str, default=None, help="--images: also write the predictions to this folder in the label format")
     ap.add_argument('--save-conf', action='store_true', help="with --save-txt: append the confidence column (needed to score the files later)")
     ap.add_argument('--det-frames', type=int, default=DET_FRAMES, help="--images: frames per detector pass")
@@ -192,14 +207,25 @@ def main(argv=None):
         from .yolo.detector import Detector
         if args.weights:
             yolo_opt.weights = args.weights
+        test = args.protocol == 'test'
+        if test:                                                       # test.py:125 and its argument defaults
+            yolo_opt.conf_thres, yolo_opt.iou_thres, yolo_opt.classes = 0.001, 0.65, None
         if args.conf_thres is not None:
             yolo_opt.conf_thres = args.conf_thres
         if args.iou_thres is not None:
             yolo_opt.iou_thres = args.iou_thres
         result = score_images(args.images, args.labels, Detector(yolo_opt, precise=True if args.precise_detector else None),
-                              args.save_txt, args.save_conf, args.json, args.det_frames)
-        note = (f"conf_thres {result['conf_thres']:g}, iou_thres {result['iou_thres']:g} (the deployed defaults are 0.25 / 0.35; "
-                "test.py's are 0.001 / 0.65 -- a PR curve cut at a higher confidence gives a lower mAP)")
+                              args.save_txt, args.save_conf, args.json, args.det_frames, multi_label=test or args.multi_label,
+                              agnostic=False if test else None, protocol=args.protocol)
+        if test:
+            note = (f"protocol test: conf_thres {result['conf_thres']:g}, iou_thres {result['iou_thres']:g}, multi-label, class-aware NMS "
+                    "over all classes, 300 boxes per image, test.py's matching and AP.  Not reproduced: test.py's dataloader "
+                    "letterbox (rect, pad 0.5; the detector's own letterbox is used), --augment, --single-cls, --save-hybrid, COCO JSON")
+        else:
+            note = (f"conf_thres {result['conf_thres']:g}, iou_thres {result['iou_thres']:g} (the deployed defaults are 0.25 / 0.35; "
+                    "test.py's are 0.001 / 0.65 -- a PR curve cut at a higher confidence gives a lower mAP)")
+            if args.multi_label:
+                note += "; multi-label candidates"
     print(format_table(result))
     print(note)
     for s in result["only_labels"]:

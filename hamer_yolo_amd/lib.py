@@ -43,6 +43,7 @@ EXPORTS = [
     "hm_pose_eval",
     "hm_skeleton_overlay_workspace_bytes", "hm_skeleton_overlay",
     "hm_det_match", "hm_det_ap_workspace_bytes", "hm_det_ap", "hm_det_ap_curve",
+    "hm_nms_batch_workspace_bytes", "hm_yolo_nms_batch",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -229,6 +230,10 @@ def load() -> C.CDLL:
     lib.hm_nms_workspace_bytes.argtypes = [i]
     lib.hm_nms_workspace_bytes.restype = C.c_size_t
     lib.hm_yolo_nms.argtypes = [vp, i, i, f, f, C.c_uint, i, i, C.POINTER(LetterboxPlan), vp, vp, vp, C.c_size_t, vp]
+    lib.hm_nms_batch_workspace_bytes.argtypes = [i, i, i, i]
+    lib.hm_nms_batch_workspace_bytes.restype = C.c_size_t
+    lib.hm_yolo_nms_batch.argtypes = [vp, C.c_size_t, i, i, i, f, f, C.c_uint, i, i, i, C.POINTER(LetterboxPlan), vp, C.c_size_t, vp, vp,
+                                      C.c_size_t, vp]
     lib.hm_yolo_run.argtypes = [C.POINTER(YoloOp), i, vp]
     lib.hm_tome_index_bytes.argtypes = [i]
     lib.hm_tome_index_bytes.restype = C.c_size_t
@@ -284,7 +289,7 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         if name not in ("hm_version", "hm_last_error_string", "hm_hamer_workspace_bytes", "hm_nms_workspace_bytes", "hm_tome_index_bytes", "hm_conv_splitk_bytes",
                         "hm_mesh_overlay_workspace_bytes", "hm_mesh_render_workspace_bytes",
-                        "hm_skeleton_overlay_workspace_bytes", "hm_det_ap_workspace_bytes"):
+                        "hm_skeleton_overlay_workspace_bytes", "hm_det_ap_workspace_bytes", "hm_nms_batch_workspace_bytes"):
             fn.restype = i
     if lib.hm_version() != HM_VERSION:
         raise HipLibraryError(f"{LIB_PATH} reports HM_VERSION {lib.hm_version()}, this binding is written for {HM_VERSION}: "

@@ -344,10 +344,23 @@ class YoloEngine:
         return p
 
     def nms_enqueue(self, p: dict, conf_thres: float, iou_thres: float, classes: Optional[List[int]], agnostic: bool,
-                    scale: bool = True, max_det: int = 300) -> None:
-        """Enqueue NMS for every image of the plan; results stay on the device (``dets`` rows [i*300, ..), ``count[i]``)."""
+                    scale: bool = True, max_det: int = 300, multi_label: bool = False, batched: bool = False) -> None:
+        """Enqueue NMS for every image of the plan; results stay on the device (``dets`` rows [i*300, ..), ``count[i]``).
+        Default: one hm_yolo_nms call per image.  ``batched``: ONE hm_yolo_nms_batch call for the pass (a workgroup per image,
+        the same bytes).  ``multi_label``: the reference's multi-label branch (a candidate per (row, class) above the
+        threshold, general.py:662-664); it exists in the batch entry only, so it implies ``batched``."""
         mask = 0xFFFFFFFF if classes is None else sum(1 << int(c) for c in classes)
         n = p["n_pred"]
+        if batched or multi_label:
+            ml = int(bool(multi_label))
+            ws = p.setdefault("nms_batch_ws", {})                      # allocated on first use, per multi_label value
+            if ml not in ws:
+                ws[ml] = torch.empty(self.lib.hm_nms_batch_workspace_bytes(p["nb"], n, self.nc, ml), dtype=torch.uint8, device=self.device)
+            L.check(self.lib.hm_yolo_nms_batch(p["pred"].data_ptr(), n * self.no, p["nb"], n, self.nc, conf_thres, iou_thres, mask,
+                                               int(bool(agnostic)), ml, max_det, C.byref(p["lp"]) if scale else None,
+                                               p["dets"].data_ptr(), 300, p["count"].data_ptr(), ws[ml].data_ptr(), ws[ml].numel(),
+                                               L.current_stream()), "hm_yolo_nms_batch")
+            return
         for i in range(p["nb"]):
             L.check(self.lib.hm_yolo_nms(p["pred"].data_ptr() + i * n * self.no * 4, n, self.nc, conf_thres, iou_thres, mask,
                                          int(bool(agnostic)), max_det, C.byref(p["lp"]) if scale else None,
@@ -355,9 +368,9 @@ class YoloEngine:
                                          p["nms_ws"].data_ptr(), p["nms_ws"].numel(), L.current_stream()), "hm_yolo_nms")
 
     def nms(self, p: dict, conf_thres: float, iou_thres: float, classes: Optional[List[int]], agnostic: bool,
-            scale: bool = True, max_det: int = 300):
+            scale: bool = True, max_det: int = 300, multi_label: bool = False, batched: bool = False):
         """NMS + one host sync (the box list is host data).  One (k, 6) tensor, or a list of them for a batched plan."""
-        self.nms_enqueue(p, conf_thres, iou_thres, classes, agnostic, scale, max_det)
+        self.nms_enqueue(p, conf_thres, iou_thres, classes, agnostic, scale, max_det, multi_label, batched)
         counts = p["count"].tolist()
         outs = [p["dets"][i * 300:i * 300 + int(k)].clone() for i, k in enumerate(counts)]
         return outs[0] if p["nb"] == 1 else outs

@@ -481,6 +481,31 @@ int hm_yolo_nms(const float* pred, int n, int nc, float conf_thres, float iou_th
                 int max_det, const hm_letterbox_plan* plan, float* dets, int* count, void* workspace,
                 size_t workspace_bytes, void* stream);
 
+/* The same function for the nb images of a pass in ONE call (csrc/nms_batch.hip): one memset of the counters, one filter
+ * launch over nb * n rows, one suppression launch of nb workgroups -- the number of launches does not depend on nb.  Image i
+ * reads pred + i * pred_image_stride (floats, [n][5+nc] f32), writes dets + i * dets_image_stride * 6 (stride in ROWS,
+ * >= max_det) and count[i]; rows past count[i] are not written.  Both branches of general.py:611-703 (labels=(), no merge):
+ *   multi_label == 0  best class per row (:665-667): the bytes hm_yolo_nms gives for that image alone;
+ *   multi_label == 1  every class c with obj * cls_c > conf_thres is a candidate (:662-664), in (row, class) order; nc == 1
+ *                     turns it off (:628).
+ * Per image: rows with obj > conf_thres; score s_c = cls_c * obj (one fp32 multiply; obj itself when nc == 1); class_mask;
+ * box = x -+ w/2, y -+ h/2; descending score, EQUAL SCORES BY ASCENDING row * nc + c (the reference leaves that to its sort);
+ * the best 30000 enter the suppression (:681-682; the reference's argsort there is not stable, this one is); greedy NMS on
+ * box + cls * 4096 (0 when agnostic; the sum rounded to fp32), IoU = inter / (area_i + area_j - inter), each product and sum
+ * rounded on its own, suppressed when IoU > iou_thres (a NaN does not suppress); the first max_det kept, in score order, as
+ * x1, y1, x2, y2, conf, cls without the class offset; plan != NULL: subtract pad, divide by gain, clamp, rintf as hm_yolo_nms.
+ * Workspace, with C = n * (multi_label && nc > 1 ? nc : 1), pow2(x) the least power of two >= x:
+ *   int counter[nb] rounded up to 256 bytes, then per image  u64 key[pow2(C)] | float4 box[n] | float4 sorted[min(C, 30000)]
+ *   hm_nms_batch_workspace_bytes = roundup(nb * 4, 256) + nb * (pow2(C) * 8 + n * 16 + min(C, 30000) * 16), 0 for a refused shape.
+ * A key is (sortable(score) << 32) | ~(row * nc + c); score and class are read back out of it.
+ * HM_ERR_ARG before any device work: a null pred / dets / count / workspace, nb outside 1..4096, nc outside 1..32, max_det
+ * outside 1..1024, n <= 0 or C > 1048576, conf_thres < 0 or NaN, dets_image_stride < max_det, a workspace smaller than the
+ * above or not 16-byte aligned. */
+size_t hm_nms_batch_workspace_bytes(int nb, int n, int nc, int multi_label);
+int hm_yolo_nms_batch(const float* pred, size_t pred_image_stride, int nb, int n, int nc, float conf_thres, float iou_thres,
+                      unsigned class_mask, int agnostic, int multi_label, int max_det, const hm_letterbox_plan* plan,
+                      float* dets, size_t dets_image_stride, int* count, void* workspace, size_t workspace_bytes, void* stream);
+
 /* One enqueue for a whole planned graph (Model.forward_once, yolo.py:609-639): the host planner
  * (hamer_yolo_amd/yolo/engine.py) turns the layer list into this op array once per input size. */
 enum { HM_OP_CONV = 0, HM_OP_MAXPOOL = 1, HM_OP_UPSAMPLE2X = 2,
