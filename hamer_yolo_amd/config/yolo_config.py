@@ -15,6 +15,9 @@ class Config:
     device = "cuda"
     save_path = "./output"
     precise = False       # True: the fp32 detector route (the reference's CPU branch, detector.py:110-112 half = False)
+    tta = False           # True: test-time augmentation, Model.forward(x, augment=True) (yolo.py:589-605): scales 1, 0.83 mirrored
+                          # and 0.67, one NMS, ~2.2x the detector time.  NOT `augment` above, which stays ignored as the reference
+                          # ignores it -- this is the switch that does what that name promises
 
 
 yolo_opt = Config()

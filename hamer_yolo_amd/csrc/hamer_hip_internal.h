@@ -38,3 +38,19 @@ int hm_conv2d_f32(const hm_conv_args* args, hipStream_t stream);
 // attention.hip: the MFMA attention kernel with a runtime token count and proportional attention (used by hm_tome_attention)
 int hm_attention_tome_launch(const void* qkv, const float* size, void* out, int B, int tokens, int heads, float scale, int dtype,
                              hipStream_t s);   // multiProcessorCount of the current device (cached per device), <= 0 on error
+
+// Element-type dispatch of the detector-side kernels (yolo.hip, tta.hip): f is called with a null pointer of the element type.
+template <class F>
+int with_dtype(int dtype, F&& f) {
+  if (dtype == HM_DTYPE_BF16) return f((__bf16*)nullptr);
+  if (dtype == HM_DTYPE_F16) return f((_Float16*)nullptr);
+  return hm_set_error(HM_ERR_ARG, "bad dtype");
+}
+
+// the detector ops that also have an fp32 form (HM_DTYPE_F32, the precise route): pooling, upsampling, letterbox, the TTA
+// resize.  with_dtype stays 16-bit only -- the RootNet ops share it and have no fp32 route
+template <class F>
+int with_dtype_or_f32(int dtype, F&& f) {
+  if (dtype == HM_DTYPE_F32) return f((float*)nullptr);
+  return with_dtype(dtype, static_cast<F&&>(f));
+}

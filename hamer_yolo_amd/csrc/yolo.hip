@@ -240,21 +240,6 @@ __global__ __launch_bounds__(1024) void nms_kernel(const Cand* __restrict__ cand
   }
 }
 
-template <class F>
-int with_dtype(int dtype, F&& f) {
-  if (dtype == HM_DTYPE_BF16) return f((__bf16*)nullptr);
-  if (dtype == HM_DTYPE_F16) return f((_Float16*)nullptr);
-  return hm_set_error(HM_ERR_ARG, "bad dtype");
-}
-
-// the detector ops that also have an fp32 form (HM_DTYPE_F32, the precise route): pooling, upsampling, letterbox.  with_dtype
-// stays 16-bit only -- the RootNet ops share it and have no fp32 route
-template <class F>
-int with_dtype_or_f32(int dtype, F&& f) {
-  if (dtype == HM_DTYPE_F32) return f((float*)nullptr);
-  return with_dtype(dtype, static_cast<F&&>(f));
-}
-
 }  // namespace
 
 extern "C" int hm_maxpool_nhwc(const void* x, int ldx, void* y, int ldy, int N, int H, int W, int C, int k, int stride,

@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from .infer import *  # noqa: F401,F403
-from .infer import (FRAMES_PER_STEP, _default_models, _detection_list, _imread_bgr, _list_images, _antialias_args, _precise_hamer_args, _record_from, _render_args, render_keypoint_args, apply_antialias_args, apply_precise_args, hamer_inference,  # noqa: F401
+from .infer import (FRAMES_PER_STEP, _default_models, _detection_list, _imread_bgr, _list_images, _antialias_args, _precise_hamer_args, _tta_args, apply_tta_args, _record_from, _render_args, render_keypoint_args, apply_antialias_args, apply_precise_args, hamer_inference,  # noqa: F401
                     hamer_opt, hand_record, iter_folder_results, load_intrinsics, reconstruct_and_save_obj_with_wrapper)
 from .rootnet.Model_RGB import get_model  # noqa: F401
 
@@ -52,6 +52,7 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument('--rootnet-backbone', choices=('resnet34', 'convnext'), default=None,
                     help="the SAR backbone of the RootNet checkpoint (rgb_opt.backbone / rgb_opt.in_channels: 512 / 1024); "
                          "default: the config's (resnet34)")
+    _tta_args(ap)
     _precise_hamer_args(ap)
     _antialias_args(ap)
     _render_args(ap)
@@ -73,6 +74,7 @@ def main(argv=None):
     keypoint_kw = render_keypoint_args(ap, args)
     apply_precise_args(args)
     apply_antialias_args(args)
+    apply_tta_args(args)
     apply_rootnet_backbone(args)
     k_real = load_intrinsics(args.intrinsics)
     hamer = hamer_inference(hamer_opt)

@@ -2,7 +2,7 @@
 
     python -m hamer_yolo_amd.evaluate_det --pred DIR --labels DIR [--size W H] [--json out.json]
     python -m hamer_yolo_amd.evaluate_det --images DIR --labels DIR [--weights W] [--precise-detector]
-                                          [--protocol {deployed,test}] [--multi-label]
+                                          [--protocol {deployed,test}] [--multi-label] [--augment]
                                           [--conf-thres C] [--iou-thres I] [--save-txt DIR [--save-conf]]
                                           [--det-frames N] [--json out.json]
 
@@ -21,9 +21,10 @@ only, NMS as configured there).  A PR curve cut at conf 0.25 ends early, so that
 the same weights.  ``--protocol test`` is test.py's own (test.py:125): conf 0.001, IoU 0.65, multi-label candidates, class-aware
 NMS over all classes, 300 boxes per image, then the same matching and AP; the whole pass goes through one hm_yolo_nms_batch
 call.  An explicit ``--conf-thres`` / ``--iou-thres`` still wins, and ``--multi-label`` alone adds the multi-label branch to the
-deployed thresholds.  Not reproduced from test.py: its dataloader's letterbox (``rect``, pad 0.5) -- the detector's own
-letterbox is used -- ``--augment``, ``--single-cls``, ``--save-hybrid`` and the COCO JSON.  The table says which protocol and
-thresholds it was made with.
+deployed thresholds.  ``--augment`` (test.py's name, either protocol) runs the detector with test-time augmentation
+(``Detector(tta=True)``: scales 1, 0.83 mirrored, 0.67 and one NMS, yolo.py:589-605).  Not reproduced from test.py: its
+dataloader's letterbox (``rect``, pad 0.5) -- the detector's own letterbox is used -- ``--single-cls``, ``--save-hybrid`` and
+the COCO JSON, and ``--augment`` unless it is given.  The table says which protocol and thresholds it was made with.
 """
 from __future__ import annotations
 
@@ -112,7 +113,7 @@ def score_images(image_dir: str, label_dir: str, detector, save_txt: Optional[st
     ``det_frames``) and score every pass on the device against the label files of ``label_dir``.  ``save_txt``: also write the
     predictions, one file per image, in the label format (this copies each pass's boxes to the host).  ``multi_label``: the
     reference's multi-label NMS branch (the pass then goes through one hm_yolo_nms_batch call); ``agnostic``: None reads
-    ``detector.opt.agnostic_nms``; ``protocol`` is recorded in the result."""
+    ``detector.opt.agnostic_nms``; ``protocol`` is recorded in the result, and so is the detector's ``tta`` as ``augment``."""
     import torch
     from .infer import _imread_bgr, _list_images
     from .yolo import metrics as M
@@ -148,7 +149,7 @@ def score_images(image_dir: str, label_dir: str, detector, save_txt: Optional[st
             continue
         H, W = run[0][1].shape[:2]
         frames = torch.from_numpy(np.stack([im for _, im in run])).to(detector.device)
-        p = eng.forward(list(frames))
+        p = eng.forward(list(frames), tta=bool(getattr(detector, "tta", False)))
         eng.nms_enqueue(p, opt.conf_thres, opt.iou_thres, opt.classes, agnostic, scale=True, multi_label=bool(multi_label))
         g = np.array([W, H, W, H], np.float32)
         T = [M.load_label_file(labels[s]) if s in labels else np.zeros((0, 5), np.float32) for s, _ in run]
@@ -167,7 +168,7 @@ def score_images(image_dir: str, label_dir: str, detector, save_txt: Optional[st
     result = _result_dict(ev.result(), list(eng.names),
                           {"only_labels": only_labels, "unreadable": unreadable, "conf_thres": float(opt.conf_thres),
                            "iou_thres": float(opt.iou_thres), "precise": bool(detector.precise), "protocol": str(protocol),
-                           "multi_label": bool(multi_label), "agnostic": agnostic})
+                           "multi_label": bool(multi_label), "agnostic": agnostic, "augment": bool(getattr(detector, "tta", False))})
     if json_path:
         with open(json_path, "w") as f:
             json.dump(result, f, indent=1)
@@ -186,6 +187,8 @@ def _parser() -> argparse.ArgumentParser:
                     help="--images: deployed = the thresholds and NMS of config/yolo_config.py; test = test.py's: conf 0.001, IoU 0.65, "
                          "multi-label, class-aware, all classes")
     ap.add_argument('--multi-label', action='store_true', help="--images: one candidate per (box, class) above the threshold (implied by --protocol test)")
+    ap.add_argument('--augment', action='store_true',
+                    help="--images: test-time augmentation in the detector (scales 1, 0.83 mirrored, 0.67; one NMS), about 2.2x the detector time")
     ap.add_argument('--conf-thres', type=float, default=None, help="--images: default the protocol's (deployed: yolo_opt.conf_thres; test: 0.001)")
     ap.add_argument('--iou-thres', type=float, default=None, help="--images: NMS IoU, default the protocol's (deployed: yolo_opt.iou_thres; test: 0.65)")
     ap.add_argument('--save-txt', type=str, default=None, help="--images: also write the predictions to this folder in the label format")
@@ -214,18 +217,24 @@ def main(argv=None):
             yolo_opt.conf_thres = args.conf_thres
         if args.iou_thres is not None:
             yolo_opt.iou_thres = args.iou_thres
-        result = score_images(args.images, args.labels, Detector(yolo_opt, precise=True if args.precise_detector else None),
+        result = score_images(args.images, args.labels, Detector(yolo_opt, precise=True if args.precise_detector else None,
+                                                                        tta=True if args.augment else None),
                               args.save_txt, args.save_conf, args.json, args.det_frames, multi_label=test or args.multi_label,
                               agnostic=False if test else None, protocol=args.protocol)
         if test:
             note = (f"protocol test: conf_thres {result['conf_thres']:g}, iou_thres {result['iou_thres']:g}, multi-label, class-aware NMS "
                     "over all classes, 300 boxes per image, test.py's matching and AP.  Not reproduced: test.py's dataloader "
-                    "letterbox (rect, pad 0.5; the detector's own letterbox is used), --augment, --single-cls, --save-hybrid, COCO JSON")
+                    "letterbox (rect, pad 0.5; the detector's own letterbox is used), "
+                    + ("" if result["augment"] else "--augment, ") + "--single-cls, --save-hybrid, COCO JSON")
+            if result["augment"]:
+                note += ".  --augment: scales 1, 0.83 (mirrored), 0.67 into one NMS"
         else:
             note = (f"conf_thres {result['conf_thres']:g}, iou_thres {result['iou_thres']:g} (the deployed defaults are 0.25 / 0.35; "
                     "test.py's are 0.001 / 0.65 -- a PR curve cut at a higher confidence gives a lower mAP)")
             if args.multi_label:
                 note += "; multi-label candidates"
+            if result["augment"]:
+                note += "; --augment: scales 1, 0.83 (mirrored), 0.67 into one NMS"
     print(format_table(result))
     print(note)
     for s in result["only_labels"]:

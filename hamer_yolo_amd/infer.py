@@ -1118,10 +1118,24 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument('--yolo-weights', type=str, default=None, help="yolov7 .pt path or synthetic:<seed> (default: config/yolo_config.py)")
     ap.add_argument('--precise-detector', action='store_true',
                     help="run YOLOv7 in fp32 (the reference's CPU branch) instead of fp16: its boxes, at about twice the detector time")
+    _tta_args(ap)
     _precise_hamer_args(ap)
     _antialias_args(ap)
     _render_args(ap)
     return ap
+
+
+def _tta_args(ap: argparse.ArgumentParser) -> None:
+    ap.add_argument('--tta-detector', action='store_true',
+                    help="test-time augmentation in the detector (the reference model's forward(augment=True)): YOLOv7 at scales 1, "
+                         "0.83 (mirrored) and 0.67 and one NMS over all three, at about 2.2x the detector time; off by default")
+
+
+def apply_tta_args(args) -> None:
+    """``--tta-detector`` -> ``yolo_opt.tta``.  No precise switch implies it: it is another set of candidates, not a precision."""
+    if getattr(args, "tta_detector", False):
+        from .config.yolo_config import yolo_opt
+        yolo_opt.tta = True
 
 
 def _antialias_args(ap: argparse.ArgumentParser) -> None:
@@ -1201,6 +1215,7 @@ def main(argv=None):
         yolo_opt.weights = args.yolo_weights
     apply_precise_args(args)
     apply_antialias_args(args)
+    apply_tta_args(args)
     # under `python -m torch.distributed.run --nproc-per-node N -m hamer_yolo_amd.infer ...` every rank takes its share of
     # the folder on its own GPU (RANK / LOCAL_RANK / WORLD_SIZE from the environment); a plain launch is one process
     from . import shard

@@ -44,6 +44,7 @@ EXPORTS = [
     "hm_skeleton_overlay_workspace_bytes", "hm_skeleton_overlay",
     "hm_det_match", "hm_det_ap_workspace_bytes", "hm_det_ap", "hm_det_ap_curve",
     "hm_nms_batch_workspace_bytes", "hm_yolo_nms_batch",
+    "hm_tta_sizes", "hm_tta_tables", "hm_tta_scale", "hm_yolo_decode_batch_tta",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -227,6 +228,10 @@ def load() -> C.CDLL:
     lib.hm_letterbox_batch.argtypes = [vp, C.c_size_t, i, C.POINTER(LetterboxPlan), vp, vp, i, vp]
     lib.hm_yolo_decode.argtypes = [vp, i, vp, i, i, i, i, f, C.POINTER(C.c_float), vp]
     lib.hm_yolo_decode_batch.argtypes = [vp, i, vp, i, i, i, i, f, C.POINTER(C.c_float), i, C.c_size_t, vp]
+    lib.hm_tta_sizes.argtypes = [i, i, d, i, C.POINTER(C.c_int)]
+    lib.hm_tta_tables.argtypes = [i, i, d, i, i, C.POINTER(C.c_int32)]
+    lib.hm_tta_scale.argtypes = [vp, vp, vp, i, i, i, d, i, i, vp]
+    lib.hm_yolo_decode_batch_tta.argtypes = [vp, i, vp, i, i, i, i, f, C.POINTER(C.c_float), i, C.c_size_t, f, i, f, vp]
     lib.hm_nms_workspace_bytes.argtypes = [i]
     lib.hm_nms_workspace_bytes.restype = C.c_size_t
     lib.hm_yolo_nms.argtypes = [vp, i, i, f, f, C.c_uint, i, i, C.POINTER(LetterboxPlan), vp, vp, vp, C.c_size_t, vp]

@@ -407,3 +407,59 @@ def det_ap_curve(recall: torch.Tensor, precision: torch.Tensor, x101: torch.Tens
     L.check(L.load().hm_det_ap_curve(L.ptr(recall), L.ptr(precision), n, L.ptr(x101), int(bool(v5_metric)), L.ptr(ap),
                                      L.ptr(mpre), L.ptr(mrec), L.current_stream()), "hm_det_ap_curve")
     return ap, mpre, mrec
+
+
+# ----------------------------------------------------------------------------- detector test-time augmentation (csrc/tta.hip)
+_DT_TTA = {torch.bfloat16: L.HM_DTYPE_BF16, torch.float16: L.HM_DTYPE_F16, torch.float32: L.HM_DTYPE_F32}
+
+
+def tta_sizes(h: int, w: int, ratio: float, gs: int = 32):
+    """hm_tta_sizes: scale_img's (resized h, resized w, padded h, padded w) for an h x w network input."""
+    sz = (C.c_int * 4)()
+    L.check(L.load().hm_tta_sizes(int(h), int(w), float(ratio), int(gs), sz), "hm_tta_sizes")
+    return tuple(sz)
+
+
+def tta_tables(h: int, w: int, ratio: float, gs: int = 32, flip_lr: bool = False) -> torch.Tensor:
+    """hm_tta_tables: the tap table of one scale as an int32 host tensor of 4 * wp + 4 * hp entries (tap0 | tap1 | weight0 |
+    weight1 for the columns, then for the rows; the weights are fp32 bits)."""
+    _, _, hp, wp = tta_sizes(h, w, ratio, gs)
+    tab = (C.c_int32 * (4 * wp + 4 * hp))()
+    L.check(L.load().hm_tta_tables(int(h), int(w), float(ratio), int(gs), int(bool(flip_lr)), tab), "hm_tta_tables")
+    return torch.frombuffer(bytearray(bytes(tab)), dtype=torch.int32).clone()
+
+
+def tta_scale(x: torch.Tensor, ratio: float, gs: int = 32, flip_lr: bool = False, tab: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """hm_tta_scale.  x (nb, h, w, 8) fp16 / bf16 / fp32 on the device, channels 0-2 the image -> (nb, hp, wp, 8): mirrored
+    when ``flip_lr``, resized by ``ratio`` and padded with 0.447 to multiples of ``gs``.  ``tab``: tta_tables' tensor on the
+    device (built and uploaded here when None)."""
+    _dev(x, tab)
+    if x.dim() != 4 or x.shape[3] != 8 or x.dtype not in _DT_TTA or not x.is_contiguous():
+        raise ValueError(f"tta_scale: expected a contiguous (nb, h, w, 8) fp16 / bf16 / fp32 tensor, got {x.dtype} {tuple(x.shape)}")
+    nb, h, w, _ = x.shape
+    _, _, hp, wp = tta_sizes(h, w, ratio, gs)
+    if tab is None:
+        tab = tta_tables(h, w, ratio, gs, flip_lr).to(x.device)
+    _chk(tab, torch.int32, (4 * wp + 4 * hp,), "tta_scale: tab")
+    y = torch.empty(nb, hp, wp, 8, dtype=x.dtype, device=x.device)
+    L.check(L.load().hm_tta_scale(L.ptr(x), L.ptr(y), L.ptr(tab), nb, h, w, float(ratio), int(gs), _DT_TTA[x.dtype], L.current_stream()),
+            "hm_tta_scale")
+    return y
+
+
+def yolo_decode_batch_tta(raw: torch.Tensor, pred: torch.Tensor, row0: int, ny: int, nx: int, nc: int, stride: float, anchors6,
+                          nb: int, pred_rows_per_image: int, scale: float, flip_lr: bool, full_w: float) -> None:
+    """hm_yolo_decode_batch_tta: raw (nb * ny * nx, 3 * (5 + nc)) fp32 of one level -> rows [row0, row0 + 3 * ny * nx) of every
+    image's ``pred_rows_per_image`` rows of pred (.., 5 + nc) fp32, xywh divided by ``scale`` and x mirrored in ``full_w``
+    when ``flip_lr``."""
+    _dev(raw, pred)
+    no = 5 + nc
+    _chk(raw, torch.float32, (nb * ny * nx, 3 * no), "yolo_decode_batch_tta: raw")
+    if pred.dtype != torch.float32 or not pred.is_contiguous() or pred.shape[-1] != no or row0 < 0 or \
+            row0 + 3 * ny * nx > pred_rows_per_image or pred.numel() < nb * pred_rows_per_image * no:
+        raise ValueError("yolo_decode_batch_tta: pred must be contiguous fp32 (.., 5 + nc) with nb * pred_rows_per_image rows, "
+                         "the level's rows inside an image's")
+    anc = (C.c_float * 6)(*[float(v) for v in anchors6])
+    L.check(L.load().hm_yolo_decode_batch_tta(L.ptr(raw), 3 * no, L.ptr(pred), int(row0), ny, nx, nc, float(stride), anc, nb,
+                                              int(pred_rows_per_image), float(scale), int(bool(flip_lr)), float(full_w),
+                                              L.current_stream()), "hm_yolo_decode_batch_tta")

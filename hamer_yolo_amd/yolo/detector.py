@@ -6,7 +6,9 @@ device, save_path}`` (config/yolo_config.py:4-13); ``detect(image)`` takes an Hx
 ``dets_list`` a list with one list of ``[label, [x1, y1, x2, y2]]``, label 'right' iff cls == 1
 (detector.py:144-147).  ``Detector(config, precise=True)`` (default: ``config.precise``, else False) runs the network in
 fp32 -- the reference's CPU branch (detector.py:110-112, ``half = False``) -- instead of its GPU branch's fp16.  ``augment`` is ignored exactly as in the reference (TracedModel.forward drops it,
-utils/torch_utils.py:371-374).  Everything between the frame upload and the box list is HIP
+utils/torch_utils.py:371-374).  ``Detector(config, tta=True)`` (default: ``config.tta``, else False) is the switch that does
+augment: ``Model.forward(x, augment=True)`` (yolo.py:589-605), the network at scales 1, 0.83 (mirrored) and 0.67 of the
+letterboxed input and one NMS over all three predictions, on either route.  Everything between the frame upload and the box list is HIP
 (letterbox, 92 implicit-GEMM convolutions, pooling, decode, NMS, scale_coords).
 """
 from __future__ import annotations
@@ -70,9 +72,11 @@ class _Model:
 
 
 class Detector():
-    def __init__(self, config, precise=None):
+    def __init__(self, config, precise=None, tta=None):
         """precise: None reads ``getattr(config, "precise", False)``; True runs the fp32 route (YoloEngine dtype torch.float32:
-        the reference's CPU-branch arithmetic, boxes equal to its fp32 detector's), False the default fp16 route."""
+        the reference's CPU-branch arithmetic, boxes equal to its fp32 detector's), False the default fp16 route.
+        tta: None reads ``getattr(config, "tta", False)``; True runs every pass with test-time augmentation (about 2.2x the
+        detector time); ``config.augment`` does not turn it on."""
         weights, imgsz, self.device = config.weights, config.imgsz, config.device
         self.device = torch.device(self.device if torch.cuda.is_available() else 'cpu')
         if self.device.type != 'cuda':
@@ -81,6 +85,7 @@ class Detector():
         stride = 32
         self.imgsz = int(np.ceil(imgsz / stride) * stride)               # check_img_size, general.py:126-131
         self.precise = bool(getattr(config, "precise", False) if precise is None else precise)
+        self.tta = bool(getattr(config, "tta", False) if tta is None else tta)
         self.engine = YoloEngine(sd, nc=nc, device=self.device, dtype=torch.float32 if self.precise else torch.float16,
                                  new_shape=self.imgsz, stride=stride, names=names)
         self.model = _Model(self.engine)
@@ -95,7 +100,7 @@ class Detector():
     def detect(self, image: np.ndarray):
         opt = self.opt
         frame = torch.from_numpy(np.ascontiguousarray(image)).to(self.device)
-        p = self.engine.forward(frame)
+        p = self.engine.forward(frame, tta=self.tta)
         det = self.engine.nms(p, opt.conf_thres, opt.iou_thres, opt.classes, opt.agnostic_nms, scale=True)
         return [det], [self._labelled(det.tolist())]
 
@@ -106,7 +111,7 @@ class Detector():
         on the current stream, no host sync.  The plan's device buffers are shared by every pass of that shape, so a later
         pass on the same stream may overwrite them; the host copy is what ``detect_frames_finish`` reads."""
         opt = self.opt
-        p = self.engine.forward(list(frames))
+        p = self.engine.forward(list(frames), tta=self.tta)
         self.engine.nms_enqueue(p, opt.conf_thres, opt.iou_thres, opt.classes, opt.agnostic_nms, scale=True)
         nb = p["nb"]
         counts = torch.empty(nb, dtype=torch.int32, pin_memory=True)
@@ -133,7 +138,7 @@ class Detector():
         NMS launch per frame, ONE host transfer for all box lists.  Returns (preds, dets_lists) with one entry per frame, each
         as ``detect`` returns it for a single image."""
         opt = self.opt
-        p = self.engine.forward(list(frames))
+        p = self.engine.forward(list(frames), tta=self.tta)
         self.engine.nms_enqueue(p, opt.conf_thres, opt.iou_thres, opt.classes, opt.agnostic_nms, scale=True)
         counts = p["count"].tolist()                                   # the only host sync of the chunk
         dets = p["dets"].reshape(p["nb"], 300, 6)

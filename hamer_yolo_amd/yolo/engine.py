@@ -8,6 +8,8 @@ Plan time (host, once per letterboxed size): every tensor gets a home in an NHWC
 that feeds a Concat lives directly in a channel slice of the concat's buffer, so Concat costs
 nothing (reference: Model.forward_once, yolo.py:609-639, copies on every torch.cat).
 Run time: hm_letterbox -> hm_yolo_run (one enqueue for ~110 kernels) -> 3 x hm_yolo_decode -> hm_yolo_nms.
+Test-time augmentation (``forward(frames, tta=True)``, opt-in): hm_letterbox -> 2 x hm_tta_scale -> 3 x (hm_yolo_run -> 3 x
+hm_yolo_decode_batch_tta) -> the same NMS over the three scales' rows (Model.forward(x, augment=True), yolo.py:589-605).
 """
 from __future__ import annotations
 
@@ -82,26 +84,19 @@ class YoloEngine:
         self.fuse_stem = not f32      # Conv 0 + Conv 1 as one launch, the 32-channel full-size map never written (round 4); False: two launches
 
     # ------------------------------------------------------------------ planning
-    def _plan(self, H: int, W: int, nb: int = 1) -> dict:
-        """Plan for `nb` frames of size HxW processed as one batch (every conv launch covers all of them)."""
-        key = (H, W, nb)
-        if key in self._plans:
-            self._plans[key] = self._plans.pop(key)           # (most recently used last)
-            return self._plans[key]
-        self._evict_plans()
-        lib = self.lib
-        lp = L.LetterboxPlan()
-        L.check(lib.hm_letterbox_plan_make(H, W, self.new_shape, self.stride, C.byref(lp)), "hm_letterbox_plan_make")
-        tab = (C.c_int32 * (3 * lp.new_w + 3 * lp.new_h))()
-        L.check(lib.hm_letterbox_tables(C.byref(lp), tab), "hm_letterbox_tables")
-        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.int32).clone().to(self.device)
+    # Model.forward(x, augment=True), yolo.py:592-593: the scales and which of them is mirrored left-right
+    TTA_SCALES = (1.0, 0.83, 0.67)
+    TTA_FLIPS = (False, True, False)
 
+    def _graph_layout(self, in_h: int, in_w: int, nb: int) -> dict:
+        """Where every tensor of the graph lives for `nb` network inputs of in_h x in_w: spatial size per layer, homes
+        (buffer id, channel offset, ld) and buffer sizes in elements."""
         layers = arch.resolve(self.layers)
         ch = arch.channels(self.layers, 3, self.nc)
         # spatial size per layer
         hw: List[Tuple[int, int]] = []
         for i, (srcs, kind, args) in enumerate(layers):
-            h, w = (lp.out_h, lp.out_w) if srcs[0] < 0 else hw[srcs[0]]
+            h, w = (in_h, in_w) if srcs[0] < 0 else hw[srcs[0]]
             if kind == "conv" and args[2] == 2:
                 h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1      # k3 s2 p1
             elif kind == "mp":
@@ -128,7 +123,7 @@ class YoloEngine:
                 sizes[i] = nb * hw[i][0] * hw[i][1] * ch[i]
         # extra buffers: image (8 ch), SPPCSPC internals, detect raw maps (f32)
         IMG = -1
-        sizes[IMG] = nb * lp.out_h * lp.out_w * 8
+        sizes[IMG] = nb * in_h * in_w * 8
         home[IMG] = (IMG, 0, 8)
         spp_i = next(i for i, (_, kind, _) in enumerate(layers) if kind == "sppcspc")
         c_ = layers[spp_i][2][0]
@@ -136,12 +131,23 @@ class YoloEngine:
         spp = {"t1": 1000, "t3": 1001, "cat4": 1002, "t5": 1003, "cat2": 1004}
         for nm, cc in (("t1", c_), ("t3", c_), ("cat4", 4 * c_), ("t5", c_), ("cat2", 2 * c_)):
             sizes[spp[nm]] = nb * sh * sw * cc
+        return {"layers": layers, "ch": ch, "hw": hw, "home": home, "sizes": sizes, "spp": spp, "c_": c_, "in_hw": (in_h, in_w)}
+
+    def _offsets(self, sizes: Dict[int, int], skip=()) -> Tuple[Dict[int, int], int]:
+        """Byte offset of every buffer, one after another, each rounded up to 256 bytes; and the total."""
         offs, total = {}, 0
         for b, n in sizes.items():
+            if b in skip:
+                continue
             offs[b] = total
             total += (n * self.esz + 255) // 256 * 256
-        arena = torch.zeros(total, dtype=torch.uint8, device=self.device)
-        base = arena.data_ptr()
+        return offs, total
+
+    def _graph_ops(self, g: dict, nb: int, base: int, offs: Dict[int, int]):
+        """The op list of one laid-out graph (buffer b at base + offs[b]) and its detect raw maps [(raw, ny, nx)] x 3."""
+        layers, ch, hw, home, spp, c_ = g["layers"], g["ch"], g["hw"], g["home"], g["spp"], g["c_"]
+        in_h, in_w = g["in_hw"]
+        IMG = -1
         esz = self.esz
 
         def addr(buf, ch_off=0):
@@ -217,7 +223,7 @@ class YoloEngine:
                 continue
             s0 = srcs[0] if srcs[0] >= 0 else IMG
             xptr, ldx = loc(s0)
-            h, w = (lp.out_h, lp.out_w) if s0 == IMG else hw[s0]
+            h, w = (in_h, in_w) if s0 == IMG else hw[s0]
             if kind == "conv":
                 yptr, ldy = loc(i)
                 if readers.get(i, 0) == 1 and home[i][0] == i:
@@ -254,26 +260,80 @@ class YoloEngine:
                     raws.append((raw, hh, ww))
                     conv(f"model.{i}.m.{l}", xp, ldxx, hh, ww, raw.data_ptr(), 3 * self.no, act=0, out_f32=1)
         flush()
+        return ops, raws
+
+    def _plan(self, H: int, W: int, nb: int = 1, tta: bool = False) -> dict:
+        """Plan for `nb` frames of size HxW processed as one batch (every conv launch covers all of them).  ``tta``: the plan
+        of the test-time-augmented pass (its own cache entry): the full-size graph laid out exactly as in the plain plan, then
+        one graph per further scale of TTA_SCALES -- its image buffer behind the full-size graph's buffers (hm_tta_scale
+        fills it from the full-size image BEFORE any graph runs, so no graph may overwrite it), its other buffers over the
+        full-size graph's, which is free by the time it runs: the launches are serial and the head maps live outside the
+        arena."""
+        key = (H, W, nb, "tta") if tta else (H, W, nb)
+        if key in self._plans:
+            self._plans[key] = self._plans.pop(key)           # (most recently used last)
+            return self._plans[key]
+        self._evict_plans()
+        lib = self.lib
+        lp = L.LetterboxPlan()
+        L.check(lib.hm_letterbox_plan_make(H, W, self.new_shape, self.stride, C.byref(lp)), "hm_letterbox_plan_make")
+        tab = (C.c_int32 * (3 * lp.new_w + 3 * lp.new_h))()
+        L.check(lib.hm_letterbox_tables(C.byref(lp), tab), "hm_letterbox_tables")
+        tab_dev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.int32).clone().to(self.device)
+
+        IMG = -1
+        g = self._graph_layout(lp.out_h, lp.out_w, nb)
+        offs, total = self._offsets(g["sizes"])
+        scaled = []                                            # TTA: (ratio, flip, sizes4, layout, offsets) per further scale
+        if tta:
+            for ratio, flip in list(zip(self.TTA_SCALES, self.TTA_FLIPS))[1:]:
+                sz = (C.c_int * 4)()
+                L.check(lib.hm_tta_sizes(lp.out_h, lp.out_w, ratio, self.stride, sz), "hm_tta_sizes")
+                gk = self._graph_layout(sz[2], sz[3], nb)
+                offk, totk = self._offsets(gk["sizes"], skip=(IMG,))
+                assert totk <= total, "a scaled graph fits over the full-size graph's buffers"
+                offk[IMG] = total
+                total += (gk["sizes"][IMG] * self.esz + 255) // 256 * 256
+                scaled.append((ratio, flip, tuple(sz), gk, offk))
+        arena = torch.zeros(total, dtype=torch.uint8, device=self.device)
+        base = arena.data_ptr()
+        ops, raws = self._graph_ops(g, nb, base, offs)
+        graphs = [(ops, raws)]
+        for ratio, flip, sz, gk, offk in scaled:
+            graphs.append(self._graph_ops(gk, nb, base, offk))
         # split-K scratch (hm_conv_args.splitk_ws), shared by the plan's layers (they run one after another): the library says
         # how much each convolution needs (its rule looks at one image's output, so results do not depend on nb)
-        ws_bytes = max([self.lib.hm_conv_splitk_bytes(C.byref(op.conv)) for op in ops if op.kind == 0] + [0]) if self.split_k else 0
+        all_ops = [op for gops, _ in graphs for op in gops]
+        ws_bytes = max([self.lib.hm_conv_splitk_bytes(C.byref(op.conv)) for op in all_ops if op.kind == 0] + [0]) if self.split_k else 0
         splitk_ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=self.device)
         if ws_bytes:
-            for op in ops:
+            for op in all_ops:
                 if op.kind == 0:
                     op.conv.splitk_ws, op.conv.splitk_ws_bytes = splitk_ws.data_ptr(), ws_bytes
         op_arr = (L.YoloOp * len(ops))(*ops)
-        n_pred = sum(3 * hh * ww for _, hh, ww in raws)
+        n_pred = sum(3 * hh * ww for gops, graws in graphs for _, hh, ww in graws)
         plan = {
-            "lp": lp, "tab": tab_dev, "arena": arena, "img_ptr": addr(IMG), "ops": op_arr, "n_ops": len(ops), "raws": raws,
+            "lp": lp, "tab": tab_dev, "arena": arena, "img_ptr": base + offs[IMG], "ops": op_arr, "n_ops": len(ops), "raws": raws,
             "nb": nb, "n_pred": n_pred,
             "pred": torch.empty(nb * n_pred, self.no, dtype=torch.float32, device=self.device),
             "dets": torch.zeros(nb * 300, 6, dtype=torch.float32, device=self.device),
             "count": torch.zeros(nb, dtype=torch.int32, device=self.device),
             "nms_ws": torch.empty(self.lib.hm_nms_workspace_bytes(n_pred), dtype=torch.uint8, device=self.device),
             "u8": torch.empty(3, lp.out_h, lp.out_w, dtype=torch.uint8, device=self.device),
-            "home": home, "hw": hw, "ch": ch, "offs": offs, "splitk_ws": splitk_ws,
+            "home": g["home"], "hw": g["hw"], "ch": g["ch"], "offs": offs, "splitk_ws": splitk_ws,
         }
+        if tta:
+            # one entry per scale, in the order of the pred rows; the full-size one carries no table (nothing to resize)
+            row0 = sum(3 * hh * ww for _, hh, ww in raws)
+            plan["tta"] = [{"ratio": 1.0, "flip": False, "h": lp.out_h, "w": lp.out_w, "ops": op_arr, "n_ops": len(ops), "raws": raws,
+                            "row0": 0, "img_ptr": plan["img_ptr"], "tab": None}]
+            for (ratio, flip, sz, gk, offk), (kops, kraws) in zip(scaled, graphs[1:]):
+                ktab = (C.c_int32 * (4 * sz[3] + 4 * sz[2]))()
+                L.check(lib.hm_tta_tables(lp.out_h, lp.out_w, ratio, self.stride, int(flip), ktab), "hm_tta_tables")
+                plan["tta"].append({"ratio": ratio, "flip": flip, "h": sz[2], "w": sz[3], "ops": (L.YoloOp * len(kops))(*kops),
+                                    "n_ops": len(kops), "raws": kraws, "row0": row0, "img_ptr": base + offk[IMG],
+                                    "tab": torch.frombuffer(bytearray(bytes(ktab)), dtype=torch.int32).clone().to(self.device)})
+                row0 += sum(3 * hh * ww for _, hh, ww in kraws)
         self._plans[key] = plan
         return plan
 
@@ -312,15 +372,18 @@ class YoloEngine:
                                       self.dt, p["u8"].data_ptr() if want_u8 else None, L.current_stream()), "hm_letterbox")
         return p
 
-    def forward(self, frame, want_u8: bool = False) -> dict:
+    def forward(self, frame, want_u8: bool = False, tta: bool = False) -> dict:
         """frame: (H, W, 3) uint8 BGR device tensor, or a list of equally sized frames (one batched pass).
-        Returns the plan dict with ``pred`` (nb * n, 5+nc) filled, image i in rows [i*n, (i+1)*n)."""
+        Returns the plan dict with ``pred`` (nb * n, 5+nc) filled, image i in rows [i*n, (i+1)*n).
+        ``tta``: the test-time-augmented pass (Model.forward(x, augment=True), yolo.py:589-605): one letterbox, the network at
+        scales 1, 0.83 (mirrored) and 0.67 of the letterboxed input, every prediction de-scaled and de-flipped, image i's
+        rows in the order of the scales -- ``n_pred`` is their sum, and NMS takes the plan as it takes a plain one."""
         frames = list(frame) if isinstance(frame, (list, tuple)) else [frame]
         for f in frames:
             if not f.is_cuda or f.dtype != torch.uint8 or f.shape != frames[0].shape:
                 raise L.HipLibraryError("YoloEngine.forward takes uint8 device frames of one size")
         H, W, _ = frames[0].shape
-        p = self._plan(H, W, len(frames))
+        p = self._plan(H, W, len(frames), tta=bool(tta))
         # frames that are equally spaced slices of one device tensor (the folder drivers upload a chunk as one tensor): ONE
         # letterbox launch for the pass; otherwise one per frame
         nb = len(frames)
@@ -334,6 +397,8 @@ class YoloEngine:
             for i, f in enumerate(frames):
                 self.letterbox(f.contiguous(), want_u8 and len(frames) == 1, p, i)
         st = L.current_stream()
+        if tta:
+            return self._forward_tta(p, st)
         L.check(self.lib.hm_yolo_run(p["ops"], p["n_ops"], st), "hm_yolo_run")
         row0 = 0
         for l, (raw, hh, ww) in enumerate(p["raws"]):        # one decode launch per level for all images of the pass
@@ -341,6 +406,24 @@ class YoloEngine:
             L.check(self.lib.hm_yolo_decode_batch(raw.data_ptr(), 3 * self.no, p["pred"].data_ptr(), row0, hh, ww, self.nc,
                                                   float(arch.STRIDES[l]), anc, p["nb"], p["n_pred"], st), "hm_yolo_decode_batch")
             row0 += 3 * hh * ww
+        return p
+
+    def _forward_tta(self, p: dict, st) -> dict:
+        """The rest of a TTA pass after the letterbox: the resizes first -- they read the full-size image, which lives in the
+        arena the graphs write -- then a graph and three decode launches per scale."""
+        lib, lp = self.lib, p["lp"]
+        for t in p["tta"][1:]:
+            L.check(lib.hm_tta_scale(p["img_ptr"], t["img_ptr"], t["tab"].data_ptr(), p["nb"], lp.out_h, lp.out_w, t["ratio"],
+                                     self.stride, self.dt, st), "hm_tta_scale")
+        for t in p["tta"]:
+            L.check(lib.hm_yolo_run(t["ops"], t["n_ops"], st), "hm_yolo_run")
+            row0 = t["row0"]
+            for l, (raw, hh, ww) in enumerate(t["raws"]):
+                anc = (C.c_float * 6)(*self.anchors[l])
+                L.check(lib.hm_yolo_decode_batch_tta(raw.data_ptr(), 3 * self.no, p["pred"].data_ptr(), row0, hh, ww, self.nc,
+                                                     float(arch.STRIDES[l]), anc, p["nb"], p["n_pred"], t["ratio"], int(t["flip"]),
+                                                     float(lp.out_w), st), "hm_yolo_decode_batch_tta")
+                row0 += 3 * hh * ww
         return p
 
     def nms_enqueue(self, p: dict, conf_thres: float, iou_thres: float, classes: Optional[List[int]], agnostic: bool,

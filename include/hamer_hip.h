@@ -472,6 +472,44 @@ int hm_yolo_decode(const float* raw, int ldraw, float* pred, int row0, int ny, i
 int hm_yolo_decode_batch(const float* raw, int ldraw, float* pred, int row0, int ny, int nx, int nc, float stride,
                          const float* anchors, int nb, size_t pred_rows_per_image, void* stream);
 
+/* Test-time augmentation (csrc/tta.hip): Model.forward(x, augment=True), yolo.py:589-605.  For a letterboxed network input
+ * x of h x w, in [0,1] and RGB, the reference runs forward_once on scale_img(x, s) for s = 1, 0.83, 0.67 -- the 0.83 pass on
+ * x.flip(3), the left-right mirror -- divides each prediction's xywh by s, sets x = w - x on the mirrored pass, and
+ * concatenates the three predictions per image in that order for ONE non_max_suppression.  scale_img (utils/torch_utils.py:
+ * 247-257) with gs = the largest stride:
+ *   resized size   (sh, sw) = (int(h * s), int(w * s))                    in doubles, as Python
+ *   padded size    (hp, wp) = (ceil(h * s / gs) * gs, ceil(w * s / gs) * gs)
+ *   resize         F.interpolate(mode='bilinear', align_corners=False): along each axis, for output d < out,
+ *                  src = max(0, (in / out) * (d + 0.5) - 0.5) in fp32 -- in / out and d + 0.5 rounded, the multiply and
+ *                  subtract as one fused multiply-add, which is how torch's kernels evaluate it; tap0 = (int)src,
+ *                  tap1 = tap0 + (tap0 < in - 1), weight1 = src - tap0, weight0 = 1 - weight1
+ *   pad            right and bottom with 0.447 (F.pad) up to (hp, wp)
+ * 384 x 640 gives 384x640, 320x544 (resized 318x531) and 288x448 (257x428): 15120 + 10710 + 7938 = 33768 rows per image.
+ *
+ * hm_tta_sizes (host): sizes4 = {sh, sw, hp, wp}.
+ * hm_tta_tables (host): the taps of one plan, 4 * wp + 4 * hp int32 -- columns first:
+ *   tap0[wp] | tap1[wp] | weight0[wp] | weight1[wp] (fp32 bits), then the same four for the hp rows.
+ *   Outputs past the resized size are padding: taps -1, weights 0.  flip_lr folds the mirror into the column taps
+ *   (tap -> w - 1 - tap), so the mirrored image is never written.
+ * hm_tta_scale: x [nb][h][w][8] -> y [nb][hp][wp][8] in `dtype` (HM_DTYPE_F16, HM_DTYPE_BF16 or HM_DTYPE_F32), tab_dev the
+ *   table of hm_tta_tables for the same (h, w, ratio, gs) on the device.  Channels 0-2 are interpolated in fp32 from the
+ *   four taps (columns first, then rows) and rounded once to `dtype`; padding pixels get 0.447 rounded to `dtype`; channels
+ *   3-7 are 0.  x and y must not overlap.
+ * All three: HM_ERR_ARG, before any device work, for a null pointer, h, w or gs outside 1..16384, a ratio outside (0, 1] (or
+ *   NaN), a resized side of 0 pixels; hm_tta_scale also for nb outside 1..65535, an unknown dtype, x or y not aligned to one
+ *   pixel (16 bytes, 32 with HM_DTYPE_F32) or a table not aligned to 4 bytes. */
+int hm_tta_sizes(int h, int w, double ratio, int gs, int* sizes4);                                      /* host */
+int hm_tta_tables(int h, int w, double ratio, int gs, int flip_lr, int32_t* tab_host);                  /* host */
+int hm_tta_scale(const void* x, void* y, const int32_t* tab_dev, int nb, int h, int w, double ratio, int gs, int dtype,
+                 void* stream);
+/* hm_yolo_decode_batch for one scale of a TTA pass: the same decode (the same bits), then xywh = xywh / scale as an fp32
+ * IEEE division (torch divides; not a reciprocal multiply), then x = full_w - x when flip_lr (yolo.py:599-603).  The
+ * confidence and class columns are those of hm_yolo_decode_batch.  HM_ERR_ARG as hm_yolo_decode_batch, and for a scale outside
+ * (0, 1] or a flipped pass without a positive full_w. */
+int hm_yolo_decode_batch_tta(const float* raw, int ldraw, float* pred, int row0, int ny, int nx, int nc, float stride,
+                             const float* anchors, int nb, size_t pred_rows_per_image, float scale, int flip_lr, float full_w,
+                             void* stream);
+
 /* non_max_suppression (utils/general.py:611-703, best-class branch) + scale_coords/clip/round
  * (general.py:323-344, detector.py:142).  pred [n][5+nc] f32.  class_mask: bit c set = class c kept.
  * Workspace: hm_nms_workspace_bytes(n).  dets [max_det][6] f32 = x1,y1,x2,y2,conf,cls (score order),
