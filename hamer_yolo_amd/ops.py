@@ -222,6 +222,33 @@ def tome_merge(qkv: torch.Tensor, x: torch.Tensor, size: Optional[torch.Tensor],
     return xo, so, index.view(B, 3, -1), metric.view(B, tokens, head_dim)
 
 
+def tome_merge_metric(metric: torch.Tensor, lo_off: int, x: torch.Tensor, size: Optional[torch.Tensor], B: int, tokens: int, r: int,
+                      x_out: Optional[torch.Tensor] = None, size_out: Optional[torch.Tensor] = None,
+                      index: Optional[torch.Tensor] = None):
+    """hm_tome_merge_metric: matching on a given fp32 metric + size-weighted merge of the fp32 stream x (B*tokens, D).
+    metric: (B*tokens, >= 80) rows of any stride (taken from the tensor); lo_off > 0: the value is column d + column
+    lo_off + d.  x_out (>= B*(tokens-r), D), size_out (>= B*(tokens-r),) and index (B*3*96 int32) may be given (written in
+    place, further rows untouched).  Returns (x_out, size_out, index (B, 3, 96) = unm | src | dst)."""
+    _dev(metric, x, size, x_out, size_out, index)
+    D = x.shape[1]
+    rows = B * (tokens - r)
+    assert metric.dtype == torch.float32 and metric.dim() == 2 and metric.shape[0] == B * tokens and metric.stride(1) == 1
+    assert metric.shape[1] >= (lo_off + 80 if lo_off else 80)
+    assert x.shape[0] == B * tokens and x.dtype == torch.float32 and x.is_contiguous()
+    assert size is None or (size.shape == (B * tokens,) and size.dtype == torch.float32 and size.is_contiguous())
+    x_out = _out_rows(x_out, rows, D, torch.float32, x.device)
+    if size_out is None:
+        size_out = torch.empty(rows, device=x.device, dtype=torch.float32)
+    assert size_out.dim() == 1 and size_out.shape[0] >= rows and size_out.dtype == torch.float32 and size_out.is_contiguous()
+    words = L.load().hm_tome_index_bytes(B) // 4
+    if index is None:
+        index = torch.zeros(words, device=x.device, dtype=torch.int32)
+    assert index.numel() == words and index.dtype == torch.int32 and index.is_contiguous()
+    L.check(L.load().hm_tome_merge_metric(L.ptr(metric), metric.stride(0), lo_off, L.ptr(x), L.ptr(size), L.ptr(x_out), L.ptr(size_out),
+                                          L.ptr(index), B, tokens, r, D, L.current_stream()), "hm_tome_merge_metric")
+    return x_out, size_out, index.view(B, 3, -1)
+
+
 def patch_im2col(img: torch.Tensor, x0: int, win_w: int, patch: int, pad: int, dtype=torch.bfloat16) -> torch.Tensor:
     _dev(img)
     B, Cc, H, Wf = img.shape
@@ -233,13 +260,17 @@ def patch_im2col(img: torch.Tensor, x0: int, win_w: int, patch: int, pad: int, d
     return out
 
 
-def linear_f32(x: torch.Tensor, w: torch.Tensor, bias=None, resid=None, act: int = 0) -> torch.Tensor:
-    _dev(x, w, bias, resid)
+def linear_f32(x: torch.Tensor, w: torch.Tensor, bias=None, resid=None, act: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """hm_linear_f32: out (M,N) fp32 = act(x @ w.T + bias) (+ resid), act 1 = GELU; x (M,K), w (N,K), resid and out row-major
+    with any row stride.  out: optional buffer to write into (returned as given); it may be `resid` itself (x += ...)."""
+    _dev(x, w, bias, resid, out)
     M, K = x.shape
     N = w.shape[0]
-    out = torch.empty(M, N, device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty(M, N, device=x.device, dtype=torch.float32)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == torch.float32
     L.check(L.load().hm_linear_f32(L.ptr(x), x.stride(0), L.ptr(w), w.stride(0), L.ptr(bias), L.ptr(resid),
-                                   resid.stride(0) if resid is not None else 0, L.ptr(out), N, M, N, K, act,
+                                   resid.stride(0) if resid is not None else 0, L.ptr(out), out.stride(0), M, N, K, act,
                                    L.current_stream()), "hm_linear_f32")
     return out
 

@@ -301,6 +301,126 @@ def gemm_f32_shapes():
     return [(h * 192, N, K) for h in GEMM_F32_HANDS for (K, N) in GEMM_F32_KN] + GEMM_F32_RAGGED
 
 
+# ------------------------------------------------------------------------------------------------ hm_linear_f32
+# (M, N, K) of the decoder's small fp32 linear (csrc/decoder.hip: one 16 x 16 tile per workgroup, four waves splitting K in
+# 16-wide blocks, a 4-deep prefetch loop entered while kb + 192 < K).  PROD: what forward.hip launches for synth.HamerConfig().
+def linear_f32_prod():
+    cfg = synth.HamerConfig()
+    d, v = cfg.dec, cfg.vit
+    nk = sorted({(d.dim, d.dim), (d.inner, d.dim), (d.dim, d.inner), (d.mlp_dim, d.dim), (d.dim, d.mlp_dim)})
+    shapes = [(M, N, K) for (N, K) in nk for M in (1, 7, 64)]
+    shapes += [(M, 112, d.dim) for M in (1, 7, 64)]                                  # the 112-wide head, ldo = 112
+    shapes.append((2 * v.tokens, v.head_dim, v.embed_dim))                          # the token-merging metric, ldo = 80
+    return shapes
+
+
+LINEAR_F32_PROD = linear_f32_prod()
+# EDGE: every M in {1, 15, 16, 17, 33} (row clamp, second blockIdx.y), N in {4, 12, 20, 80, 112} (the n >= N guard inside a
+# tile; one lane group at 4) and K in {16, 48, 64, 208, 240, 256, 272, 464} at least twice.  K = 16: waves 1-3 add zeros; 48:
+# wave 3 adds nothing; 208: only wave 0 enters the prefetch loop; 240, 256: the waves enter it one by one, 256 is one round
+# and no tail; 272: a tail step for wave 0 after the round; 464: two rounds for waves 0 and 1.
+LINEAR_F32_M = [1, 15, 16, 17, 33]
+LINEAR_F32_N = [4, 12, 20, 80, 112]
+LINEAR_F32_K = [16, 48, 64, 208, 240, 256, 272, 464]
+LINEAR_F32_EDGE = [(1, 4, 16), (15, 12, 48), (16, 20, 64), (17, 80, 208), (33, 112, 240), (1, 12, 256), (15, 20, 272), (16, 80, 464),
+                   (17, 112, 16), (33, 4, 48), (1, 20, 64), (15, 80, 208), (16, 112, 240), (17, 4, 256), (33, 12, 272), (1, 80, 464),
+                   (15, 112, 16), (16, 4, 48), (17, 12, 64), (33, 20, 272), (33, 80, 256), (17, 20, 464)]
+# leading dimensions wider than the row: one shape of whole tiles, one ragged in M, N and K (both are in the lists above)
+LINEAR_F32_STRIDED = [(64, 512, 1024), (33, 20, 272)]
+
+
+# ------------------------------------------------------------------------------------------------ token merging
+# Metric rows whose bipartite matching is exact in fp32 whatever the summation order.  A token is +-m on c of the 80 channels,
+# m in {1, 2, 3, 5} and c in {4, 16, 64}: the squared norm m^2 c is an integer, the norm m sqrt(c) an integer, every normalised
+# value +-1 / sqrt(c) a power of two and every cosine a multiple of 1/64 of magnitude <= 1.  A token takes one of TOME_POOL
+# (sign pattern, channel order) pairs, its support being the first c channels of that order, with up to three hashed sign
+# flips inside the support: duplicates (cosine 1 whatever the magnitudes), near-duplicates and ties are plentiful.
+TOME_HD = 80
+TOME_POOL = 6
+TOME_MAGNITUDES = [1, 2, 3, 5]
+TOME_SUPPORTS = [4, 16, 64]
+TOME_B = 3
+TOME_D = [8, 320]
+TOME_EXACT = [(192, 16), (192, 96), (191, 95), (161, 14), (129, 1), (17, 4), (3, 1), (2, 1)]      # (T, r)
+# Goes into the seed of the case.  tests/test_exact_data_host.py states what the matching data must contain at every T >= 17
+# (distinct scores, tied maxima, a crowded and an empty B token, a tie across the merge boundary, norms that matter); these
+# are the first salts under which all of it holds.
+TOME_SALT = {17: 2}
+TOME_FILL = 3.0                           # what the columns around the metric hold in the wide layouts
+TOME_LAYOUTS = ("ld80", "ld96", "hi_lo")
+
+
+def tome_sizes_given(T):
+    return T != 192
+
+
+def tome_match_case(B, T, seed=0):
+    """(B, T, 80) fp32 metric of small integers as described above; element (b, t) is a hash of b * T + t, so no crop repeats
+    another."""
+    sd = _shape_seed(B, T, seed)
+    sign = 2 * ints("exact.tome.sign", (TOME_POOL, TOME_HD), 0, 1, sd) - 1
+    order = torch.argsort(ints("exact.tome.order", (TOME_POOL, TOME_HD), 0, 1 << 20, sd), dim=1, stable=True)
+    place = torch.argsort(order, dim=1)                                              # place[p, channel] = its position in order[p]
+    p = ints("exact.tome.pool", (B, T), 0, TOME_POOL - 1, sd).long()
+    c = torch.tensor(TOME_SUPPORTS)[ints("exact.tome.support", (B, T), 0, len(TOME_SUPPORTS) - 1, sd).long()]
+    m = torch.tensor(TOME_MAGNITUDES, dtype=torch.float32)[ints("exact.tome.magnitude", (B, T), 0, len(TOME_MAGNITUDES) - 1, sd).long()]
+    nflip = ints("exact.tome.nflip", (B, T), 0, 3, sd).long()
+    at = ints("exact.tome.flip", (B, T, 3), 0, 63, sd).long() % c[..., None]          # positions inside the support
+    s = sign[p].clone()                                                               # (B, T, 80)
+    for k in range(3):
+        ch = order[p].gather(2, at[..., k:k + 1])                                     # (B, T, 1) channel of flip k
+        flip = torch.where(nflip[..., None] > k, -1.0, 1.0)
+        s.scatter_(2, ch, s.gather(2, ch) * flip)
+    metric = m[..., None] * s * (place[p] < c[..., None])
+    assert metric.dtype == torch.float32 and metric.shape == (B, T, TOME_HD) and torch.equal(metric, metric.round())
+    return metric
+
+
+def tome_merge_case(B, T, D, with_size):
+    """x (B, T, D) of integers in -50..50 and sizes (B, T) of integers in 1..4 (or None): every size-weighted sum of a merged
+    group (at most 97 tokens) is an integer below 2^24."""
+    sd = _shape_seed(B, T, D)
+    x = ints("exact.tome.x", (B, T, D), -50, 50, sd)
+    size = ints("exact.tome.size", (B, T), 1, 4, sd) if with_size else None
+    assert 50 * 4 * (T // 2 + 2) < EXACT_LIMIT
+    return x, size
+
+
+def tome_metric_layout(metric, kind):
+    """The metric as hm_tome_merge_metric is handed it: (buf (B * T, ld), first column, columns, lo_off).  The kernel gets the
+    column slice buf[:, first:first + columns], row stride ld.  'ld80': the rows as they are.  'ld96': 80 columns from column 8
+    of 96, TOME_FILL around them.  'hi_lo': ld = 176, the slice starts at column 4, hi = v + c in its columns 0..79 and
+    lo = -c in its columns 88..167 for hashed integers c in -7..7 (hi + lo = v exactly), TOME_FILL everywhere else."""
+    B, T, hd = metric.shape
+    rows = metric.reshape(B * T, hd)
+    if kind == "ld80":
+        return rows.clone(), 0, hd, 0
+    if kind == "ld96":
+        buf = torch.full((B * T, 96), TOME_FILL)
+        buf[:, 8:8 + hd] = rows
+        return buf, 8, hd, 0
+    assert kind == "hi_lo"
+    c = ints("exact.tome.lo", (B * T, hd), -7, 7, _shape_seed(B, T))
+    buf = torch.full((B * T, 176), TOME_FILL)
+    buf[:, 4:4 + hd] = rows + c
+    buf[:, 4 + 88:4 + 88 + hd] = -c
+    assert torch.equal(buf[:, 4:4 + hd] + buf[:, 92:92 + hd], rows)
+    return buf, 4, 88 + hd, 88
+
+
+def tome_head_keys(metric, heads, dtype):
+    """(B * T, 3 * heads * 80) qkv rows of `dtype` whose keys are metric + delta_h for hashed integers delta_h (-8..8, the
+    last head's the negated sum of the others): their mean over the heads is the metric bit for bit.  q and v hold 1."""
+    B, T, hd = metric.shape
+    d = ints("exact.tome.delta", (B * T, heads - 1, hd), -8, 8, _shape_seed(B, T, heads))
+    d = torch.cat([d, -d.sum(1, keepdim=True)], 1)
+    k = metric.reshape(B * T, 1, hd) + d
+    assert torch.equal(k.sum(1) / heads, metric.reshape(B * T, hd)) and torch.equal(k.to(dtype).float(), k)
+    qkv = torch.ones(B * T, 3, heads, hd)
+    qkv[:, 1] = k
+    return qkv.reshape(B * T, 3 * heads * hd).to(dtype)
+
+
 # ------------------------------------------------------------------------------------------------ the comparison
 def _blocks(idx, n):
     b = sorted(set((idx // 64).tolist()))

@@ -25,6 +25,7 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import exact_data as ED  # noqa: E402
+import tome_rule as TR  # noqa: E402
 
 SUB = 256
 HALF = 0.5
@@ -42,7 +43,7 @@ def _ar(n):
 # ------------------------------------------------------------------------------------------------ index maps
 def k_tiles_rotated(K):
     k = _ar(K)
-    return ((k // 64 + 1) % (K // 64)) * 64 + k % 64
+    return ((k // 64 + 1) % (K // 64)) * 64 + k % 64 if K >= 64 else k        # (K % 64 != 0: the partial last tile takes tile 1's slot)
 
 
 def k_chunks_swapped(K):                       # neighbouring 8-wide chunks of a K-tile change places
@@ -220,6 +221,298 @@ def test_gemm_f32_positional_residual_sees_every_fault():
     for (M, N, K) in ED.gemm_f32_shapes() + ED.GEMM_F32_STRIDED:
         if M % 192 == 0:
             _gemm_catalogue(M, N, K, bias=True, resid=5, resid_rows=192)
+
+
+# ------------------------------------------------------------------------------------------------ hm_linear_f32
+def k_lane_group_transposed(K):                # k-slot g of MFMA i reads k = kb + 4i + g instead of kb + 4g + i
+    k = _ar(K)
+    return k // 16 * 16 + (k % 4) * 4 + (k % 16) // 4
+
+
+LINEAR_FAULTS = GEMM_FAULTS + [
+    ("X: the four k of a lane group permuted (4i + g)", "x", 1, k_lane_group_transposed),
+    ("W: the four k of a lane group permuted (4i + g)", "w", 1, k_lane_group_transposed),
+]
+LINEAR_WAVES = 4
+
+
+def linear_wave_not_applicable(shapes):
+    """(shape, wave) where the wave has no 16-wide K block: K <= 16 * wave."""
+    return {((M, N, K), w) for (M, N, K) in shapes for w in range(LINEAR_WAVES) if K <= 16 * w}
+
+
+def linear_fault_fractions(shapes):
+    """{fault name: [(fraction of outputs changed, shape), ...]} over the index-map catalogue and the four dropped waves, and
+    the set of (shape, wave) at which a dropped wave is no fault because the wave has no K block."""
+    table, na = {}, set()
+    for (M, N, K) in shapes:
+        x, w, b, r = ED.gemm_case(M, N, K, resid=5)
+        assert ED.exact_bound(x, w, K, b, r) < ED.EXACT_LIMIT
+        ops = {"x": x, "w": w, "bias": b, "resid": r}
+        rows, cols = _spread(M), _spread(N)
+        sizes = {("x", 0): M, ("x", 1): K, ("w", 0): N, ("w", 1): K, ("bias", 0): N, ("resid", 0): M, ("resid", 1): N}
+        ref = _gemm_sub(ops, rows, cols)
+        assert float(ref.abs().max()) < ED.EXACT_LIMIT
+        for name, op, axis, fn in LINEAR_FAULTS:
+            m = fn(sizes[(op, axis)])
+            if _is_identity(m):
+                continue
+            frac = float((_gemm_sub(ops, rows, cols, {(op, axis): m}) != ref).float().mean())
+            table.setdefault(name, []).append((frac, (M, N, K)))
+        for wave in range(LINEAR_WAVES):
+            name = f"wave {wave}'s 16-wide K blocks dropped"
+            mine = (_ar(K) // 16) % LINEAR_WAVES == wave
+            if not bool(mine.any()):
+                na.add(((M, N, K), wave))
+                continue
+            xz = x.clone()
+            xz[:, mine] = 0.0
+            frac = float((_gemm_sub(dict(ops, x=xz), rows, cols) != ref).float().mean())
+            table.setdefault(name, []).append((frac, (M, N, K)))
+    return table, na
+
+
+@pytest.mark.parametrize("name,shapes", [("prod", ED.LINEAR_F32_PROD), ("edge", ED.LINEAR_F32_EDGE)])
+def test_linear_f32_data_sees_every_fault(name, shapes):
+    """The GEMM catalogue, the lane map k = kb + 4i + g on either operand and each of the four waves' K blocks dropped change
+    more than half of the outputs at every hm_linear_f32 shape.  A dropped wave is no fault where the wave has no block
+    (K = 16: waves 1-3, K = 48: wave 3): those are listed, and the list is exactly that.  Smallest fractions measured: 0.75
+    (three of the four outputs of (1, 4, 16)) for the chunk and lane-group faults, 0.75 for the bias rotated by 1 at (1, 20, 64),
+    0.875 for a dropped wave (wave 1 at (16, 4, 48)); at the production shapes 0.86 (bias) and 0.98 and more (every K fault)."""
+    table, na = linear_fault_fractions(shapes)
+    low = [(n, f, sh) for n, rows in table.items() for (f, sh) in rows if not f > HALF]
+    assert not low, low
+    assert set(table) == {f[0] for f in LINEAR_FAULTS} | {f"wave {w}'s 16-wide K blocks dropped" for w in range(LINEAR_WAVES)}
+    assert na == linear_wave_not_applicable(shapes)
+    if name == "edge":
+        assert {K for (_, K), _ in ((sh[1:], w) for sh, w in na)} == {16, 48} and len({w for _, w in na}) == 3
+    else:
+        assert not na
+
+
+def test_linear_f32_edge_shapes_cover_every_value():
+    for axis, values in enumerate((ED.LINEAR_F32_M, ED.LINEAR_F32_N, ED.LINEAR_F32_K)):
+        for v in values:
+            assert sum(sh[axis] == v for sh in ED.LINEAR_F32_EDGE) >= 2, (axis, v)
+        assert {sh[axis] for sh in ED.LINEAR_F32_EDGE} == set(values)
+    assert len(set(ED.LINEAR_F32_EDGE)) == len(ED.LINEAR_F32_EDGE) and all(sh in ED.LINEAR_F32_PROD + ED.LINEAR_F32_EDGE for sh in ED.LINEAR_F32_STRIDED)
+    cfg = ED.synth.HamerConfig()
+    assert (64, cfg.dec.dim, cfg.dec.mlp_dim) in ED.LINEAR_F32_PROD and (1, 112, cfg.dec.dim) in ED.LINEAR_F32_PROD
+    assert (384, 80, 1280) in ED.LINEAR_F32_PROD and len(ED.LINEAR_F32_PROD) == 13
+
+
+# ------------------------------------------------------------------------------------------------ token merging
+def _tome_metric(T):
+    return ED.tome_match_case(ED.TOME_B, T, ED.TOME_SALT.get(T, 0))
+
+
+def _match_variant(metric, r, last_max=False, high_a_first=False, swapped=False, normalise=True):
+    """The matching again, vectorised and in float64, with one decision of the rule changed."""
+    m = metric.double()
+    if normalise:
+        m = m / (m * m).sum(-1, keepdim=True).sqrt()
+    a, b = (m[:, 1::2], m[:, 0::2]) if swapped else (m[:, 0::2], m[:, 1::2])
+    s = a @ b.transpose(1, 2)
+    mx = s.max(-1).values
+    j = _ar(s.shape[2])
+    at_max = s == mx[..., None]
+    best = torch.where(at_max, j, -1).max(-1).values if last_max else torch.where(at_max, j, s.shape[2]).min(-1).values
+    unm, src, dst = [], [], []
+    for c in range(s.shape[0]):
+        p = mx[c].tolist()
+        order = sorted(range(len(p)), key=lambda i: (-p[i], -i if high_a_first else i))
+        unm.append(order[r:])
+        src.append(order[:r])
+        dst.append(best[c][order[:r]].tolist())
+    B = s.shape[0]
+    return tuple(torch.tensor(t, dtype=torch.int64).reshape(B, -1) for t in (unm, src, dst))
+
+
+def _merge_variant(x, size, unm, src, dst, first_only=False, unweighted=False, size_kept=False):
+    """The merge again, with index_add_, and one step of it changed."""
+    B, T, D = x.shape
+    sz = (torch.ones(B, T) if size is None else size).double()
+    xs, ss = [], []
+    for b in range(B):
+        s_, d_ = src[b], dst[b]
+        if first_only:
+            keep = [k for k, j in enumerate(d_.tolist()) if j not in d_[:k].tolist()]
+            s_, d_ = s_[keep], d_[keep]
+        w = torch.ones_like(sz[b]) if unweighted else sz[b]
+        xw = x[b].double() * w[:, None]
+        num = torch.cat([x[b, 2 * unm[b]].double() * sz[b, 2 * unm[b], None], xw[1::2].index_add(0, d_, xw[2 * s_])])
+        den = torch.cat([sz[b, 2 * unm[b]], sz[b, 1::2].index_add(0, d_, sz[b, 2 * s_])])
+        xs.append(num.float() / den.float()[:, None])
+        ss.append((torch.cat([sz[b, 2 * unm[b]], sz[b, 1::2]]) if size_kept else den).float())
+    return torch.stack(xs), torch.stack(ss)
+
+
+def _same(got, ref):
+    return all(g.shape == r.shape and torch.equal(g, r) for g, r in zip(got, ref))
+
+
+def _changed_fraction(got, ref):
+    if any(g.shape != r.shape for g, r in zip(got, ref)):
+        return 1.0
+    n = sum(r.numel() for r in ref)
+    return sum(int((g != r).sum()) for g, r in zip(got, ref)) / max(n, 1)
+
+
+def _tome_merge_inputs(T, D):
+    return ED.tome_merge_case(ED.TOME_B, T, D, ED.tome_sizes_given(T))
+
+
+def test_tome_rule_is_the_oracle_on_exact_and_random_data():
+    """tests/tome_rule.py against oracle.tome_ref.bipartite_match / merge_tokens: indices, merged rows and sizes equal on every
+    TOME_EXACT case (where the rule asserts that all its intermediates are exact) and D; on the random-data cases of
+    test_tome_kernels_vs_oracle the indices and sizes equal and the merged rows, whose fp32 sums the oracle rounds, within
+    that test's own atol = 2e-6, rtol = 1e-6.  The vectorised second statement used for the fault catalogue agrees too."""
+    from oracle import tome_ref as T
+    for (tokens, r) in ED.TOME_EXACT:
+        metric = _tome_metric(tokens)
+        mine = TR.match(metric, r)
+        assert _same(mine, T.bipartite_match(metric, r)) and _same(mine, _match_variant(metric, r)), (tokens, r)
+        assert mine[0].shape == (ED.TOME_B, (tokens + 1) // 2 - r)
+        for D in ED.TOME_D:
+            x, size = _tome_merge_inputs(tokens, D)
+            sz = size if size is not None else torch.ones(ED.TOME_B, tokens)
+            xo, so = TR.merge(x, size, *mine)
+            x_ref, s_ref = T.merge_tokens(x, sz[..., None], *mine)
+            assert torch.equal(xo, x_ref) and torch.equal(so, s_ref[..., 0]), (tokens, r, D)
+            assert _same((xo, so), _merge_variant(x, size, *mine))
+            assert bool(TR.quotient_representable(x, size, *mine)[:, :mine[0].shape[1]].all())
+    B, H, d, D = 3, 4, 80, 320
+    for tokens, r, with_size in ((192, 16, False), (161, 14, True), (176, 15, True), (23, 8, True), (17, 4, True), (16, 4, True), (3, 1, True)):
+        qkv = ED.synth.uniform("tq", (B * tokens, 3 * H * d), 1.2, seed=tokens).half()
+        size = (1.0 + (ED.synth._hash_u32(torch.arange(B * tokens, dtype=torch.int64), 7) % 4).float()).reshape(B, tokens) if with_size else None
+        x = ED.synth.uniform("tx", (B * tokens, D), 1.0, seed=tokens + 1).reshape(B, tokens, D)
+        metric = qkv.float().reshape(B, tokens, 3, H, d)[:, :, 1].mean(2)
+        mine = TR.match(metric, r, exact=False)
+        assert _same(mine, T.bipartite_match(metric, r)), (tokens, r)
+        xo, so = TR.merge(x, size, *mine, exact=False)
+        x_ref, s_ref = T.merge_tokens(x, (size if with_size else torch.ones(B, tokens))[..., None], *mine)
+        assert torch.equal(so, s_ref[..., 0])
+        torch.testing.assert_close(xo, x_ref, atol=2e-6, rtol=1e-6)
+    with pytest.raises(AssertionError):
+        TR.match(metric, r)                                 # random data is not exact, and the rule says so
+
+
+def tome_data_conditions(T, r, metric):
+    """What the matching data must contain for the GPU test to decide the tie rules (names of the conditions that fail)."""
+    Na = (T + 1) // 2
+    unm, src, dst = TR.match(metric, r)
+    fails, boundary_tie = [], False
+    for c in range(metric.shape[0]):
+        s = TR.scores(metric[c])
+        p = s.max(1).values
+        if len(set(p.tolist())) < 4:
+            fails.append(f"crop {c}: fewer than 4 distinct proposal scores")
+        norm = (metric[c].double() ** 2).sum(1).sqrt()
+        if float(norm.max() / norm.min()) < 4:
+            fails.append(f"crop {c}: norms within a factor of 4")
+        ranked = sorted(p.tolist(), reverse=True)
+        boundary_tie |= r < Na and ranked[r - 1] == ranked[r]
+    tied = [(TR.scores(metric[c])[a] == TR.scores(metric[c])[a].max()).sum() >= 2 for c in range(metric.shape[0]) for a in src[c].tolist()]
+    if not any(bool(t) for t in tied):
+        fails.append("no merged A token whose maximal score is reached by two B tokens")
+    if r >= 3:
+        counts = torch.stack([torch.bincount(dst[c], minlength=T // 2) for c in range(metric.shape[0])])
+        if int(counts.max()) < 3 or int(counts.min()) > 0:
+            fails.append("no B token with three merges, or none without one")
+    if r < Na and not boundary_tie:
+        fails.append("no crop with equal scores at ranks r - 1 and r")
+    if _same(_match_variant(metric, r, normalise=False), (unm, src, dst)):
+        fails.append("the matching is the same without normalisation")
+    return fails
+
+
+def test_tome_match_data_decides_the_tie_rules():
+    """At every TOME_EXACT case with T >= 17: at least 4 distinct proposal scores and norms a factor of 4 apart in every crop; a
+    MERGED A token whose maximum is reached by two or more B tokens (so first-versus-last maximum changes a dst); where r >= 3
+    (a B token cannot receive three merges otherwise) a B token with three or more merges and one with none; where r < Na,
+    equal scores at ranks r - 1 and r in some crop (the tie rule decides WHO is merged); another matching without
+    normalisation.  The data is integer-valued, hashed per crop, and a pure function of (B, T, salt)."""
+    for (T, r) in ED.TOME_EXACT:
+        metric = _tome_metric(T)
+        assert torch.equal(metric, _tome_metric(T)) and not torch.equal(metric[0], metric[1]) and not torch.equal(metric[1], metric[2])
+        mags = metric.abs().amax(-1)
+        assert set(mags.unique().tolist()) <= set(map(float, ED.TOME_MAGNITUDES)) and bool(((metric == 0) | (metric.abs() == mags[..., None])).all())
+        assert set((metric != 0).sum(-1).unique().tolist()) <= set(ED.TOME_SUPPORTS)
+        for kind in ED.TOME_LAYOUTS:                                             # the layouts hold the metric, and something else around it
+            buf, first, cols, lo_off = ED.tome_metric_layout(metric, kind)
+            view = buf[:, first:first + cols]
+            value = view[:, :80] + (view[:, lo_off:lo_off + 80] if lo_off else 0)
+            assert torch.equal(value.reshape(ED.TOME_B, T, 80), metric) and buf.shape[1] == {"ld80": 80, "ld96": 96, "hi_lo": 176}[kind]
+            outside = torch.ones_like(buf, dtype=torch.bool)
+            outside[:, first:first + 80] = False
+            if lo_off:
+                outside[:, first + lo_off:first + lo_off + 80] = False
+                assert not torch.equal(view[:, :80].reshape(ED.TOME_B, T, 80), metric)
+            assert bool((buf[outside] == ED.TOME_FILL).all())
+        for dt in (torch.float16, torch.bfloat16):                               # (the builder asserts the head mean and the 16-bit exactness)
+            assert ED.tome_head_keys(metric, 4, dt).shape == (ED.TOME_B * T, 3 * 4 * 80)
+        if T >= 17:
+            assert bool((metric != 0).any(0).any(0).all())                       # every channel is used
+            fails = tome_data_conditions(T, r, metric)
+            assert not fails, ((T, r), fails)
+
+
+def tome_rule_fault_table():
+    """{fault: [(fraction of indices and merged values changed, (T, r)), ...]} and {fault: [(T, r) it does not apply to]}.
+    Matching faults are judged on (unm, src, dst) and the rows merged with them, merge faults on (x_out, size_out)."""
+    table, na = {}, {}
+
+    def note(name, applies, case, got, ref):
+        if applies:
+            table.setdefault(name, []).append((_changed_fraction(got, ref), case))
+        else:
+            na.setdefault(name, []).append(case)
+
+    for (T, r) in ED.TOME_EXACT:
+        metric = _tome_metric(T)
+        ref = TR.match(metric, r)
+        x, size = _tome_merge_inputs(T, ED.TOME_D[0])
+        out = TR.merge(x, size, *ref)
+        big = T >= 17                      # below, the crops hold one to four A tokens: ties and crowded B tokens are not promised
+        B = ED.TOME_B
+
+        def matched(name, applies, got):
+            full = got + _merge_variant(x, size, *got) if all(g.shape == f.shape for g, f in zip(got, ref)) else got
+            note(name, applies, (T, r), full, ref + out)
+
+        matched("last maximum instead of the first", big, _match_variant(metric, r, last_max=True))
+        matched("equal scores ranked higher a first", big, _match_variant(metric, r, high_a_first=True))
+        matched("A and B sets swapped", T >= 3, _match_variant(metric, r, swapped=True))
+        matched("no normalisation", big, _match_variant(metric, r, normalise=False))
+        buf, first, cols, lo_off = ED.tome_metric_layout(metric, "hi_lo")
+        matched("lo part ignored", big, _match_variant(buf[:, first:first + 80].reshape(B, T, 80), r))
+        buf, first, cols, lo_off = ED.tome_metric_layout(metric, "ld96")
+        matched("metric read with row stride 80 in the ld = 96 layout", big, _match_variant(buf.reshape(-1)[first:first + B * T * 80].reshape(B, T, 80), r))
+        matched("crop 0's indices used for every crop", big, tuple(t[:1].expand(B, -1) for t in ref))
+        crowded = big and r >= 3
+        note("only the first proposer merged into a dst", crowded, (T, r), _merge_variant(x, size, *ref, first_only=True), out)
+        note("size weights ignored in the sum", size is not None, (T, r), _merge_variant(x, size, *ref, unweighted=True), out)
+        note("size not accumulated into size_out", True, (T, r), _merge_variant(x, size, *ref, size_kept=True), out)
+    return table, na
+
+
+def test_tome_rule_fault_catalogue():
+    """Each wrong rule changes the indices or the merged rows at every case it applies to.  Not applicable, and listed: the
+    tie, normalisation, layout and crop faults below T = 17 (a crop of 2 or 3 tokens has one B token and promises no tie);
+    swapped sets at T = 2 (either way the two tokens end as one); a crowded B token where r < 3; size weights where no sizes
+    are given (T = 192)."""
+    table, na = tome_rule_fault_table()
+    low = [(n, f, c) for n, rows in table.items() for (f, c) in rows if not f > 0]
+    assert not low, low
+    assert len(table) == 10 and all(len(table[n]) + len(na.get(n, [])) == len(ED.TOME_EXACT) for n in table)
+    small = [(3, 1), (2, 1)]
+    assert na == {
+        "last maximum instead of the first": small, "equal scores ranked higher a first": small, "no normalisation": small,
+        "lo part ignored": small, "metric read with row stride 80 in the ld = 96 layout": small,
+        "crop 0's indices used for every crop": small, "A and B sets swapped": [(2, 1)],
+        "only the first proposer merged into a dst": [(129, 1)] + small,
+        "size weights ignored in the sum": [(192, 16), (192, 96)],
+    }
 
 
 # ------------------------------------------------------------------------------------------------ fp8
@@ -550,3 +843,4 @@ def test_assert_exact_locates_the_fault():
     g4[1, 3, 2, 4] += 1.0
     with pytest.raises(AssertionError, match=r"1 of 480 elements wrong; first at \(row 46, col 3\)"):
         ED.assert_exact(g4, r4, "conv")
+

@@ -466,6 +466,34 @@ def test_cross_attention(dt):
         np.testing.assert_allclose(out.double().numpy(), ref.numpy(), atol=2e-5, rtol=1e-4, err_msg=f"tokens {T}")
 
 
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16, torch.float32])
+def test_cross_attention_one_dominant_token_exact(dt):
+    """Every (hand, head) has one dominant context token: q = +-4 per channel (hashed signs), the chosen token's key = 4 q, every
+    other key +-1.  The chosen token's q . k * scale is 64 * 64 / 8 = 512 against at most 64 * 4 / 8 = 32 for any other: without
+    the max subtraction exp overflows, with it every other weight is exp(<= -480) = 0, the chosen one 1 and the sum 1, so the
+    output is the chosen token's v row -- hashed integers, exact in all three kv dtypes -- bit for bit.  That pins the token,
+    head and channel maps of both passes.  T in {1, 65, 192, 256} with the dominant token first, last and at T - 64 (the
+    last full 64-token step of the score pass), in the wide kv rows and at the offsets of test_cross_attention."""
+    B, heads, dh, layers, li = 5, 8, 64, 3, 1
+    inner = heads * dh
+    q = 4.0 * (2 * ED.ints("ca.exact.q", (B, heads, dh), 0, 1) - 1)
+    for T in (1, 65, 192, 256):
+        for pos in sorted({0, T - 1, max(T - 64, 0)}):
+            kv = ED.ints("ca.exact.other", (B, T, layers, 2, heads, dh), -3, 3, seed=T)
+            kv[:, :, li, 0] = 2 * ED.ints("ca.exact.k", (B, T, heads, dh), 0, 1, seed=T) - 1
+            kv[:, pos, li, 0] = 4.0 * q
+            v = ED.ints("ca.exact.v", (B, T, heads, dh), -100, 100, seed=T)
+            kv[:, :, li, 1] = v
+            scores = torch.einsum("bhd,bthd->bht", q, kv[:, :, li, 0]) * dh ** -0.5
+            assert bool((scores[:, :, pos] == 512).all())
+            assert T == 1 or float(torch.cat([scores[:, :, :pos], scores[:, :, pos + 1:]], -1).abs().max()) <= 32
+            kvd = kv.reshape(B * T, layers * 2 * inner).to(dt)
+            assert torch.equal(kvd.float(), kv.reshape(B * T, -1))
+            out = ops.cross_attention(q.reshape(B, inner).to(DEV), kvd.to(DEV), li * 2 * inner, li * 2 * inner + inner, B, T, heads, dh,
+                                      dh ** -0.5)
+            ED.assert_exact(out, v[:, pos].reshape(B, inner), (dt, "tokens", T, "dominant", pos))
+
+
 def test_cross_attention_rejects_token_counts_outside_1_to_256():
     B, heads, dh = 2, 8, 64
     q = _u("caq", (B, heads * dh), 2.0, seed=1).to(DEV)
