@@ -1,6 +1,6 @@
 """Compare two folders of the drivers' ``.npy`` records in the field's hand metrics, in millimetres.
 
-    python -m hamer_yolo_amd.evaluate --pred A --ref B [--json out.json]
+    python -m hamer_yolo_amd.evaluate --pred A --ref B [--json out.json] [--mesh-scores]
 
 Both folders hold what ``process_batch_manopara`` writes (``{'left': None | hand, 'right': None | hand}`` per image, a hand
 being ``betas``, ``pose_global``, ``pose_hand``, ``cam_t``, ``is_right``); a ground-truth folder in the same format works too.
@@ -10,6 +10,12 @@ as ``reconstruct_and_save_obj_with_wrapper`` does; its 21 joints and 778 vertice
 wrist-relative).  ``cam_t`` is NOT added to the points: all four metrics are relative to the wrist, where a translation
 cancels exactly, and adding it in fp32 would first round every coordinate at the magnitude of the depth (2.4e-7 m at 2 m, the
 order of the distances between two precision routes).  The translation is reported on its own, as ``root``, from the records.
+
+``--mesh-scores`` (``compare_folders_with(..., mesh_scores=True)``) adds the other half of the field's tables: F@5 mm and F@15 mm
+of the 778 vertices and the area under the PCK curve over 0-50 mm of joints and vertices, each raw and Procrustes-aligned
+(``hamer.utils.mesh_eval.MeshEvaluator``: hm_mesh_score, hm_pck_auc).  The points are the same wrist-relative ones: FreiHAND's
+UNALIGNED F-score is taken on absolute coordinates, this driver's is not (cam_t is not added, see above), so only the aligned
+F-scores and the AUCs compare with published tables.  The F-score rule is unpinned against FreiHAND's script.
 """
 from __future__ import annotations
 
@@ -68,6 +74,15 @@ def compare_folders(pred_dir: str, ref_dir: str, hamer, json_path: Optional[str]
     """Score the hands of ``pred_dir`` against those of ``ref_dir``.  Returns ``{'pairs', 'only_pred', 'only_ref' (counts),
     'only_pred_hands', 'only_ref_hands', 'hands' (lists of "stem/side"), 'metrics': {name: {mean, median, p95, max}},
     'per_hand': {name: [...]}}``; distances in mm, ``max_dtheta`` in radians, ``max_dbeta`` in MANO shape units."""
+    return compare_folders_with(pred_dir, ref_dir, hamer, json_path)
+
+
+def compare_folders_with(pred_dir: str, ref_dir: str, hamer, json_path: Optional[str] = None, mesh_scores: bool = False) -> Dict:
+    """``compare_folders`` with its opt-in parts.  ``mesh_scores=True`` adds ONE key to the result, ``'mesh_scores'``:
+    ``{'per_hand': {f5, f15, pa_f5, pa_f15: [...]}, 'metrics': {name: {mean, median, p95, max}}, 'auc': {auc_j, auc_v,
+    pa_auc_j, pa_auc_v, val_min, val_max, steps}}`` -- F-scores of the vertices at 5 and 15 mm and areas under the 0-50 mm PCK
+    curves of joints and vertices, raw (wrist-relative, NOT FreiHAND's absolute coordinates) and Procrustes-aligned.
+    Everything else in the result is what ``compare_folders`` returns."""
     import torch
     from .hamer.utils.pose_utils import pose_eval
     pairs, only_pred, only_ref = pair_records(pred_dir, ref_dir)
@@ -92,6 +107,17 @@ def compare_folders(pred_dir: str, ref_dir: str, hamer, json_path: Optional[str]
               "hands": [name(p[:2]) for p in pairs],
               "metrics": {m: summary(per_hand[m]) for m in METRICS},
               "per_hand": {m: [float(x) for x in per_hand[m]] for m in METRICS}}
+    if mesh_scores:
+        from .hamer.utils.mesh_eval import MeshEvaluator
+        ev = MeshEvaluator(max(len(pairs), 1), N_JOINTS, root=0)
+        auc = {k: float("nan") for k in ("auc_j", "auc_v", "pa_auc_j", "pa_auc_v")}
+        if pairs:
+            ev(P, G)
+            auc = {k: v for k, v in ev.result().items() if k in auc}
+        f = ev.per_hand()
+        auc.update({"val_min": ev.auc[0], "val_max": ev.auc[1], "steps": ev.auc[2]})
+        result["mesh_scores"] = {"per_hand": {k: [float(x) for x in f[k]] for k in ev.f_names},
+                                 "metrics": {k: summary(f[k]) for k in ev.f_names}, "auc": auc}
     if json_path:
         with open(json_path, "w") as f:
             json.dump(result, f, indent=1)
@@ -106,11 +132,23 @@ def format_line(result: Dict) -> str:
             f"only in pred {result['only_pred']}, only in ref {result['only_ref']}")
 
 
+def format_mesh_line(result: Dict) -> str:
+    """The line ``--mesh-scores`` adds: mean F-scores of the vertices and the areas under the PCK curves."""
+    ms = result["mesh_scores"]
+    f = " ".join(f"{'PA-' if k.startswith('pa_') else ''}F@{k.split('f')[-1]} {v['mean']:.4f}" for k, v in ms["metrics"].items())
+    a = ms["auc"]
+    auc = " ".join(f"{n} {a[k]:.4f}" for k, n in (("auc_j", "J"), ("auc_v", "V"), ("pa_auc_j", "PA-J"), ("pa_auc_v", "PA-V")))
+    return (f"mesh scores (wrist-relative): {f} (mean); AUC {1000 * a['val_min']:g}-{1000 * a['val_max']:g} mm, "
+            f"{a['steps']} steps: {auc}")
+
+
 def _parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="compare two folders of hand records: MPJPE / PA-MPJPE / MPVPE / PA-MPVPE in mm")
     ap.add_argument('--pred', type=str, required=True, help="folder of .npy records to score")
     ap.add_argument('--ref', type=str, required=True, help="folder of .npy records to score against (another route, or ground truth)")
     ap.add_argument('--json', type=str, default=None, help="also write the full result, per-hand vectors included, to this file")
+    ap.add_argument('--mesh-scores', action='store_true',
+                    help="also report F@5 / F@15 of the vertices and the AUC of the 0-50 mm PCK curves, raw and Procrustes-aligned")
     ap.add_argument('--ckpt', type=str, default=None, help="hamer.ckpt path or synthetic:<seed> (default: config/hamer_config.py); only its MANO model is used")
     return ap
 
@@ -121,8 +159,10 @@ def main(argv=None):
     from .infer import hamer_inference
     if args.ckpt:
         hamer_opt.ckpt_path = args.ckpt
-    result = compare_folders(args.pred, args.ref, hamer_inference(hamer_opt), args.json)
+    result = compare_folders_with(args.pred, args.ref, hamer_inference(hamer_opt), args.json, mesh_scores=args.mesh_scores)
     print(format_line(result))
+    if args.mesh_scores:
+        print(format_mesh_line(result))
     return result
 
 

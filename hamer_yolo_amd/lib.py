@@ -45,6 +45,7 @@ EXPORTS = [
     "hm_det_match", "hm_det_ap_workspace_bytes", "hm_det_ap", "hm_det_ap_curve",
     "hm_nms_batch_workspace_bytes", "hm_yolo_nms_batch",
     "hm_tta_sizes", "hm_tta_tables", "hm_tta_scale", "hm_yolo_decode_batch_tta",
+    "hm_mesh_score", "hm_pck_auc_workspace_bytes", "hm_pck_auc",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -93,6 +94,22 @@ class PoseEvalArgs(C.Structure):
     """hm_pose_eval_args: sel is a bit mask over the P points (all zero: every point); NULL outputs are not computed."""
     _fields_ = [("pred", vp), ("gt", vp), ("B", C.c_int), ("P", C.c_int), ("gt_stride", C.c_int), ("root", C.c_int),
                 ("sel", C.c_uint64 * 16), ("err", vp), ("pa_err", vp), ("aligned", vp), ("transform", vp)]
+
+
+class MeshScoreArgs(C.Structure):
+    """hm_mesh_score_args: the participating points are pred_lo .. pred_lo + pred_n - 1 and gt_lo .. gt_lo + gt_n - 1; NULL
+    outputs are not computed."""
+    _fields_ = [("pred", vp), ("gt", vp), ("transform", vp)] + \
+               [(n, C.c_int) for n in ("B", "P", "Q", "gt_stride", "root", "pred_lo", "pred_n", "gt_lo", "gt_n", "n_thr")] + \
+               [("thresholds", C.c_double * 8)] + \
+               [(n, vp) for n in ("d_pred", "d_gt", "precision", "recall", "fscore", "point_err")]
+
+
+class PckAucArgs(C.Structure):
+    """hm_pck_auc_args: err [N][ld] f32; thresholds np.linspace(val_min, val_max, steps); chunk_rows 0 = the default."""
+    _fields_ = [("err", vp), ("N", C.c_longlong), ("ld", C.c_longlong), ("chunk_rows", C.c_longlong),
+                ("val_min", C.c_double), ("val_max", C.c_double), ("K", C.c_int), ("steps", C.c_int)] + \
+               [(n, vp) for n in ("pck", "auc", "mean_auc", "curve", "thresholds", "workspace")] + [("workspace_bytes", C.c_size_t)]
 
 
 class VitBlock(C.Structure):
@@ -277,6 +294,10 @@ def load() -> C.CDLL:
     lib.hm_stem4_im2col.argtypes = [vp, vp, i, i, i, i, vp]
     lib.hm_sar_saigb_ch.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
     lib.hm_pose_eval.argtypes = [C.POINTER(PoseEvalArgs), vp]
+    lib.hm_mesh_score.argtypes = [C.POINTER(MeshScoreArgs), vp]
+    lib.hm_pck_auc_workspace_bytes.argtypes = [i, i]
+    lib.hm_pck_auc_workspace_bytes.restype = C.c_size_t
+    lib.hm_pck_auc.argtypes = [C.POINTER(PckAucArgs), vp]
     lib.hm_skeleton_overlay_workspace_bytes.argtypes = [i, i, i, i]
     lib.hm_skeleton_overlay_workspace_bytes.restype = C.c_size_t
     lib.hm_skeleton_overlay.argtypes = [vp, i, i, i, vp, i, C.POINTER(Skeleton), i, C.POINTER(C.c_uint8), i, vp, vp, C.c_size_t, vp]
@@ -294,7 +315,8 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)
         if name not in ("hm_version", "hm_last_error_string", "hm_hamer_workspace_bytes", "hm_nms_workspace_bytes", "hm_tome_index_bytes", "hm_conv_splitk_bytes",
                         "hm_mesh_overlay_workspace_bytes", "hm_mesh_render_workspace_bytes",
-                        "hm_skeleton_overlay_workspace_bytes", "hm_det_ap_workspace_bytes", "hm_nms_batch_workspace_bytes"):
+                        "hm_skeleton_overlay_workspace_bytes", "hm_det_ap_workspace_bytes", "hm_nms_batch_workspace_bytes",
+                        "hm_pck_auc_workspace_bytes"):
             fn.restype = i
     if lib.hm_version() != HM_VERSION:
         raise HipLibraryError(f"{LIB_PATH} reports HM_VERSION {lib.hm_version()}, this binding is written for {HM_VERSION}: "

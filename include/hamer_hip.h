@@ -814,6 +814,73 @@ typedef struct hm_pose_eval_args {
  * or 4, root outside -1..P-1, a bit of sel at or past P, all four outputs NULL, pred or gt not 4-byte aligned. */
 int hm_pose_eval(const hm_pose_eval_args* args, void* stream);
 
+/* ---- Mesh F-scores and the area under the PCK curve: csrc/mesh_eval.hip.  The caller owns every buffer, the calls are
+ * asynchronous on `stream`, nothing synchronises or allocates, argument errors return HM_ERR_ARG before any device work.  All
+ * fp64 arithmetic is plain IEEE in the order written (no FMA contraction, no fast-math).
+ *
+ * hm_mesh_score: nearest-neighbour distances between two point sets per hand, both ways, and what the hand-mesh tables make of
+ * them, in one launch (one 1024-thread workgroup per hand, both sets staged once in LDS as fp64).  Per hand: pred[b][root] and
+ * gt[b][root] are subtracted from every point in fp64 (root >= 0), each participating pred point x becomes scale * R * x + t
+ * in fp64 when `transform` is given (exactly the [13] hm_pose_eval writes), then for every participating point of one set
+ *   d = sqrt(min over the participating points of the other set of (dx dx + dy dy) + dz dz),
+ * a NaN candidate making the minimum NaN (numpy.min); precision[j] = #(d_pred < thr[j]) / pred_n, recall[j] =
+ * #(d_gt < thr[j]) / gt_n (strict, in fp64 on the unrounded distances, NaN compares false), fscore = 2 p r / (p + r), 0 when
+ * p + r == 0.  This is the F-score of the FreiHAND evaluation (its script names the two shares the other way round; F is
+ * symmetric); it is UNPINNED against FreiHAND's script and open3d -- the rule above is the definition.  Every output is
+ * rounded to fp32 once, at the store.  A hand's bytes do not depend on B or on its place in the batch; a non-finite input
+ * reaches the outputs of its own hand only.
+ * Measured on an MI355X (tools/bench_mesh_eval.py, profiles/mesh_eval_bench.log; per call, host submission included): 64 hands
+ * of 778 x 778 points 0.163 ms, 1024 hands 0.648 ms (the same computation in torch ops: 1.17 / 16.9 ms). */
+typedef struct hm_mesh_score_args {
+  const float* pred;        /* [B][P][3] f32 */
+  const float* gt;          /* [B][Q][gt_stride] f32, gt_stride 3 or 4; the fourth component is never read */
+  const float* transform;   /* [B][13]: scale, R row-major, t (hm_pose_eval's layout), applied to pred       or NULL */
+  int B, P, Q, gt_stride;   /* P and Q in 1..1024, independent of one another */
+  int root;                 /* -1, or an index into both sets */
+  int pred_lo, pred_n;      /* the participating pred points: pred_lo .. pred_lo + pred_n - 1 (pred_n >= 1) */
+  int gt_lo, gt_n;          /* the participating gt points */
+  int n_thr;                /* 0..8 */
+  double thresholds[8];     /* metres */
+  float* d_pred;            /* [B][pred_n] distance of every participating pred point to its nearest gt point  or NULL */
+  float* d_gt;              /* [B][gt_n]   the other direction                                               or NULL */
+  float* precision;         /* [B][n_thr]                                                                    or NULL */
+  float* recall;            /* [B][n_thr]                                                                    or NULL */
+  float* fscore;            /* [B][n_thr]                                                                    or NULL */
+  float* point_err;         /* [B][pred_n] |pred_i - gt_i| of corresponding participating points (after the same root
+                               subtraction and transform): the per-point error of the PCK curve; pred_n == gt_n   or NULL */
+} hm_mesh_score_args;
+/* HM_ERR_ARG: null args / pred / gt, B <= 0, P or Q outside 1..1024, gt_stride not 3 or 4, root outside -1..min(P, Q) - 1,
+ * a range that leaves its set or is empty, n_thr outside 0..8 (0 with precision, recall or fscore wanted), point_err with
+ * pred_n != gt_n, all six outputs NULL, pred / gt / transform not 4-byte aligned. */
+int hm_mesh_score(const hm_mesh_score_args* args, void* stream);
+
+/* hm_pck_auc: get_measures / _get_pck of rootnet/KeypointFusion/util/eval_utils.py (:38-75) for any number of keypoints K
+ * (the reference is hard-wired to 21).  thresholds = np.linspace(val_min, val_max, steps) bit for bit, formed in the kernel
+ * (i * step + start, step = (val_max - val_min) / (steps - 1), the last one set to val_max);
+ *   pck[k][i] = #(err[n][k] <= thr[i]) / N   (the reference's <=; a NaN error is a miss; one division),
+ *   auc[k] = trapz(pck[k], thr) / trapz(1, thr),  mean_auc = their mean,  curve[i] = mean over k of pck[k][i] (ascending k).
+ * The counts are integer histograms (LDS atomics, then 64-bit integer atomics into `workspace`, which the call zeroes on the
+ * stream first): the result does not depend on chunk_rows, the number of samples a workgroup takes (0: the default).  N is
+ * bounded by memory only.  Three operations on the stream: the zeroing, the histogram, one finishing workgroup.
+ * Measured on an MI355X (profiles/mesh_eval_bench.log; per call, 100 steps): N = 10000, K = 799 0.149 ms (torch ops 4.60 ms);
+ * N = 64, K = 799 0.102 ms (torch ops 0.093 ms); N = 64, K = 21 0.033 ms (0.093 ms).
+ * HM_ERR_ARG: a null args / err / pck / auc / workspace, N <= 0 (the reference returns None there and then fails), K < 1,
+ * ld < K, steps outside 2..256, val_min >= val_max or either not finite, chunk_rows < 0, workspace_bytes below the query. */
+typedef struct hm_pck_auc_args {
+  const float* err;         /* [N][ld] f32 on the device, the first K of each row are read */
+  long long N, ld, chunk_rows;
+  double val_min, val_max;
+  int K, steps;             /* steps in 2..256 */
+  double* pck;              /* [K][steps] f64 */
+  double* auc;              /* [K] f64 */
+  double* mean_auc;         /* [1] f64                                                                       or NULL */
+  double* curve;            /* [steps] f64                                                                   or NULL */
+  double* thresholds;       /* [steps] f64, the thresholds as the kernel formed them                          or NULL */
+  void* workspace; size_t workspace_bytes;
+} hm_pck_auc_args;
+size_t hm_pck_auc_workspace_bytes(int K, int steps);   /* 0 for an illegal K or steps */
+int hm_pck_auc(const hm_pck_auc_args* args, void* stream);
+
 /* ---- Detector evaluation (yolo/yolov7/test.py and utils/metrics.py): csrc/det_eval.hip.  The caller owns every buffer, the
  * calls are asynchronous on `stream`, nothing synchronises or allocates, argument errors return HM_ERR_ARG before any device
  * work.  All fp32 / fp64 arithmetic is plain IEEE in the order written (no FMA contraction, no fast-math).
