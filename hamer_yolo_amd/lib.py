@@ -46,6 +46,7 @@ EXPORTS = [
     "hm_nms_batch_workspace_bytes", "hm_yolo_nms_batch",
     "hm_tta_sizes", "hm_tta_tables", "hm_tta_scale", "hm_yolo_decode_batch_tta",
     "hm_mesh_score", "hm_pck_auc_workspace_bytes", "hm_pck_auc",
+    "hm_mask_score_workspace_bytes", "hm_mask_score",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -110,6 +111,11 @@ class PckAucArgs(C.Structure):
     _fields_ = [("err", vp), ("N", C.c_longlong), ("ld", C.c_longlong), ("chunk_rows", C.c_longlong),
                 ("val_min", C.c_double), ("val_max", C.c_double), ("K", C.c_int), ("steps", C.c_int)] + \
                [(n, vp) for n in ("pck", "auc", "mean_auc", "curve", "thresholds", "workspace")] + [("workspace_bytes", C.c_size_t)]
+
+
+class MaskQuery(C.Structure):
+    """hm_mask_query: pred = id_lo <= pred_id < id_hi, gt = mask == label (label -1: mask != 0), both of frame ``frame``."""
+    _fields_ = [(n, C.c_int32) for n in ("frame", "id_lo", "id_hi", "label")]
 
 
 class VitBlock(C.Structure):
@@ -298,6 +304,9 @@ def load() -> C.CDLL:
     lib.hm_pck_auc_workspace_bytes.argtypes = [i, i]
     lib.hm_pck_auc_workspace_bytes.restype = C.c_size_t
     lib.hm_pck_auc.argtypes = [C.POINTER(PckAucArgs), vp]
+    lib.hm_mask_score_workspace_bytes.argtypes = [i, i, i, i]
+    lib.hm_mask_score_workspace_bytes.restype = C.c_size_t
+    lib.hm_mask_score.argtypes = [vp, vp, i, i, i, vp, i, i, vp, vp, C.c_size_t, vp]
     lib.hm_skeleton_overlay_workspace_bytes.argtypes = [i, i, i, i]
     lib.hm_skeleton_overlay_workspace_bytes.restype = C.c_size_t
     lib.hm_skeleton_overlay.argtypes = [vp, i, i, i, vp, i, C.POINTER(Skeleton), i, C.POINTER(C.c_uint8), i, vp, vp, C.c_size_t, vp]
@@ -316,7 +325,7 @@ def load() -> C.CDLL:
         if name not in ("hm_version", "hm_last_error_string", "hm_hamer_workspace_bytes", "hm_nms_workspace_bytes", "hm_tome_index_bytes", "hm_conv_splitk_bytes",
                         "hm_mesh_overlay_workspace_bytes", "hm_mesh_render_workspace_bytes",
                         "hm_skeleton_overlay_workspace_bytes", "hm_det_ap_workspace_bytes", "hm_nms_batch_workspace_bytes",
-                        "hm_pck_auc_workspace_bytes"):
+                        "hm_pck_auc_workspace_bytes", "hm_mask_score_workspace_bytes"):
             fn.restype = i
     if lib.hm_version() != HM_VERSION:
         raise HipLibraryError(f"{LIB_PATH} reports HM_VERSION {lib.hm_version()}, this binding is written for {HM_VERSION}: "

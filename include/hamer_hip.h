@@ -881,6 +881,41 @@ typedef struct hm_pck_auc_args {
 size_t hm_pck_auc_workspace_bytes(int K, int steps);   /* 0 for an illegal K or steps */
 int hm_pck_auc(const hm_pck_auc_args* args, void* stream);
 
+/* ---- Mask scores: region similarity J and contour accuracy F of a predicted silhouette against a label mask, the pair of
+ * segmentation measures of the DAVIS benchmark, written from its definition: csrc/mask_eval.hip.  The rule below is the
+ * definition; it is UNPINNED against DAVIS's own script (and skimage), neither of which this project can run.
+ *
+ * For one query, pred and gt are binary images of H x W pixels.
+ *   Boundary map  b(s)[y][x] = s[y][x] != s[y][x1] || s[y][x] != s[y1][x] || s[y][x] != s[y1][x1],
+ *                 x1 = min(x + 1, W - 1), y1 = min(y + 1, H - 1): the east, south and south-east neighbours with the last row
+ *                 and column replicated.  A full or an empty image has no boundary pixel; the bottom-right pixel never is one.
+ *   Match         a boundary pixel of pred is matched when some boundary pixel of gt lies at an integer offset (dx, dy) with
+ *                 dx dx + dy dy <= r r, and the same the other way round: dilation by a disk of radius r, in integers only.
+ *   Radius        bound_radius(H, W, bound_th = 0.008) = bound_th if bound_th >= 1, else ceil(bound_th * sqrt(H H + W W)):
+ *                 18 for 1080 x 1920, 12 for 720 x 1280 (hamer/utils/mask_eval.py).  The kernel takes r in 0..64.
+ *   counts[q][8]  0 inter = sum(pred & gt), 1 pred_area, 2 gt_area, 3 pred_boundary, 4 gt_boundary, 5 pred_matched,
+ *                 6 gt_matched, 7 pixels = H W: exact integers.
+ *   From counts, in float64: J = 1 if pred_area + gt_area == 0, else inter / (pred_area + gt_area - inter);
+ *                 P = pred_matched / pred_boundary, R = gt_matched / gt_boundary; neither boundary exists: P = R = 1; only gt
+ *                 has one: P = 1, R = 0; only pred has one: P = 0, R = 1; F = 0 if P + R == 0, else 2 P R / (P + R).
+ *
+ * pred_id [N][H][W] int32 is what hm_mesh_render writes (a mesh index or -1); mask [N][H][W] uint8 is a label image.  Query q
+ * looks at frame `frame`; a pixel is pred when id_lo <= pred_id < id_hi (an empty range is an empty pred) and gt when
+ * mask == label, or mask != 0 when label == -1.  Several queries may name one frame.  A query whose frame is outside 0..N-1 is
+ * not read: its counts are all zero, pixels included.  All 8 counts of every query are written on every call (callers do not
+ * clear them).  A query's counts depend on its own images and the radius alone: not on Q, the order of the queries, the rest of
+ * the batch or the grid (the sums are integer atomics).  Asynchronous on `stream`: three kernels, no host synchronisation, no
+ * allocation.  Q == 0 succeeds and launches nothing (queries, counts and workspace may then be NULL).
+ * HM_ERR_ARG before any device work: a null pointer, N, H or W < 1, N H W >= 2^31, radius outside 0..64, Q < 0, workspace_bytes
+ * below the query, counts or workspace not 8-byte aligned (pred_id and queries: 4-byte).
+ * Measured on an MI355X (tools/bench_mask_eval.py, profiles/mask_eval_bench.log; per call, host submission included, 1080 x 1920,
+ * r = 18): 16 frames with one query each 0.148 ms, with four 0.377 ms; 64 frames 0.456 / 1.418 ms (the same counts from torch ops
+ * on the device 12.4 / 49.3 / 48.9 / 197 ms; the hm_mesh_render call of the same frames 0.96 / 3.24 ms). */
+typedef struct hm_mask_query { int32_t frame, id_lo, id_hi, label; } hm_mask_query;
+size_t hm_mask_score_workspace_bytes(int Q, int H, int W, int radius);   /* 0 for illegal sizes; positive otherwise */
+int hm_mask_score(const int32_t* pred_id, const uint8_t* mask, int N, int H, int W, const hm_mask_query* queries /* device */,
+                  int Q, int radius, int64_t* counts /* device [Q][8] */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Detector evaluation (yolo/yolov7/test.py and utils/metrics.py): csrc/det_eval.hip.  The caller owns every buffer, the
  * calls are asynchronous on `stream`, nothing synchronises or allocates, argument errors return HM_ERR_ARG before any device
  * work.  All fp32 / fp64 arithmetic is plain IEEE in the order written (no FMA contraction, no fast-math).
