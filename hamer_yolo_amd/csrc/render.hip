@@ -9,17 +9,17 @@
 //              (fp32 mean depth, face id) goes into the frame's key buffer with one unsigned 64-bit atomicMin.
 //  * compose - one pass over the frames: key -> face -> colour -> output frame (never in place); the key is reset on the
 //              way, so the key buffer is filled once when it is allocated and stays clean between calls.
+// The tile list, the cull step and the key buffer's contract are raster_tiles.h's, shared with zrender.hip.
 // Every fp32 / fp64 expression of the rule is evaluated without contraction (`#pragma clang fp contract(off)`), in the
 // order the rule gives, so the bytes are those of the numpy restatement.
 #include <math.h>
 #include "common.h"
-#include "hamer_hip_internal.h"
+#include "raster_tiles.h"
 
 namespace {
+using namespace raster_tiles;
 
-constexpr int TILE = 16;
 constexpr int MESHES_PER_LAUNCH = 120;             // setup kernel argument block stays under 4 KiB
-constexpr unsigned long long NO_KEY = ~0ull;
 constexpr int F_DEGENERATE = 1, F_SMALL = 2;       // FaceRec.flags
 
 struct MeshBlock {
@@ -33,34 +33,10 @@ struct FaceRec {
   unsigned depth;                                  // bits of the fp32 mean corner depth (> 0, so ordered as unsigned)
   int flags;
 };
-struct MeshRec { int frame, f0, nf, tiles_x; };    // what raster needs of a mesh
 
-struct Layout {
-  size_t keys, counter, flags, meshes, items, recs, boxes, colours, total;
-};
-
-size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
+using Layout = TileLayout;                         // tail: one packed B G R colour per face
 Layout layout(int N, int H, int W, int n_meshes, int n_faces) {
-  const size_t tiles = (size_t)((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
-  Layout L;
-  L.keys = 0;                                                          // N*H*W keys, first: their place never moves
-  L.counter = align256((size_t)N * H * W * 8);
-  L.flags = L.counter + 256;                                           // one byte per (frame, tile): a key was written there
-  L.meshes = align256(L.flags + (size_t)N * tiles);
-  L.items = align256(L.meshes + (size_t)n_meshes * sizeof(MeshRec));
-  L.recs = align256(L.items + (size_t)n_meshes * tiles * sizeof(int2));
-  L.boxes = align256(L.recs + (size_t)n_faces * sizeof(FaceRec));
-  L.colours = align256(L.boxes + (size_t)n_faces * sizeof(int4));
-  L.total = align256(L.colours + (size_t)n_faces * 4);
-  return L;
-}
-
-__device__ __forceinline__ long long edge64(int ax, int ay, int bx, int by, int px, int py) {
-  return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
-}
-__device__ __forceinline__ int edge32(int ax, int ay, int bx, int by, int px, int py) {
-  return (bx - ax) * (py - ay) - (by - ay) * (px - ax);
+  return tile_layout(N, H, W, n_meshes, n_faces, sizeof(FaceRec), (size_t)n_faces * 4);
 }
 
 // Closed-triangle coverage of pixel (px, py), already known to lie inside the face's bounding box.  F_SMALL: the box
@@ -82,11 +58,6 @@ __device__ __forceinline__ bool covers(const FaceRec& f, int px, int py) {
   return (f.flags & F_SMALL) ? covers_t<int, edge32>(f, px, py) : covers_t<long long, edge64>(f, px, py);
 }
 
-__device__ __forceinline__ unsigned rint_u8(double v) {
-  const double r = rint(v);
-  return (unsigned)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
-}
-
 // One workgroup per mesh of the block.
 __global__ __launch_bounds__(256) void overlay_setup_kernel(MeshBlock mb, const double* __restrict__ K,
                                                             const double* __restrict__ verts, const int* __restrict__ faces,
@@ -94,16 +65,12 @@ __global__ __launch_bounds__(256) void overlay_setup_kernel(MeshBlock mb, const 
 #pragma clang fp contract(off)
   const int mi = blockIdx.x, tid = threadIdx.x;
   const hm_mesh m = mb.m[mi];
-  const int mesh = mb.first + mi;
   const double* k = K + (size_t)m.frame * 9;
   const double k00 = k[0], k01 = k[1], k02 = k[2], k10 = k[3], k11 = k[4], k12 = k[5], k20 = k[6], k21 = k[7], k22 = k[8];
   const double* vb = verts + (size_t)m.v0 * 3;
   FaceRec* recs = (FaceRec*)(ws + L.recs);
   int4* boxes = (int4*)(ws + L.boxes);
-  unsigned* colours = (unsigned*)(ws + L.colours);
-  __shared__ int bx0, by0, bx1, by1, base;
-  if (tid == 0) { bx0 = INT_MAX; by0 = INT_MAX; bx1 = INT_MIN; by1 = INT_MIN; }
-  __syncthreads();
+  unsigned* colours = (unsigned*)(ws + L.tail);
   int lx0 = INT_MAX, ly0 = INT_MAX, lx1 = INT_MIN, ly1 = INT_MIN;
   for (int j = tid; j < m.nf; j += 256) {
     const size_t fid = (size_t)m.f0 + j;
@@ -153,61 +120,34 @@ __global__ __launch_bounds__(256) void overlay_setup_kernel(MeshBlock mb, const 
     boxes[fid] = box;
     colours[fid] = col;
   }
-  if (lx0 <= lx1) { atomicMin(&bx0, lx0); atomicMin(&by0, ly0); atomicMax(&bx1, lx1); atomicMax(&by1, ly1); }
-  __syncthreads();
-  const bool any = bx0 <= bx1;
-  const int tx0 = any ? bx0 / TILE : 0, ty0 = any ? by0 / TILE : 0;
-  const int ntx = any ? bx1 / TILE - tx0 + 1 : 0, nty = any ? by1 / TILE - ty0 + 1 : 0;
-  if (tid == 0) {
-    base = ntx * nty ? (int)atomicAdd((unsigned*)(ws + L.counter), (unsigned)(ntx * nty)) : 0;
-    MeshRec mr = {m.frame, m.f0, m.nf, 0};
-    ((MeshRec*)(ws + L.meshes))[mesh] = mr;
-  }
-  __syncthreads();
-  int2* items = (int2*)(ws + L.items);
-  for (int t = tid; t < ntx * nty; t += 256)
-    items[base + t] = make_int2(mesh, ((ty0 + t / ntx) << 16) | (tx0 + t % ntx));
+  emit_mesh_tiles(lx0, ly0, lx1, ly1, mb.first + mi, MeshRec{m.frame, m.f0, m.nf, 0}, ws, L);
 }
 
 // Grid-strided over the work list; one lane per pixel of a 16 x 16 tile.
 __global__ __launch_bounds__(256) void overlay_raster_kernel(int H, int W, char* __restrict__ ws, Layout L) {
   __shared__ FaceRec s_face[256];
-  __shared__ int s_wave[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const unsigned count = *(const unsigned*)(ws + L.counter);
   const int2* items = (const int2*)(ws + L.items);
   const MeshRec* meshes = (const MeshRec*)(ws + L.meshes);
   const FaceRec* recs = (const FaceRec*)(ws + L.recs);
   const int4* boxes = (const int4*)(ws + L.boxes);
-  unsigned long long* keys = (unsigned long long*)(ws + L.keys);
-  const int tiles_x = (W + TILE - 1) / TILE, tiles = tiles_x * ((H + TILE - 1) / TILE);
   for (unsigned w = blockIdx.x; w < count; w += gridDim.x) {
     const int2 it = items[w];
     const MeshRec m = meshes[it.x];
-    const int tx = it.y & 0xFFFF, ty = it.y >> 16;
+    const int tx = tile_x(it.y), ty = tile_y(it.y);
     const int x0 = tx * TILE, y0 = ty * TILE;
     const int px = x0 + (tid & (TILE - 1)), py = y0 + (tid >> 4);
     unsigned long long best = NO_KEY;
     for (int c0 = 0; c0 < m.nf; c0 += 256) {
       // cull 256 faces against the tile into the LDS list
       const int j = c0 + tid;
-      bool hit = false;
-      if (j < m.nf) {
-        const int4 b = boxes[(size_t)m.f0 + j];
-        hit = b.x <= b.z && b.x <= x0 + TILE - 1 && b.z >= x0 && b.y <= y0 + TILE - 1 && b.w >= y0;
-      }
-      const unsigned long long mask = __ballot(hit);
-      const int before = __popcll(mask & ((1ull << lane) - 1));
-      if (lane == 0) s_wave[wave] = __popcll(mask);
-      __syncthreads();
-      int off = 0, n = 0;
-      for (int q = 0; q < 4; ++q) { off += q < wave ? s_wave[q] : 0; n += s_wave[q]; }
-      if (hit) {
+      const bool hit = j < m.nf && box_meets_tile(boxes[(size_t)m.f0 + j], x0, y0);
+      const int n = cull_to_lds(hit, [&](int slot) {
         FaceRec r = recs[(size_t)m.f0 + j];
         r.flags |= j << 2;                                           // the face's index inside the mesh rides along
-        s_face[off + before] = r;
-      }
-      __syncthreads();
+        s_face[slot] = r;
+      });
       if (px < W && py < H) {
         for (int q = 0; q < n; ++q) {
           const FaceRec f = s_face[q];
@@ -220,10 +160,7 @@ __global__ __launch_bounds__(256) void overlay_raster_kernel(int H, int W, char*
       }
       __syncthreads();                                               // the list is rewritten by the next chunk
     }
-    if (best != NO_KEY) {
-      atomicMin(keys + ((size_t)m.frame * H + py) * W + px, best);
-      ((unsigned char*)(ws + L.flags))[(size_t)m.frame * tiles + ty * tiles_x + tx] = 1;
-    }
+    if (best != NO_KEY) commit_key(ws, L, ((size_t)m.view * H + py) * W + px, tile_index(m.view, tx, ty, H, W), best);
   }
 }
 
@@ -234,19 +171,13 @@ __global__ __launch_bounds__(256) void overlay_compose_kernel(const uint8_t* __r
 #pragma clang fp contract(off)
   const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y, n = blockIdx.z;
   if (x >= W || y >= H) return;
-  const int tiles_x = (W + TILE - 1) / TILE, tiles = tiles_x * ((H + TILE - 1) / TILE);
   const size_t p = ((size_t)n * H + y) * W + x;
   const uint8_t* src = frames + p * 3;
   uint8_t* dst = out + p * 3;
   const uint8_t b = src[0], g = src[1], r = src[2];
-  unsigned long long key = NO_KEY;
-  if (((const unsigned char*)(ws + L.flags))[(size_t)n * tiles + (y / TILE) * tiles_x + x / TILE]) {
-    unsigned long long* kp = (unsigned long long*)(ws + L.keys) + p;
-    key = *kp;
-    if (key != NO_KEY) *kp = NO_KEY;
-  }
+  const unsigned long long key = take_key(ws, L, p, tile_index(n, x / TILE, y / TILE, H, W));
   if (key == NO_KEY) { dst[0] = b; dst[1] = g; dst[2] = r; return; }
-  const unsigned col = ((const unsigned*)(ws + L.colours))[(unsigned)key];
+  const unsigned col = ((const unsigned*)(ws + L.tail))[(unsigned)key];
   const unsigned cb = col & 255, cg = (col >> 8) & 255, cr = (col >> 16) & 255;
   if (style == HM_STYLE_SHADED) { dst[0] = cb; dst[1] = cg; dst[2] = cr; return; }
   // cv2.addWeighted(overlay, alpha, image, beta, 0): rint(alpha * c + beta * i) in fp32, product then sum
@@ -269,23 +200,9 @@ int check_args(const uint8_t* frames, int N, int H, int W, const double* K, cons
   if ((n_verts > 0 && !verts) || (n_faces > 0 && !faces)) return hm_set_error(HM_ERR_ARG, "hm_mesh_overlay: null vertices or faces");
   if (style != HM_STYLE_FLAT && style != HM_STYLE_SHADED) return hm_set_error(HM_ERR_ARG, "hm_mesh_overlay: unknown style");
   if (!(alpha >= 0.0 && alpha <= 1.0)) return hm_set_error(HM_ERR_ARG, "hm_mesh_overlay: alpha outside [0, 1]");
-  const size_t fb = (size_t)N * H * W * 3;
-  if (frames < out + fb && out < frames + fb) return hm_set_error(HM_ERR_ARG, "hm_mesh_overlay: out overlaps frames (never in place)");
-  for (int i = 0; i < n_meshes; ++i) {
-    const hm_mesh& m = meshes[i];
-    if (m.frame < 0 || m.frame >= N) return hm_set_error(HM_ERR_ARG, "hm_mesh_overlay: mesh frame outside the batch");
-    if (m.nv < 0 || m.nf < 0 || m.v0 < 0 || m.f0 < 0) return hm_set_error(HM_ERR_ARG, "hm_mesh_overlay: negative mesh range");
-    if (m.nv == 0 && m.nf > 0) return hm_set_error(HM_ERR_ARG, "hm_mesh_overlay: a mesh with faces but no vertices");
-    if ((long long)m.v0 + m.nv > n_verts || (long long)m.f0 + m.nf > n_faces)
-      return hm_set_error(HM_ERR_ARG, "hm_mesh_overlay: mesh range outside the vertex or face array");
-  }
-  // face ranges of two meshes must not overlap: the face id names one face of one mesh
-  for (int i = 0; i < n_meshes; ++i)
-    for (int j = i + 1; j < n_meshes; ++j) {
-      const hm_mesh &a = meshes[i], &b = meshes[j];
-      if (a.nf > 0 && b.nf > 0 && a.f0 < b.f0 + b.nf && b.f0 < a.f0 + a.nf)
-        return hm_set_error(HM_ERR_ARG, "hm_mesh_overlay: two meshes share faces");
-    }
+  int rc = check_out_apart("hm_mesh_overlay", frames, out, (size_t)N * H * W * 3);
+  if (rc == HM_OK) rc = check_mesh_table("hm_mesh_overlay", "frame", meshes, n_meshes, N, n_verts, n_faces, false);
+  if (rc != HM_OK) return rc;
   if (ws_bytes < layout(N, H, W, n_meshes, n_faces).total) return hm_set_error(HM_ERR_ARG, "hm_mesh_overlay: workspace too small");
   return HM_OK;
 }
@@ -316,11 +233,7 @@ extern "C" int hm_mesh_overlay(const uint8_t* frames, int N, int H, int W, const
     for (int i = 0; i < mb.count; ++i) mb.m[i] = meshes_host[first + i];
     hipLaunchKernelGGL(overlay_setup_kernel, dim3(mb.count), dim3(256), 0, s, mb, K, verts, faces, H, W, style, ws, L);
   }
-  if (n_meshes > 0) {
-    const size_t upper = (size_t)n_meshes * ((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
-    const int grid = (int)(upper < 2048 ? upper : 2048);
-    hipLaunchKernelGGL(overlay_raster_kernel, dim3(grid), dim3(256), 0, s, H, W, ws, L);
-  }
+  if (n_meshes > 0) hipLaunchKernelGGL(overlay_raster_kernel, dim3(raster_grid(n_meshes, H, W)), dim3(256), 0, s, H, W, ws, L);
   const float a = (float)alpha, b = (float)(1.0 - alpha);
   hipLaunchKernelGGL(overlay_compose_kernel, dim3((W + 63) / 64, (H + 3) / 4, N), dim3(64, 4), 0, s, frames, out, H, W, style, a, b,
                      ws, L);

@@ -18,15 +18,12 @@
 // a pixel at signed major-axis offset c from `a` can only be covered by the samples c - r .. c + r, and only their minor
 // coordinate needs the fp64 expression, evaluated without contraction as numpy does.
 #include <math.h>
-#include <algorithm>
-#include <numeric>
-#include <vector>
 #include "common.h"
-#include "hamer_hip_internal.h"
+#include "raster_tiles.h"
 
 namespace {
+using namespace raster_tiles;
 
-constexpr int TILE = 16;
 constexpr int NJ = 21;
 constexpr int MAX_RADIUS = 32, MAX_SIDE = 16384;
 constexpr int HANDS_PER_LAUNCH = 128;              // setup kernel argument block stays under 4 KiB
@@ -57,10 +54,8 @@ static_assert(sizeof(HandRec) % 8 == 0, "HandRec is copied as 8-byte words");
 
 struct Layout { size_t counter, flags, ranges, items, recs, total; };
 
-size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
 Layout layout(int N, int H, int W, int n_hands) {
-  const size_t tiles = (size_t)((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
+  const size_t tiles = tiles_of(H, W);
   Layout L;
   L.counter = 0;
   L.flags = 256;                                                       // one byte per (image, tile): the tile is on the list
@@ -132,7 +127,7 @@ __global__ __launch_bounds__(64) void skeleton_setup_kernel(HandBlock hb, const 
     const unsigned bit = 1u << (8 * (f & 3));
     if (!(atomicOr(flags + (f >> 2), bit) & bit)) {
       const unsigned slot = atomicAdd((unsigned*)(ws + L.counter), 1u);
-      items[slot] = make_int2(a.image, (ty << 16) | tx);
+      items[slot] = make_int2(a.image, pack_tile(tx, ty));
     }
   }
 }
@@ -205,7 +200,7 @@ __global__ __launch_bounds__(256) void skeleton_raster_kernel(uint8_t* __restric
   for (unsigned w = blockIdx.x; w < count; w += gridDim.x) {
     const int2 it = items[w];
     const int2 range = ranges[it.x];
-    const int x0 = (it.y & 0xFFFF) * TILE, y0 = (it.y >> 16) * TILE;
+    const int x0 = tile_x(it.y) * TILE, y0 = tile_y(it.y) * TILE;
     const int px = x0 + (tid & (TILE - 1)), py = y0 + (tid >> 4);
     int joint = -1;
     for (int c0 = 0; c0 < range.y; c0 += CHUNK) {
@@ -215,7 +210,7 @@ __global__ __launch_bounds__(256) void skeleton_raster_kernel(uint8_t* __restric
         bool hit = false;
         if (k < range.y) {
           const HandRec& r = recs[range.x + k];
-          hit = r.bx0 <= r.bx1 && r.bx0 <= x0 + TILE - 1 && r.bx1 >= x0 && r.by0 <= y0 + TILE - 1 && r.by1 >= y0;
+          hit = box_meets_tile(make_int4(r.bx0, r.by0, r.bx1, r.by1), x0, y0);
         }
         const unsigned long long mask = __ballot(hit);
         if (hit) {
@@ -312,9 +307,7 @@ extern "C" int hm_skeleton_overlay(const uint8_t* images, int N, int H, int W, c
   Palette pal;
   for (int j = 0; j < NJ; ++j)
     pal.c[j] = palette_host[j * 3] | ((unsigned)palette_host[j * 3 + 1] << 8) | ((unsigned)palette_host[j * 3 + 2] << 16);
-  const size_t tiles = (size_t)((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
-  const size_t upper = std::min((size_t)N, (size_t)n_hands) * tiles;               // a hand touches tiles of one image
-  const int grid = (int)(upper < 4096 ? upper : 4096);
+  const int grid = raster_grid(std::min((size_t)N, (size_t)n_hands), H, W, 4096);   // a hand touches tiles of one image
   hipLaunchKernelGGL(skeleton_raster_kernel, dim3(grid), dim3(256), 0, s, out, H, W, pal, order, (const char*)ws, L);
   return hm_check_launch("hm_skeleton_overlay");
 }

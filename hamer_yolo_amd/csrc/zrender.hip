@@ -1,8 +1,8 @@
 // Z-buffered mesh renderer (reference: hamer/utils/mesh_renderer.py MeshRenderer.__call__, :243-320, `color, rend_depth =
 // renderer.render(...)`): per view an RGBA image, a per-pixel depth map and a per-pixel mesh label, and optionally the
 // colour composed onto BGR frames.  The rule is stated in include/hamer_hip.h (hm_mesh_render) and DESIGN.md section 8.1;
-// tests/zrender_rule.py restates it in numpy.  It keeps the shape of render.hip: one workspace whose key buffer stays
-// 0xFF between calls, mesh records as kernel arguments, no host synchronisation.
+// tests/zrender_rule.py restates it in numpy.  It has the shape of render.hip, and the common part is raster_tiles.h: one
+// workspace whose key buffer stays 0xFF between calls, mesh records as kernel arguments, no host synchronisation.
 //  * normals - one thread per vertex walks its mesh's faces, staged in LDS 1024 at a time, and sums the fp64 face cross
 //              products of the faces that name it in ascending row order: no float atomics, one order.
 //  * setup   - one workgroup per mesh: per face the fp64 projection to 24.8 fixed point, the validity tests, the winding
@@ -18,19 +18,16 @@
 //              vertex normals interpolated and shaded, and the requested outputs written.
 // The whole file is compiled without contraction, and every fp64 expression is written in the rule's order.
 #include <math.h>
-#include <algorithm>
-#include <vector>
 #include "common.h"
-#include "hamer_hip_internal.h"
+#include "raster_tiles.h"
 
 #pragma clang fp contract(off)
 
 namespace {
+using namespace raster_tiles;
 
-constexpr int TILE = 16;
 constexpr int MESHES_PER_LAUNCH = 48;              // kernel argument block stays under 4 KiB
 constexpr int NORMAL_CHUNK = 1024;                 // faces staged in LDS per step of the normals kernel
-constexpr unsigned long long NO_KEY = ~0ull;
 constexpr int F_SMALL = 1, F_OWN0 = 2, F_OWN1 = 4, F_OWN2 = 8;
 
 struct ZMesh {
@@ -56,44 +53,16 @@ struct ZTileFace {                                 // what raster keeps in LDS
   int flags, j;                                    // j: the face's index inside its mesh
   double area2, r0, r1, r2;
 };
-struct ZMeshRec { int view, f0, nf, pad; };
 
-struct ZLayout {
-  size_t keys, counter, flags, meshes, items, recs, boxes, normals, total;
-};
-
-size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
+using ZLayout = TileLayout;                        // tail: one fp64 normal (three doubles) per vertex
 ZLayout layout(int N, int H, int W, int n_verts, int n_meshes, int n_faces) {
-  const size_t tiles = (size_t)((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
-  ZLayout L;
-  L.keys = 0;                                                          // N*H*W keys, first: their place never moves
-  L.counter = align256((size_t)N * H * W * 8);
-  L.flags = L.counter + 256;                                           // one byte per (view, tile): a key was written there
-  L.meshes = align256(L.flags + (size_t)N * tiles);
-  L.items = align256(L.meshes + (size_t)n_meshes * sizeof(ZMeshRec));
-  L.recs = align256(L.items + (size_t)n_meshes * tiles * sizeof(int2));
-  L.boxes = align256(L.recs + (size_t)n_faces * sizeof(ZFace));
-  L.normals = align256(L.boxes + (size_t)n_faces * sizeof(int4));
-  L.total = align256(L.normals + (size_t)n_verts * 3 * sizeof(double));
-  return L;
+  return tile_layout(N, H, W, n_meshes, n_faces, sizeof(ZFace), (size_t)n_verts * 3 * sizeof(double));
 }
 
-__device__ __forceinline__ long long edge64(int ax, int ay, int bx, int by, int px, int py) {
-  return (long long)(bx - ax) * (py - ay) - (long long)(by - ay) * (px - ax);
-}
-__device__ __forceinline__ int edge32(int ax, int ay, int bx, int by, int px, int py) {
-  return (bx - ax) * (py - ay) - (by - ay) * (px - ax);
-}
 // Edge a -> b owns the samples on its line: a top edge or a left edge of a triangle of positive area.
 __device__ __forceinline__ bool owns(int ax, int ay, int bx, int by) {
   const int dy = by - ay, dx = bx - ax;
   return dy < 0 || (dy == 0 && dx > 0);
-}
-
-__device__ __forceinline__ unsigned rint_u8(double v) {
-  const double r = rint(v);
-  return !(r >= 0.0) ? 0u : (r > 255.0 ? 255u : (unsigned)r);          // not-a-number -> 0
 }
 
 // Grid (ceil(max nv / 256), meshes of the block): one thread per vertex.
@@ -131,7 +100,7 @@ __global__ __launch_bounds__(256) void zrender_normals_kernel(ZMeshBlock mb, con
     __syncthreads();                                                   // the list is rewritten by the next chunk
   }
   if (v < m.nv) {
-    double* out = (double*)(ws + L.normals) + ((size_t)m.v0 + v) * 3;
+    double* out = (double*)(ws + L.tail) + ((size_t)m.v0 + v) * 3;
     out[0] = nx; out[1] = ny; out[2] = nz;
   }
 }
@@ -148,9 +117,6 @@ __global__ __launch_bounds__(256) void zrender_setup_kernel(ZMeshBlock mb, const
   const double* vb = verts + (size_t)m.v0 * 3;
   ZFace* recs = (ZFace*)(ws + L.recs);
   int4* boxes = (int4*)(ws + L.boxes);
-  __shared__ int bx0, by0, bx1, by1, base;
-  if (tid == 0) { bx0 = INT_MAX; by0 = INT_MAX; bx1 = INT_MIN; by1 = INT_MIN; }
-  __syncthreads();
   int lx0 = INT_MAX, ly0 = INT_MAX, lx1 = INT_MIN, ly1 = INT_MIN;
   for (int j = tid; j < m.nf; j += 256) {
     const size_t fid = (size_t)m.f0 + j;
@@ -201,20 +167,7 @@ __global__ __launch_bounds__(256) void zrender_setup_kernel(ZMeshBlock mb, const
     recs[fid] = r;
     boxes[fid] = box;
   }
-  if (lx0 <= lx1) { atomicMin(&bx0, lx0); atomicMin(&by0, ly0); atomicMax(&bx1, lx1); atomicMax(&by1, ly1); }
-  __syncthreads();
-  const bool any = bx0 <= bx1;
-  const int tx0 = any ? bx0 / TILE : 0, ty0 = any ? by0 / TILE : 0;
-  const int ntx = any ? bx1 / TILE - tx0 + 1 : 0, nty = any ? by1 / TILE - ty0 + 1 : 0;
-  if (tid == 0) {
-    base = ntx * nty ? (int)atomicAdd((unsigned*)(ws + L.counter), (unsigned)(ntx * nty)) : 0;
-    ZMeshRec mr = {m.frame, m.f0, m.nf, 0};
-    ((ZMeshRec*)(ws + L.meshes))[mesh] = mr;
-  }
-  __syncthreads();
-  int2* items = (int2*)(ws + L.items);
-  for (int t = tid; t < ntx * nty; t += 256)
-    items[base + t] = make_int2(mesh, ((ty0 + t / ntx) << 16) | (tx0 + t % ntx));
+  emit_mesh_tiles(lx0, ly0, lx1, ly1, mesh, MeshRec{m.frame, m.f0, m.nf, 0}, ws, L);
 }
 
 __device__ __forceinline__ bool covered(long long e, bool own) { return e > 0 || (e == 0 && own); }
@@ -229,19 +182,16 @@ __device__ __forceinline__ float sample_depth(double e0, double e1, double e2, d
 // Grid-strided over the work list; one lane per pixel of a 16 x 16 tile.
 __global__ __launch_bounds__(256) void zrender_raster_kernel(int H, int W, char* __restrict__ ws, ZLayout L) {
   __shared__ ZTileFace s_face[256];
-  __shared__ int s_wave[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const unsigned count = *(const unsigned*)(ws + L.counter);
   const int2* items = (const int2*)(ws + L.items);
-  const ZMeshRec* meshes = (const ZMeshRec*)(ws + L.meshes);
+  const MeshRec* meshes = (const MeshRec*)(ws + L.meshes);
   const ZFace* recs = (const ZFace*)(ws + L.recs);
   const int4* boxes = (const int4*)(ws + L.boxes);
-  unsigned long long* keys = (unsigned long long*)(ws + L.keys);
-  const int tiles_x = (W + TILE - 1) / TILE, tiles = tiles_x * ((H + TILE - 1) / TILE);
   for (unsigned w = blockIdx.x; w < count; w += gridDim.x) {
     const int2 it = items[w];
-    const ZMeshRec m = meshes[it.x];
-    const int tx = it.y & 0xFFFF, ty = it.y >> 16;
+    const MeshRec m = meshes[it.x];
+    const int tx = tile_x(it.y), ty = tile_y(it.y);
     const int x0 = tx * TILE, y0 = ty * TILE;
     const int px = x0 + (tid & (TILE - 1)), py = y0 + (tid >> 4);
     const int sx = 256 * px + 128, sy = 256 * py + 128;                // the sample: the pixel's centre
@@ -249,23 +199,12 @@ __global__ __launch_bounds__(256) void zrender_raster_kernel(int H, int W, char*
     for (int c0 = 0; c0 < m.nf; c0 += 256) {
       // cull 256 faces against the tile into the LDS list
       const int j = c0 + tid;
-      bool hit = false;
-      if (j < m.nf) {
-        const int4 b = boxes[(size_t)m.f0 + j];
-        hit = b.x <= b.z && b.x <= x0 + TILE - 1 && b.z >= x0 && b.y <= y0 + TILE - 1 && b.w >= y0;
-      }
-      const unsigned long long mask = __ballot(hit);
-      const int before = __popcll(mask & ((1ull << lane) - 1));
-      if (lane == 0) s_wave[wave] = __popcll(mask);
-      __syncthreads();
-      int off = 0, n = 0;
-      for (int q = 0; q < 4; ++q) { off += q < wave ? s_wave[q] : 0; n += s_wave[q]; }
-      if (hit) {
+      const bool hit = j < m.nf && box_meets_tile(boxes[(size_t)m.f0 + j], x0, y0);
+      const int n = cull_to_lds(hit, [&](int slot) {
         const ZFace r = recs[(size_t)m.f0 + j];
         const ZTileFace t = {r.x0, r.y0, r.x1, r.y1, r.x2, r.y2, r.flags, j, r.area2, r.r0, r.r1, r.r2};
-        s_face[off + before] = t;
-      }
-      __syncthreads();
+        s_face[slot] = t;
+      });
       if (px < W && py < H) {
         for (int q = 0; q < n; ++q) {
           const ZTileFace& f = s_face[q];
@@ -293,10 +232,7 @@ __global__ __launch_bounds__(256) void zrender_raster_kernel(int H, int W, char*
       }
       __syncthreads();                                               // the list is rewritten by the next chunk
     }
-    if (best != NO_KEY) {
-      atomicMin(keys + ((size_t)m.view * H + py) * W + px, best);
-      ((unsigned char*)(ws + L.flags))[(size_t)m.view * tiles + ty * tiles_x + tx] = 1;
-    }
+    if (best != NO_KEY) commit_key(ws, L, ((size_t)m.view * H + py) * W + px, tile_index(m.view, tx, ty, H, W), best);
   }
 }
 
@@ -316,7 +252,7 @@ struct ZPixel { unsigned rgba; float depth; int mesh; };
 __device__ __forceinline__ ZPixel shade(unsigned long long key, int px, int py, const ZOut& o, const char* __restrict__ ws,
                                         const ZLayout& L) {
   const ZFace f = ((const ZFace*)(ws + L.recs))[(unsigned)key];
-  const double* nrm = (const double*)(ws + L.normals);
+  const double* nrm = (const double*)(ws + L.tail);
   const int sx = 256 * px + 128, sy = 256 * py + 128;
   const double e0 = (double)edge64(f.x1, f.y1, f.x2, f.y2, sx, sy), e1 = (double)edge64(f.x2, f.y2, f.x0, f.y0, sx, sy),
                e2 = (double)edge64(f.x0, f.y0, f.x1, f.y1, sx, sy);
@@ -344,28 +280,22 @@ template <int PX>
 __global__ __launch_bounds__(256) void zrender_resolve_kernel(ZOut o, int H, int W, char* __restrict__ ws, ZLayout L) {
   const int x = (blockIdx.x * 64 + threadIdx.x) * PX, y = blockIdx.y * 4 + threadIdx.y, n = blockIdx.z;
   if (x >= W || y >= H) return;
-  const int tiles_x = (W + TILE - 1) / TILE, tiles = tiles_x * ((H + TILE - 1) / TILE);
   const size_t p = ((size_t)n * H + y) * W + x;
+  const size_t tile = tile_index(n, x / TILE, y / TILE, H, W);         // PX divides TILE: a lane's pixels share a tile
   unsigned long long key[PX];
+  if (PX == 1) {
+    key[0] = take_key(ws, L, p, tile);
+  } else {
+    // take_key's rule (raster_tiles.h), 16 bytes at a time: flagged tiles only, and the four keys are reset if one was set
 #pragma unroll
-  for (int i = 0; i < PX; ++i) key[i] = NO_KEY;
-  if (((const unsigned char*)(ws + L.flags))[(size_t)n * tiles + (y / TILE) * tiles_x + x / TILE]) {   // PX divides TILE
-    unsigned long long* kp = (unsigned long long*)(ws + L.keys) + p;
-    bool any = false;
-    if (PX == 4) {
+    for (int i = 0; i < PX; ++i) key[i] = NO_KEY;
+    if (((const unsigned char*)(ws + L.flags))[tile]) {
+      unsigned long long* kp = (unsigned long long*)(ws + L.keys) + p;
       const ulonglong2 a = ((const ulonglong2*)kp)[0], b = ((const ulonglong2*)kp)[1];
-      key[0] = a.x; key[1] = a.y; key[2 % PX] = b.x; key[3 % PX] = b.y;
-    } else {
-      key[0] = kp[0];
-    }
-#pragma unroll
-    for (int i = 0; i < PX; ++i) any |= key[i] != NO_KEY;
-    if (any) {
-      if (PX == 4) {
+      key[0] = a.x; key[1 % PX] = a.y; key[2 % PX] = b.x; key[3 % PX] = b.y;
+      if ((a.x & a.y & b.x & b.y) != NO_KEY) {
         const ulonglong2 ff = make_ulonglong2(NO_KEY, NO_KEY);
         ((ulonglong2*)kp)[0] = ff; ((ulonglong2*)kp)[1] = ff;
-      } else {
-        kp[0] = NO_KEY;
       }
     }
   }
@@ -436,34 +366,9 @@ int check_args(int N, int H, int W, const double* K, const double* verts, int n_
       if (!(base_rgb[c] >= 0.0 && base_rgb[c] <= 1.0)) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: base_rgb outside [0, 1]");
   if (!out && !rgba && !depth && !mesh_id) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: no output requested");
   if ((frames == nullptr) != (out == nullptr)) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: frames and out are given both or neither");
-  const size_t fb = (size_t)N * H * W * 3;
-  if (frames && frames < out + fb && out < frames + fb) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: out overlaps frames (never in place)");
-  for (int i = 0; i < n_meshes; ++i) {
-    const hm_mesh& m = meshes[i];
-    if (m.frame < 0 || m.frame >= N) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: mesh view outside the batch");
-    if (m.nv < 0 || m.nf < 0 || m.v0 < 0 || m.f0 < 0) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: negative mesh range");
-    if (m.nv == 0 && m.nf > 0) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: a mesh with faces but no vertices");
-    if ((long long)m.v0 + m.nv > n_verts || (long long)m.f0 + m.nf > n_faces)
-      return hm_set_error(HM_ERR_ARG, "hm_mesh_render: mesh range outside the vertex or face array");
-  }
-  // a face id names one face of one mesh, and a vertex row carries one normal: neither range is shared by two meshes.
-  // Sorted by their first row, overlapping ranges are neighbours.
-  std::vector<int> order;
-  for (int i = 0; i < n_meshes; ++i) order.push_back(i);
-  std::sort(order.begin(), order.end(), [&](int a, int b) { return meshes[a].f0 < meshes[b].f0; });
-  long long end = 0;
-  for (int i : order) {
-    if (meshes[i].nf == 0) continue;
-    if (meshes[i].f0 < end) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: two meshes share faces");
-    end = (long long)meshes[i].f0 + meshes[i].nf;
-  }
-  std::sort(order.begin(), order.end(), [&](int a, int b) { return meshes[a].v0 < meshes[b].v0; });
-  end = 0;
-  for (int i : order) {
-    if (meshes[i].nv == 0) continue;
-    if (meshes[i].v0 < end) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: two meshes share vertices");
-    end = (long long)meshes[i].v0 + meshes[i].nv;
-  }
+  int rc = check_out_apart("hm_mesh_render", frames, out, (size_t)N * H * W * 3);
+  if (rc == HM_OK) rc = check_mesh_table("hm_mesh_render", "view", meshes, n_meshes, N, n_verts, n_faces, true);
+  if (rc != HM_OK) return rc;
   if (ws_bytes < layout(N, H, W, n_verts, n_meshes, n_faces).total) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: workspace too small");
   return HM_OK;
 }
@@ -504,11 +409,7 @@ extern "C" int hm_mesh_render(int N, int H, int W, const double* K_host, const d
       hipLaunchKernelGGL(zrender_normals_kernel, dim3((max_nv + 255) / 256, mb.count), dim3(256), 0, s, mb, verts, faces, ws, L);
     hipLaunchKernelGGL(zrender_setup_kernel, dim3(mb.count), dim3(256), 0, s, mb, verts, faces, H, W, znear, ws, L);
   }
-  if (n_meshes > 0) {
-    const size_t upper = (size_t)n_meshes * ((H + TILE - 1) / TILE) * ((W + TILE - 1) / TILE);
-    const int grid = (int)(upper < 2048 ? upper : 2048);
-    hipLaunchKernelGGL(zrender_raster_kernel, dim3(grid), dim3(256), 0, s, H, W, ws, L);
-  }
+  if (n_meshes > 0) hipLaunchKernelGGL(zrender_raster_kernel, dim3(raster_grid(n_meshes, H, W)), dim3(256), 0, s, H, W, ws, L);
   ZOut o;
   o.frames = frames; o.out = out; o.rgba = rgba; o.depth = depth; o.mesh_id = mesh_id;
   o.base[0] = base_rgb ? base_rgb[0] : 1.0; o.base[1] = base_rgb ? base_rgb[1] : 1.0; o.base[2] = base_rgb ? base_rgb[2] : 0.9;

@@ -220,6 +220,75 @@ def test_deterministic_order_independent_and_workspace_reuse(H, W):
         assert np.array_equal(np.where(solo["mesh_id"][0] >= 0, solo["mesh_id"][0] + first, -1), a["mesh_id"][n])
 
 
+def _exact(got, want):
+    """Every output byte equal to the rule's: labels, depth bits and colour."""
+    assert np.array_equal(got["mesh_id"], want["mesh_id"]), f"{int((got['mesh_id'] != want['mesh_id']).sum())} labels differ"
+    assert np.array_equal(got["depth"].view(np.uint32), want["depth"].view(np.uint32))
+    step = int(np.abs(got["rgba"].astype(int) - want["rgba"].astype(int)).max())
+    print("largest colour step", step)
+    assert np.array_equal(got["rgba"], want["rgba"]), f"colour differs by up to {step}"
+
+
+def test_more_meshes_than_one_setup_launch():
+    """50 small closed meshes in 2 views: the mesh table is walked in two argument blocks (48 + 2), so meshes 48 and 49 get
+    their rows from the second block's `first`.  Mesh 49 stands in front of mesh 0, and mesh 25 has 308 faces, so the raster
+    culls it in two chunks of 256."""
+    N, H, W, foc = 2, 48, 80, 100.0
+    K = np.array([[foc, 0, W / 2], [0, foc, H / 2], [0, 0, 1]])
+    meshes = []
+    for i in range(50):
+        v, f = _surface(nu=12, nv=14, size=0.09) if i == 25 else _surface(nu=4, nv=6, size=0.03 if i == 49 else 0.06)
+        a = 0.1 * i
+        Rx = np.array([[1, 0, 0], [0, np.cos(a), -np.sin(a)], [0, np.sin(a), np.cos(a)]])
+        slot = 0 if i == 49 else i // 2                                     # 7 x 4 places per view; mesh 49 on mesh 0's
+        z = 0.42 if i == 49 else 0.5 + 0.002 * i
+        cx, cy = 7 + 11 * (slot % 7), 7 + 11 * (slot // 7)
+        t = np.array([(cx - W / 2) * z / foc, (cy - H / 2) * z / foc, z])
+        meshes.append({"frame": 0 if i == 49 else i % 2, "vertices": v @ Rx.T + t, "faces": f})
+    assert len(meshes[25]["faces"]) > 256
+    got = _gpu(N, H, W, K, meshes)
+    want = ZR.render(N, H, W, K, _oracle_meshes(meshes))
+    seen = set(np.unique(want["mesh_id"]))
+    assert {0, 25, 47, 48, 49} <= seen and len(seen) >= 45
+    _exact(got, want)
+
+
+def test_both_renderers_share_one_key_buffer():
+    """overlay, z-buffer, overlay, z-buffer on one stream and one (N, H, W): the calls share the workspace's key buffer (the
+    second call allocates the larger workspace; the third and fourth find the keys the call before them left), each result
+    equals its own rule and the same call on a fresh workspace.  W % 4 != 0: the one-pixel resolve."""
+    import render_rule as RR
+    N, H, W = 3, 120, 161
+    meshes = _scene(N, H, W, 2, seed=11, scale=0.5)
+    frames = np.stack([synth.frame_u8(H, W, seed=20 + n).numpy() for n in range(N)])
+    fd = torch.from_numpy(frames).to(DEV)
+    render.release_workspaces()
+
+    def overlay():
+        return render.overlay_frames(fd, _K(H, W), meshes).cpu().numpy()
+
+    def zbuffer():
+        return _gpu(N, H, W, _K(H, W), meshes)
+    a1, z1, a2, z2 = overlay(), zbuffer(), overlay(), zbuffer()
+    assert len(render._ws) == 1
+    ws = next(iter(render._ws.values()))[0]
+    assert bool((ws[:N * H * W * 8] == 255).all())                        # every key written was reset
+    want_a = RR.overlay(frames, _K(H, W), [dict(m, color=(0, 255, 0)) for m in _oracle_meshes(meshes)])
+    want_z = ZR.render(N, H, W, _K(H, W), _oracle_meshes(meshes))
+    assert (want_a != frames).any() and (want_z["face"] >= 0).any()
+    render.release_workspaces()
+    fresh_a = overlay()
+    render.release_workspaces()
+    fresh_z = zbuffer()
+    render.release_workspaces()
+    for a in (a1, a2, fresh_a):
+        assert np.array_equal(a, want_a), f"{int((a != want_a).any(-1).sum())} pixels differ"
+    for z in (z1, z2):
+        for k in fresh_z:
+            assert np.array_equal(z[k].view(np.uint8), fresh_z[k].view(np.uint8))
+    _exact(fresh_z, want_z)
+
+
 def test_render_views_arguments():
     m = _hand(0, 0, 64, 96, 0.5, scale=0.2)
     with pytest.raises(ValueError):
