@@ -13,6 +13,10 @@ whose centred values are +-0.5 and whose rstd is exactly 1, so that y = sigma * 
 and the MXFP8 bytes and scales are those of the oracle quantiser; and a set of hostile rows with a per-row error bound for the
 accuracy test.
 
+The SAR hand-mesh head (section "SAR hand-mesh head") takes the GEMM integers through its seven GEMM entry points, with the
+bound of an fp16 output added (|acc + bias| <= 2048), and has data of its own for the soft-argmax (few-hot logits whose softmax
+is exactly 1 / m on a hashed support) and the post-processing (dyadic coordinates, transforms, roots and depth maps).
+
 Plain helper module (imported like sar_rule.py); torch-CPU only, nothing here touches the compiled library.
 """
 import torch
@@ -419,6 +423,268 @@ def tome_head_keys(metric, heads, dtype):
     qkv = torch.ones(B * T, 3, heads, hd)
     qkv[:, 1] = k
     return qkv.reshape(B * T, 3 * heads * hd).to(dtype)
+
+
+# ------------------------------------------------------------------------------------------------ SAR hand-mesh head
+# csrc/sar.hip (f16 operands, fp32 accumulation, f16 or fp32 out) and csrc/sar_f32.hip: 128 x 128 tiles, a K loop of 32.
+# SAIGB: (B, K): M = 6224 channels, N = 64 B positions (B = 1 is half an N tile, B = 3 a tile and a half); K = 512 runs through
+# hm_sar_saigb, hm_sar_saigb_ch and hm_sar_saigb_f32, K = 1024 through hm_sar_saigb_ch alone.
+SAR_NV, SAR_NJ, SAR_NT, SAR_CELLS, SAR_KG = 778, 21, 799, 1024, 544
+SAR_SAIGB = [(1, 512), (3, 512), (1, 1024), (3, 1024)]
+# L . X, M = K = 778: N = 8 (every column group of the f16 kernel clamps to column 0), one tile + 8, the two production
+# widths at B = 1, B = 5 ragged; N = 4 and 132 are the fp32 kernel's N % 4 granularity.  ldl: production and one that adds a
+# whole K step of zero Laplacian columns.
+SAR_MIX_N = [8, 136, 544, 1024, 2720]
+SAR_MIX_N_F32_ONLY = [4, 132]
+SAR_MIX_LDL = [800, 832]
+SAR_MIX_XROWS = 800                       # rows of the x buffer; rows 778 .. 799 hold NaN in the GPU test
+# fc (M, N, K): one row, one column, one K step; one row and two columns into the second tile; an odd number of K steps; the two
+# production layers; B = 3 rows with a ragged N
+SAR_FC = [(1, 1, 32), (129, 130, 64), (257, 136, 96), (778, 1024, 544), (778, 1024, 1024), (2334, 200, 544)]
+SAR_LEAKY = 0.1
+F16_EXACT_INT = 2048.0                    # every integer of magnitude <= 2048 is an fp16 value
+
+
+def sar_leaky(v):
+    """LeakyReLU(0.1) as one fp32 multiply of the exact fp32 v (nothing here can contract into an FMA)."""
+    assert v.dtype == torch.float32
+    return torch.where(v > 0, v, v * torch.tensor(SAR_LEAKY, dtype=torch.float32))
+
+
+def _f16_once(v):
+    """v rounded once to fp16; asserts that the integers it holds (the positive half, and v before the LeakyReLU) are fp16 values."""
+    h = v.half()
+    pos = v > 0
+    assert torch.equal(h.float()[pos], v[pos]) and float(v.abs().max()) <= F16_EXACT_INT
+    return h
+
+
+def sar_fc_case(M, N, K):
+    """gemm_case(M, N, K) and the four expected outputs of the fc kernels: x (M, K), w (N, K), bias (N,), then
+    {"f16_leaky": fp16, "f32": fp32 (hm_sar_linear out_f32 = 0 / 1), "f32_leaky", "f32_logits": fp32 (hm_sar_linear_f32 logits = 0 / 1)}."""
+    x, w, b, _ = gemm_case(M, N, K)
+    assert torch.equal(x.half().float(), x) and torch.equal(w.half().float(), w)
+    v = x @ w.t() + b
+    assert torch.equal(v.double(), x.double() @ w.double().t() + b.double())
+    assert float(v.abs().max()) <= F16_EXACT_INT and torch.equal(v.half().float(), v), (M, N, K)
+    lk = sar_leaky(v)
+    return x, w, b, {"f16_leaky": _f16_once(lk), "f32": v, "f32_leaky": lk, "f32_logits": v}
+
+
+def sar_graph(v, tmpl, B):
+    """The SAIGB epilogue's scatter: v (64 B, 6224) [position b * 64 + p][channel m] -> the node-major graph (778, B, 544):
+    channel m of position p of hand b at node m // 8, column (m % 8) * 64 + p; then the 3 template columns and 29 zeros."""
+    g = torch.zeros(SAR_NV, B, SAR_KG, dtype=v.dtype)
+    g[:, :, :512] = v.reshape(B, 64, SAR_NV, 8).permute(2, 0, 3, 1).reshape(SAR_NV, B, 512)
+    g[:, :, 512:515] = tmpl.to(v.dtype)[:, None, :]
+    return g
+
+
+def sar_saigb_case(B, K):
+    """feat (64 B, K) in -3..3 (NHWC rows), w (6224, K) in -2..2, bias (6224,) in -4..4 (gemm_case's x, w, bias), the template
+    (778, 3) in -4..4, v = feat w^T + bias (64 B, 6224) exact, and the expected graphs {"f16", "f32"} (778, B, 544)."""
+    M = 8 * SAR_NV
+    feat, w, b, _ = gemm_case(64 * B, M, K)
+    tmpl = ints("exact.sar.tmpl", (SAR_NV, 3), -4, 4, _shape_seed(B, K))
+    v = feat @ w.t() + b
+    assert float(v.abs().max()) <= F16_EXACT_INT and torch.equal(v.half().float(), v), (B, K)
+    lk = sar_leaky(v)
+    return feat, w, b, tmpl, v, {"f16": sar_graph(_f16_once(lk), tmpl, B), "f32": sar_graph(lk, tmpl, B)}
+
+
+def sar_mix_case(N, ldl):
+    """lap (778, ldl): a dense 778 x 778 of integers in -2..2 and zero columns 778 .. ldl - 1; x (778, N) in -3..3;
+    y = lap[:, :778] x (778, N), exact in fp32 and unchanged by fp16."""
+    assert ldl >= SAR_NV
+    sd = _shape_seed(SAR_NV, N)
+    lap = torch.zeros(SAR_NV, ldl)
+    lap[:, :SAR_NV] = ints("exact.sar.lap", (SAR_NV, SAR_NV), -2, 2, sd)
+    x = ints("exact.sar.x", (SAR_NV, N), -3, 3, sd)
+    assert exact_bound(lap, x, SAR_NV) < EXACT_LIMIT
+    y = lap[:, :SAR_NV] @ x
+    assert torch.equal(y.double(), lap[:, :SAR_NV].double() @ x.double())
+    assert float(y.abs().max()) <= F16_EXACT_INT and torch.equal(y.half().float(), y), (N, ldl)
+    return lap, x, y
+
+
+# ---- soft-argmax: "few-hot" logits.  Per (hand, vertex) row a hashed support of m in {1, 2, 4, .., 64} cells holds a hashed
+# integer level l in -3..3 and every other cell l - 256; with beta >= 1 exp(beta (v - max)) is 1 on the support and 0 elsewhere
+# (exp reaches fp32 zero at -104: 256 leaves a wide margin), p = 1 / m exactly and the three sums are short dyadic numbers in
+# any order; with beta = 0 the row is uniform, p = 1 / 1024.  z logits are hashed integers in -8..8 at every cell.
+SAR_SOFTARGMAX_B = [1, 3]
+SAR_FEWHOT_GAP = 256
+SAR_BETAS = [0.0, 1.0, 2.0, 4.0]
+# Goes into the seed of the dense mesh2pose weights.  A dense joint row is sum_v W[j, v] (row v): its logits differ between cells
+# by multiples of 256, so its softmax (beta >= 1) is uniform over the t cells that tie for the maximum.  With t = 3 or 5, 1 / t is
+# not an fp32 value and the z sum, of magnitude up to 500 (half an ulp: 1.5e-5), cannot be held to the test's 1e-5 by any fp32
+# kernel; the builder asserts that every such t is a power of two, and this is the first salt under which that holds at B = 1 and 3.
+SAR_M2P_SALT = 32
+
+
+def sar_fewhot_expect(lxy, lz, beta, wx, wy):
+    """Closed form of SoftHeatmap + the coordinate sums on few-hot rows, float64: lxy, lz (..., 1024), beta (...,) -> (..., 3).
+    The support of a row is where lxy is the row's maximum (every cell where beta = 0); asserts the gap to every other cell."""
+    lxy, lz, beta = lxy.double(), lz.double(), beta.double()
+    top = lxy.amax(-1, keepdim=True)
+    supp = (lxy == top) | (beta[..., None] == 0)
+    assert bool(((lxy <= top - SAR_FEWHOT_GAP) | supp).all()) and bool(((beta == 0) | (beta >= 1)).all())
+    cnt = supp.sum(-1).double()
+    mean = lambda t: (supp * t.double()).sum(-1) / cnt      # noqa: E731
+    out = torch.stack([mean(wx) / 16 - 1, mean(wy) / 16 - 1, mean(lz)], -1)
+    assert torch.equal(out.float().double(), out)
+    return out
+
+
+def sar_softmax_reference(lxy, lz, beta, wx, wy):
+    """The same in plain float64 softmax, for rows that are not few-hot: (..., 1024) -> (..., 3)."""
+    p = torch.softmax(lxy.double() * beta.double()[..., None], -1)
+    return torch.stack([(p * wx.double()).sum(-1) / 16 - 1, (p * wy.double()).sum(-1) / 16 - 1, (p * lz.double()).sum(-1)], -1)
+
+
+def sar_softargmax_case(B, m2p):
+    """Operands and expectations of hm_sar_softargmax.  m2p = 'dense': mesh2pose weights (21, 778) of hashed integers in -2..2;
+    'onehot': row j picks one hashed vertex v_j with weight 1; integer biases either way.  Returns a dict: lxy, lz (B, 778, 1024)
+    fp32; w_xy, b_xy, w_z, b_z; beta (799,), wx, wy (1024,); jxy, jz (B, 21, 1024) the exact integer joint logits; coords
+    (B, 799, 3) float64, fp32-representable in its exact part: all rows for 'onehot', rows 0..777 for 'dense', whose joint rows
+    are the float64 softmax of the joint logits."""
+    sd = _shape_seed(B, SAR_NT)
+    NV, NJ, C = SAR_NV, SAR_NJ, SAR_CELLS
+    m = torch.ldexp(torch.ones(B, NV), ints("exact.sar.m", (B, NV), 0, 6, sd).to(torch.int32)).long()
+    rank = torch.argsort(torch.argsort(ints("exact.sar.cells", (B, NV, C), 0, 1 << 20, sd), dim=2, stable=True), dim=2)
+    level = ints("exact.sar.level", (B, NV), -3, 3, sd)
+    lxy = torch.where(rank < m[..., None], level[..., None], level[..., None] - SAR_FEWHOT_GAP)
+    lz = ints("exact.sar.z", (B, NV, C), -8, 8, sd)
+    beta = torch.tensor(SAR_BETAS)[ints("exact.sar.beta", (SAR_NT,), 0, len(SAR_BETAS) - 1, 0).long()]
+    cell = torch.arange(C)
+    wx, wy = (cell % 32).float(), (cell // 32).float()
+    if m2p == "dense":
+        w_xy, w_z = ints("exact.sar.m2p.xy", (NJ, NV), -2, 2, SAR_M2P_SALT), ints("exact.sar.m2p.z", (NJ, NV), -2, 2, SAR_M2P_SALT)
+    else:
+        assert m2p == "onehot"
+        pick = ints("exact.sar.m2p.pick", (NJ,), 0, NV - 1, 0).long()
+        w_xy = torch.zeros(NJ, NV)
+        w_xy[torch.arange(NJ), pick] = 1.0
+        w_z = w_xy.clone()
+    b_xy, b_z = ints("exact.sar.m2p.bxy", (NJ,), -4, 4, 0), ints("exact.sar.m2p.bz", (NJ,), -4, 4, 0)
+    assert NV * float(w_xy.abs().max()) * float(lxy.abs().max()) + 4 < EXACT_LIMIT
+    jxy = torch.einsum("jv,bvc->bjc", w_xy, lxy) + b_xy[None, :, None]
+    jz = torch.einsum("jv,bvc->bjc", w_z, lz) + b_z[None, :, None]
+    assert torch.equal(jxy.double(), torch.einsum("jv,bvc->bjc", w_xy.double(), lxy.double()) + b_xy.double()[None, :, None])
+    assert torch.equal(jz.double(), torch.einsum("jv,bvc->bjc", w_z.double(), lz.double()) + b_z.double()[None, :, None])
+    vert = sar_fewhot_expect(lxy, lz, beta[:NV].expand(B, NV), wx, wy)
+    if m2p == "onehot":
+        joint = sar_fewhot_expect(jxy, jz, beta[NV:].expand(B, NJ), wx, wy)
+    else:
+        ties = (jxy == jxy.amax(-1, keepdim=True)).sum(-1)
+        assert bool(((ties & (ties - 1)) == 0)[:, beta[NV:] > 0].all()), ("tied maxima of a dense joint row", ties.tolist())
+        joint = sar_softmax_reference(jxy, jz, beta[NV:].expand(B, NJ), wx, wy)
+    return {"lxy": lxy, "lz": lz, "w_xy": w_xy, "b_xy": b_xy, "w_z": w_z, "b_z": b_z, "beta": beta, "wx": wx, "wy": wy,
+            "jxy": jxy, "jz": jz, "coords": torch.cat([vert, joint], 1)}
+
+
+# ---- hm_sar_postprocess on dyadic data: every product and sum below is exact in fp32 (and in the double uvd -> xyz step), so
+# neither FMA contraction nor operation order can change a bit.
+SAR_POST_B, SAR_POST_P = 5, 256
+SAR_POST_IMG = (1024, 512)                                         # width, height: the integer halves are powers of two
+SAR_POST_K = (1024.0, 512.0, 512.0, 256.0)                         # fx, fy, fu, fv
+SAR_POST_MAPS = [(7 + 16 * 8 + 5, 64, 32), (7, 16, 8)]            # (offset, width, height) of the two depth maps in one buffer
+SAR_POST_DEPTH_LEN = 7 + 16 * 8 + 5 + 64 * 32 + 3
+# per hand: bb2img (2 x 3), depth_box, flip, root, depth map (index into SAR_POST_MAPS or None), (u, v) of row 778 in patch
+# pixels, and where the un-flipped row 778 must land in its map: "inside", "border" (x0 = -1 or x0 + 1 = W) or "outside"
+SAR_POST_HANDS = [
+    dict(t=[[0.5, 0.0, 100.0], [0.0, 0.5, 40.0]], box=0.25, flip=0, root=0.625, map=0, uv=(208, 120), lands="inside"),
+    dict(t=[[1.0, 0.25, -30.0], [0.0, 1.0, 17.0]], box=0.5, flip=1, root=1.375, map=None, uv=(100, 60), lands=None),
+    dict(t=[[2.0, 0.0, 500.0], [0.25, 1.0, -9.0]], box=0.25, flip=1, root=0.875, map=1, uv=(252, 104), lands="border"),
+    dict(t=[[0.25, 0.5, 3.0], [0.5, 0.0, 64.0]], box=0.5, flip=0, root=2.5, map=0, uv=(-128, -128), lands="outside"),
+    dict(t=[[1.0, 0.0, 256.0], [0.0, 2.0, -100.0]], box=0.25, flip=0, root=0.3125, map=None, uv=(40, 360), lands=None),
+]
+
+
+def sar_bilinear(depth, W, H, gx, gy):
+    """grid_sample(bilinear, zeros, align_corners=False) of the (H, W) map at one normalised point, in float64; also returns
+    (x0, y0), the top-left cell of the footprint."""
+    import math
+    ix, iy = ((gx + 1) * W - 1) / 2, ((gy + 1) * H - 1) / 2
+    x0, y0 = math.floor(ix), math.floor(iy)
+    tx, ty = ix - x0, iy - y0
+    acc = 0.0
+    for dy in (0, 1):
+        for dx in (0, 1):
+            x, y = x0 + dx, y0 + dy
+            if 0 <= x < W and 0 <= y < H:
+                acc += (tx if dx else 1 - tx) * (ty if dy else 1 - ty) * float(depth[y * W + x])
+    return acc, (x0, y0)
+
+
+def sar_post_inputs():
+    """coords (5, 799, 3) fp32: xy hashed multiples of 1/64 in [-1, 1), z hashed multiples of 1/64 in [-8, 8], row 778's xy set so
+    that it lands where SAR_POST_HANDS says; depth: one buffer of hashed integers 0..15 holding both maps."""
+    B = SAR_POST_B
+    coords = torch.cat([ints("exact.sar.post.xy", (B, SAR_NT, 2), -64, 63, 0) / 64, ints("exact.sar.post.z", (B, SAR_NT, 1), -512, 512, 0) / 64], 2)
+    for b, h in enumerate(SAR_POST_HANDS):
+        coords[b, SAR_NV, 0], coords[b, SAR_NV, 1] = h["uv"][0] / SAR_POST_P - 0.5, h["uv"][1] / SAR_POST_P - 0.5
+    depth = ints("exact.sar.post.depth", (SAR_POST_DEPTH_LEN,), 0, 15, 0)
+    return coords, depth
+
+
+def sar_post_expect(coords, depth, hands=None, with_root=True, with_depth=True, fault=None):
+    """float64 statement of post_processing plus run's depth-image root for the hands of SAR_POST_HANDS (or `hands`):
+    -> uvd, xyz (B, 799, 3) float64 and the per-hand root.  `fault` (tests/test_exact_data_host.py) names one deliberate mistake."""
+    hands = SAR_POST_HANDS if hands is None else hands
+    Wi, Hi = SAR_POST_IMG
+    fx, fy, cu, cv = SAR_POST_K
+    P = SAR_POST_P
+    c = coords.double()
+    uvd, xyz, roots = torch.empty_like(c), torch.empty_like(c), []
+    for b, h in enumerate(hands):
+        t = torch.tensor(h["t"], dtype=torch.float64)
+        u, v = (c[b, :, 0] + 0.5) * P, (c[b, :, 1] + 0.5) * P
+        fu, fv = t[0, 0] * u + t[0, 1] * v + t[0, 2], t[1, 0] * u + t[1, 1] * v + t[1, 2]
+        r = h["root"] if with_root else 0.0
+        if h["map"] is not None and with_depth:
+            off, W, H = SAR_POST_MAPS[h["map"]]
+            off = h.get("off", off)
+            su, sv = float(fu[SAR_NV]), float(fv[SAR_NV])                 # row 778, NOT un-flipped
+            if fault == "row 778 un-flipped before sampling" and h["flip"]:
+                su = Wi - su - 1
+            gx, gy = su / (Wi // 2) - 1, sv / (Hi // 2) - 1
+            if fault == "x and y of the sample swapped":
+                gx, gy = gy, gx
+            if fault == "depth_w and depth_h swapped":
+                W, H = H, W
+            r, _ = sar_bilinear(depth[off:], W, H, gx, gy)
+        if h["flip"] and fault != "flip ignored":
+            fu = Wi - fu - 1
+        z = c[b, :, 2] * h["box"] + r
+        uvd[b] = torch.stack([fu, fv, z], 1)
+        xyz[b] = torch.stack([(fu - cu) * z / fx, (fv - cv) * z / fy, z], 1)
+        roots.append(r)
+    return uvd, xyz, roots
+
+
+def sar_post_case(with_root=True, with_depth=True):
+    """coords, depth, the hand table and the expected uvd, xyz (fp32).  Asserts that row 778 of each depth hand lands where
+    its entry says and that every expected value is an fp32 value."""
+    coords, depth = sar_post_inputs()
+    uvd, xyz, _ = sar_post_expect(coords, depth, with_root=with_root, with_depth=with_depth)
+    Wi, Hi = SAR_POST_IMG
+    seen = set()
+    for b, h in enumerate(SAR_POST_HANDS):
+        if h["map"] is None:
+            continue
+        off, W, H = SAR_POST_MAPS[h["map"]]
+        t = torch.tensor(h["t"], dtype=torch.float64)
+        su, sv = (t @ torch.tensor([h["uv"][0], h["uv"][1], 1.0], dtype=torch.float64)).tolist()
+        _, (x0, y0) = sar_bilinear(depth[off:], W, H, su / (Wi // 2) - 1, sv / (Hi // 2) - 1)
+        inx, iny = [0 <= x < W for x in (x0, x0 + 1)], [0 <= y < H for y in (y0, y0 + 1)]
+        lands = "inside" if all(inx) and all(iny) else "outside" if not (any(inx) and any(iny)) else "border"
+        assert lands == h["lands"], (b, lands, x0, y0)
+        assert lands != "border" or (x0 == -1 or x0 + 1 == W), (b, x0)
+        assert off + W * H <= SAR_POST_DEPTH_LEN
+        seen.add(lands)
+    assert seen == {"inside", "border", "outside"} and sum(h["flip"] for h in SAR_POST_HANDS) == 2
+    assert torch.equal(uvd.float().double(), uvd) and torch.equal(xyz.float().double(), xyz)
+    return coords, depth, SAR_POST_HANDS, uvd.float(), xyz.float()
 
 
 # ------------------------------------------------------------------------------------------------ the comparison

@@ -11,6 +11,10 @@ of the row kernels, slabs and bias of the accumulating one, layout and neighbour
 one sign per element, so a fault changes about half of what it moves: the bar is 40 % of the values and 20 % of the scale bytes.
 The error bound of the GPU accuracy test is measured and checked against wrong formulas here as well.
 
+The SAR hand-mesh head (section "SAR hand-mesh head") gets the GEMM catalogue at its own shapes plus the faults its kernels
+alone can make (the 32-wide K loop, the transposed read's halves, the SAIGB scatter), and catalogues of their own for the
+few-hot soft-argmax data and the dyadic post-processing data; the fp32 rule of tests/sar_rule.py must reproduce both closed forms.
+
 Large problems are checked on a 256 x 256 subset of the output spread evenly over the rows and columns (so over every tile);
 a fault is an index map, applied to the full operand's indices before the subset is taken.  A fault that is the identity
 map at a shape (a rotation of K-tiles when K is one tile, a flip of a 1 x 1 kernel) is no fault there and is passed over;
@@ -792,6 +796,317 @@ def test_ln_builders_refuse_data_that_is_not_exact(monkeypatch):
     monkeypatch.setattr(ED, "LN_PEAK_GAMMA", 4097)               # y needs more bits than bf16 has
     with pytest.raises(AssertionError):
         ED.ln_case(5, 96)
+
+
+# ------------------------------------------------------------------------------------------------ SAR hand-mesh head
+def k32_tiles_rotated(K):                      # the K loop of csrc/sar.hip and csrc/sar_f32.hip is 32 wide
+    k = _ar(K)
+    return ((k // 32 + 1) % (K // 32)) * 32 + k % 32 if K >= 64 else k
+
+
+def k32_tail_is_first(K):                      # the last 32 k read from the first 32's slot
+    k = _ar(K)
+    return torch.where(k >= K - 32, k % 32, k)
+
+
+def k_halves_of_8_swapped(K):                  # k rows q and q + 4 of a group of 8: the two transposed reads of the [K][N] operand
+    return _ar(K) ^ 4
+
+
+def _xor_inside(bits):
+    def fn(n):
+        m = _ar(n) ^ bits
+        return torch.where(m < n, m, _ar(n))
+    return fn
+
+
+# "W" is the NT operand [N][K]; for L . X it is the transpose of the row-major [K][N] operand: its rows are that operand's columns
+SAR_GEMM_FAULTS = [f for f in GEMM_FAULTS if f[1] != "resid"] + [
+    ("W: 32-wide K-tiles rotated by one", "w", 1, k32_tiles_rotated),
+    ("X: 32-wide K-tiles rotated by one", "x", 1, k32_tiles_rotated),
+    ("W: last 32 k replaced by the first 32", "w", 1, k32_tail_is_first),
+    ("X: last 32 k replaced by the first 32", "x", 1, k32_tail_is_first),
+    ("W: k rows q and q + 4 swapped inside groups of 8", "w", 1, k_halves_of_8_swapped),
+    ("W rows (columns of [K][N]) reversed inside groups of 4", "w", 0, _xor_inside(3)),
+    ("W rows (columns of [K][N]): the 4-wide blocks of a group of 16 reversed", "w", 0, _xor_inside(12)),
+    ("W rows (columns of [K][N]) rotated by 64", "w", 0, rotated(64)),
+]
+
+
+def _sar_gemm_catalogue(x, w, bias, finish, faults=None):
+    """The catalogue on finish(x w^T + bias), on the module's 256 x 256 spread of outputs: (faults met, faults below the bar)."""
+    faults = SAR_GEMM_FAULTS if faults is None else faults
+    ops = {"x": x, "w": w, "bias": bias}
+    rows, cols = _spread(x.shape[0]), _spread(w.shape[0])
+    sizes = {("x", 0): x.shape[0], ("x", 1): x.shape[1], ("w", 0): w.shape[0], ("w", 1): w.shape[1], ("bias", 0): w.shape[0]}
+    _, seen, low = _run_catalogue(faults, ops, lambda maps: finish(_gemm_sub(ops, rows, cols, maps)), sizes)
+    return seen, low
+
+
+def _f16_leaky(v):
+    return ED.sar_leaky(v).half()
+
+
+def test_sar_fc_data_sees_every_fault():
+    """Every fault changes more than half of the fp16 LeakyReLU outputs (the coarsest of the four outputs) at every fc shape where
+    it is not the identity; at (1, 1, 32) the single output must change."""
+    met = set()
+    for (M, N, K) in ED.SAR_FC:
+        x, w, b, ref = ED.sar_fc_case(M, N, K)
+        assert torch.equal(ref["f16_leaky"], _f16_leaky(x @ w.t() + b))
+        seen, low = _sar_gemm_catalogue(x, w, b, _f16_leaky)
+        assert not low, ((M, N, K), low)
+        met |= seen
+    assert met == {f[0] for f in SAR_GEMM_FAULTS}, {f[0] for f in SAR_GEMM_FAULTS} - met
+
+
+def test_sar_mix_data_sees_every_fault():
+    """L . X as x = the Laplacian (778, ldl) with its zero columns and w = the [K][N] operand transposed, its k rows 778 .. ldl - 1
+    being row 777 again, as the f16 kernel's clamp reads them (they meet the zero columns: the product is the same).  The K faults
+    act on all ldl k.  A fault of the [K][N] operand that moves none of its first 778 k rows is no fault, by the contract that
+    what lies past them never contributes (the last 32 k at ldl = 832), and is passed over there."""
+    met = set()
+    for ldl in ED.SAR_MIX_LDL:
+        for N in ED.SAR_MIX_N + ED.SAR_MIX_N_F32_ONLY:
+            lap, x, y = ED.sar_mix_case(N, ldl)
+            assert not lap[:, ED.SAR_NV:].any() and lap.shape == (ED.SAR_NV, ldl)
+            wt = x[_ar(ldl).clamp(max=ED.SAR_NV - 1)].t().contiguous()
+            assert torch.equal(lap @ wt.t(), y)
+            faults = [f for f in SAR_GEMM_FAULTS if not (f[1:3] == ("w", 1) and torch.equal(f[3](ldl)[:ED.SAR_NV], _ar(ED.SAR_NV)))]
+            assert len(SAR_GEMM_FAULTS) - len(faults) == (1 if ldl == 832 else 0)
+            seen, low = _sar_gemm_catalogue(lap, wt, None, lambda v: v, faults)
+            assert not low, ((N, ldl), low)
+            met |= seen
+    assert met == {f[0] for f in SAR_GEMM_FAULTS if f[1] != "bias"}, {f[0] for f in SAR_GEMM_FAULTS if f[1] != "bias"} - met
+
+
+def _saigb_graph_variant(v, bias, tmpl, B, fault):
+    """The fp16 graph (778, B, 544) with one mistake of the epilogue's scatter."""
+    NV = ED.SAR_NV
+    if fault == "bias indexed by n instead of m":
+        v = v - bias[None, :] + bias[:v.shape[0], None]
+    h = _f16_leaky(v)
+    if fault == "channels read as [8][778]":
+        g = ED.sar_graph(h, tmpl, B)
+        g[:, :, :512] = h.reshape(B, 64, 8, NV).permute(3, 0, 2, 1).reshape(NV, B, 512)
+        return g
+    if fault == "positions and hands transposed ([64][B])":
+        g = ED.sar_graph(h, tmpl, B)
+        g[:, :, :512] = h.reshape(64, B, NV, 8).permute(2, 1, 3, 0).reshape(NV, B, 512)
+        return g
+    if fault == "template rotated by one node":
+        return ED.sar_graph(h, tmpl.roll(1, 0), B)
+    g = ED.sar_graph(h, tmpl, B)
+    if fault == "hand-major rows":
+        return g.permute(1, 0, 2).contiguous().reshape(NV, B, ED.SAR_KG)
+    return g
+
+
+SAIGB_SCATTER_FAULTS = ["channels read as [8][778]", "positions and hands transposed ([64][B])", "hand-major rows",
+                        "template rotated by one node", "bias indexed by n instead of m"]
+
+
+def test_sar_saigb_data_sees_every_fault():
+    """The GEMM catalogue on feat w^T + bias at every (B, K), and the scatter's own faults on the whole graph: each changes more
+    than half of the live columns (of the template columns for the template fault).  The two hand faults are the identity at
+    B = 1 and are met at B = 3."""
+    met, met_scatter = set(), {}
+    for (B, K) in ED.SAR_SAIGB:
+        feat, w, b, tmpl, v, graphs = ED.sar_saigb_case(B, K)
+        ref = _saigb_graph_variant(v, b, tmpl, B, None)
+        assert torch.equal(ref, graphs["f16"]) and torch.equal(ED.sar_graph(ED.sar_leaky(v), tmpl, B), graphs["f32"])
+        assert not ref[:, :, 515:].any() and torch.equal(ref[:, 0, 512:515].float(), tmpl) and float(tmpl.abs().max()) == 4
+        seen, low = _sar_gemm_catalogue(feat, w, b, _f16_leaky)
+        assert not low, ((B, K), low)
+        met |= seen
+        for fault in SAIGB_SCATTER_FAULTS:
+            got = _saigb_graph_variant(v, b, tmpl, B, fault)
+            live = slice(512, 515) if fault.startswith("template") else slice(0, 515)
+            if torch.equal(got, ref):
+                assert B == 1 and fault in SAIGB_SCATTER_FAULTS[1:3], (B, K, fault)
+                continue
+            frac = float((got[:, :, live] != ref[:, :, live]).float().mean())
+            assert frac > HALF, (B, K, fault, frac)
+            met_scatter.setdefault(fault, set()).add(B)
+    assert met == {f[0] for f in SAR_GEMM_FAULTS}
+    assert met_scatter == {f: ({3} if f in SAIGB_SCATTER_FAULTS[1:3] else {1, 3}) for f in SAIGB_SCATTER_FAULTS}
+
+
+# ---- soft-argmax
+def _softargmax_model(c, fault=None):
+    """mesh2pose + SoftHeatmap + coordinate sums in float64 on the case's operands, with one mistake: (B, 799, 3)."""
+    lxy, lz = c["lxy"].double(), c["lz"].double()
+    B = lxy.shape[0]
+    w_xy, w_z, beta, wx, wy = c["w_xy"].double(), c["w_z"].double(), c["beta"], c["wx"], c["wy"]
+    if fault == "mesh2pose W transposed":
+        w_xy, w_z = (w.t().contiguous().reshape(w.shape) for w in (w_xy, w_z))
+    if fault == "mesh2pose W rotated by one vertex":
+        w_xy, w_z = w_xy.roll(1, 1), w_z.roll(1, 1)
+    full = [torch.cat([t, torch.einsum("jv,bvc->bjc", w, t) + b.double()[None, :, None]], 1)
+            for t, w, b in ((lxy, w_xy, c["b_xy"]), (lz, w_z, c["b_z"]))]
+    if fault == "hand and node transposed in the row address":              # the buffers are [799][B][1024]; row b * 799 + n is read
+        full = [t.permute(1, 0, 2).contiguous().reshape(B, ED.SAR_NT, ED.SAR_CELLS) for t in full]
+    if fault == "beta rotated by one node":
+        beta = beta.roll(1)
+    if fault is not None and fault.startswith("cells rotated by "):
+        by = int(fault.rsplit(" ", 1)[1])
+        wx, wy = wx.roll(-by), wy.roll(-by)
+    if fault == "the four cells of a lane reversed":
+        wx, wy = wx[_ar(ED.SAR_CELLS) ^ 3], wy[_ar(ED.SAR_CELLS) ^ 3]
+    out = ED.sar_softmax_reference(full[0], full[1], beta.expand(B, ED.SAR_NT), wx, wy)
+    if fault == "output triples node-major":                                # written at (n * B + b) * 3, read as [B][799][3]
+        out = out.permute(1, 0, 2).contiguous().reshape(B, ED.SAR_NT, 3)
+    return out
+
+
+# (fault, rows it can reach, bar on the fraction of (hand, node) triples it changes)
+SOFTARGMAX_FAULTS = [("cells rotated by 4", "all", HALF), ("cells rotated by 256", "all", HALF), ("cells rotated by 32", "all", HALF),
+                     ("the four cells of a lane reversed", "all", HALF), ("hand and node transposed in the row address", "all", HALF),
+                     ("output triples node-major", "all", HALF), ("mesh2pose W transposed", "joints", HALF),
+                     ("mesh2pose W rotated by one vertex", "joints", HALF), ("beta rotated by one node", "all", 0.25)]
+
+
+@pytest.mark.parametrize("m2p", ["dense", "onehot"])
+def test_sar_softargmax_data_sees_every_fault(m2p):
+    """Each fault changes more than half of the (hand, node) triples it can reach (the mesh2pose faults reach the 21 joint rows;
+    beta rotated by one node changes only rows whose beta moves to or from 0, 3/8 of them in expectation: the bar is a quarter);
+    cells rotated by 32 changes more than half of the y values.  The two hand / node faults are the identity at B = 1."""
+    met = {}
+    for B in ED.SAR_SOFTARGMAX_B:
+        c = ED.sar_softargmax_case(B, m2p)
+        ref = _softargmax_model(c)
+        assert float((ref - c["coords"]).abs().max()) < 1e-12                 # exp(-256) is not 0 in float64: 1e-111
+        for fault, reach, bar in SOFTARGMAX_FAULTS:
+            got = _softargmax_model(c, fault)
+            rows = slice(ED.SAR_NV, ED.SAR_NT) if reach == "joints" else slice(0, ED.SAR_NT)
+            if torch.equal(got, ref):
+                assert B == 1 and fault in ("hand and node transposed in the row address", "output triples node-major"), (B, fault)
+                continue
+            frac = float((got[:, rows] != ref[:, rows]).any(-1).float().mean())
+            assert frac > bar, (B, m2p, fault, frac)
+            if fault == "cells rotated by 32":
+                assert float((got[:, :, 1] != ref[:, :, 1]).float().mean()) > HALF
+            met.setdefault(fault, set()).add(B)
+    assert set(met) == {f[0] for f in SOFTARGMAX_FAULTS} and all(3 in v for v in met.values())
+
+
+def test_sar_softargmax_data_is_exact():
+    """The fp32 rule (tests/sar_rule.py: tail) reproduces the closed form bit for bit: every row of the one-hot case, the
+    vertex rows of the dense one (its joint rows within 1e-6); the supports are spread: most rows have their own (x, y)."""
+    import sar_rule as R
+    for m2p, B in (("dense", 1), ("dense", 3), ("onehot", 3)):
+        c = ED.sar_softargmax_case(B, m2p)
+        sd = {"head.gbbmr.mesh2pose_hm.weight": c["w_xy"], "head.gbbmr.mesh2pose_hm.bias": c["b_xy"],
+              "head.gbbmr.mesh2pose_dm.weight": c["w_z"], "head.gbbmr.mesh2pose_dm.bias": c["b_z"],
+              "head.gbbmr.soft_heatmap.beta.weight": c["beta"], "head.gbbmr.soft_heatmap.wx": c["wx"].view(32, 32),
+              "head.gbbmr.soft_heatmap.wy": c["wy"].view(32, 32)}
+        got = R.tail(sd, c["lxy"], c["lz"]).double()
+        exact = slice(0, ED.SAR_NT if m2p == "onehot" else ED.SAR_NV)
+        assert torch.equal(got[:, exact], c["coords"][:, exact]), m2p
+        assert float((got - c["coords"]).abs().max()) < 1e-6
+        xy = c["coords"][:, :ED.SAR_NV, :2].reshape(-1, 2)
+        assert len({tuple(r) for r in xy.tolist()}) > HALF * xy.shape[0]         # (the quarter of the rows with beta = 0 share one answer)
+        assert set(c["beta"].tolist()) == set(ED.SAR_BETAS) and set(c["beta"][ED.SAR_NV:].tolist()) == set(ED.SAR_BETAS)
+
+
+# ---- post-processing
+def _post_hands(**change):
+    """SAR_POST_HANDS with each field named in `change` taken from the next hand: hand b gets that of hand b + 1."""
+    hands = [dict(h) for h in ED.SAR_POST_HANDS]
+    n = len(hands)
+    for k in change:
+        for b in range(n):
+            hands[b][k] = ED.SAR_POST_HANDS[(b + 1) % n][k]
+    return hands
+
+
+def _post_neighbour_offsets():
+    """Every hand with a map takes the depth offset of the next hand with a map (its own width and height)."""
+    hands = [dict(h) for h in ED.SAR_POST_HANDS]
+    with_map = [b for b, h in enumerate(hands) if h["map"] is not None]
+    for i, b in enumerate(with_map):
+        hands[b]["off"] = ED.SAR_POST_MAPS[hands[with_map[(i + 1) % len(with_map)]]["map"]][0]
+    return hands
+
+
+def test_sar_post_data_sees_every_fault():
+    """Each fault changes more than half of the values it can reach: (hands, columns of [u, v, d, x, y, z]).  A root reaches d and
+    all of xyz; the flip reaches u and x; the sampling faults reach the hands whose row 778 lands inside or across a border of
+    its map (outside, every variant samples 0)."""
+    coords, depth, hands, uvd, xyz = ED.sar_post_case()
+    ref = torch.cat([uvd, xyz], 2).double()
+    B = ED.SAR_POST_B
+    flipped = [b for b, h in enumerate(hands) if h["flip"]]
+    rooted = [b for b, h in enumerate(hands) if h["map"] is None]
+    sampled = [b for b, h in enumerate(hands) if h["lands"] in ("inside", "border")]
+    assert len(flipped) == 2 and len(rooted) == 2 and len(sampled) == 2 and set(flipped) & set(sampled) and set(flipped) & set(rooted)
+    Z = [2, 3, 4, 5]
+    every = {k: True for k in ("t", "box", "flip", "map")}      # the fields of hm_sar_hand; root[b] and the coordinates stay
+    table = [
+        ("hand structs rotated by one", dict(hands=_post_hands(**every)), range(B), range(6)),
+        ("root rotated", dict(hands=_post_hands(root=True)), rooted, Z),
+        ("flip ignored", dict(fault="flip ignored"), flipped, [0, 3]),
+        ("row 778 un-flipped before sampling", dict(fault="row 778 un-flipped before sampling"), sorted(set(flipped) & set(sampled)), Z),
+        ("depth offset of the neighbouring hand", dict(hands=_post_neighbour_offsets()), sampled, Z),
+        ("x and y of the sample swapped", dict(fault="x and y of the sample swapped"), sampled, Z),
+        ("depth_w and depth_h swapped", dict(fault="depth_w and depth_h swapped"), sampled, Z),
+    ]
+    for name, kw, hs, cols in table:
+        u2, x2, _ = ED.sar_post_expect(coords, depth, **kw)
+        got = torch.cat([u2, x2], 2)
+        frac = float((got[list(hs)][:, :, list(cols)] != ref[list(hs)][:, :, list(cols)]).float().mean())
+        assert frac > HALF, (name, frac)
+    # with neither, or with one source taken away, the roots are the ones the GPU test expects
+    assert ED.sar_post_expect(coords, depth, with_depth=False)[2] == [h["root"] for h in hands]
+    r = ED.sar_post_expect(coords, depth, with_root=False)[2]
+    assert [r[b] for b in rooted] == [0.0, 0.0] and r[[b for b, h in enumerate(hands) if h["lands"] == "outside"][0]] == 0.0
+    assert all(r[b] > 0 for b in sampled) and len({h["root"] for h in hands}) == B
+
+
+def test_sar_post_data_is_exact():
+    """The float64 formulas of ED.sar_post_expect are fp32 values (asserted by the builder) and are reproduced by the fp32 rule
+    (tests/sar_rule.py: post_process) bit for bit, the sampled roots by F.grid_sample in float64 on the un-flipped row 778."""
+    import numpy as np
+    import sar_rule as R
+    Wi, Hi = ED.SAR_POST_IMG
+    fx, fy, cu, cv = ED.SAR_POST_K
+    K = np.array([[fx, 0, cu], [0, fy, cv], [0, 0, 1]])
+    for with_root, with_depth in ((True, True), (True, False), (False, True)):
+        coords, depth, hands, uvd, xyz = ED.sar_post_case(with_root, with_depth)
+        _, _, roots = ED.sar_post_expect(coords, depth, with_root=with_root, with_depth=with_depth)
+        for b, h in enumerate(hands):
+            t = np.array(h["t"], np.float32)
+            if h["map"] is not None and with_depth:
+                off, W, H = ED.SAR_POST_MAPS[h["map"]]
+                fu, fv = (torch.tensor(h["t"], dtype=torch.float64) @ torch.tensor([h["uv"][0], h["uv"][1], 1.0], dtype=torch.float64)).tolist()
+                grid = torch.tensor([[[[fu / (Wi // 2) - 1, fv / (Hi // 2) - 1]]]], dtype=torch.float64)
+                d = depth[off:off + W * H].double().reshape(1, 1, H, W)
+                assert float(F.grid_sample(d, grid, mode="bilinear", padding_mode="zeros", align_corners=False)) == roots[b], b
+            assert np.float32(roots[b]) == roots[b]
+            out = R.post_process(coords[b].numpy(), np.float32(roots[b]), t, K, Wi, bool(h["flip"]), depth_box=h["box"], P=ED.SAR_POST_P)
+            assert out["mesh_uvd"].dtype == np.float32 and out["mesh_xyz"].dtype == np.float32
+            assert np.array_equal(np.concatenate([out["mesh_uvd"], out["pose_uvd"]]), uvd[b].numpy()), b
+            assert np.array_equal(np.concatenate([out["mesh_xyz"], out["pose_xyz"]]), xyz[b].numpy()), b
+
+
+def test_sar_builders_refuse_data_that_is_not_exact(monkeypatch):
+    monkeypatch.setattr(ED, "F16_EXACT_INT", 256.0)              # the production fc sums pass 256
+    with pytest.raises(AssertionError):
+        ED.sar_fc_case(778, 1024, 1024)
+    with pytest.raises(AssertionError):
+        ED.sar_mix_case(544, 800)
+    monkeypatch.undo()
+    monkeypatch.setattr(ED, "SAR_BETAS", [0.0, 0.25, 0.5, 1.0])  # beta (l - 256 - l) = -64: exp is no longer 0
+    with pytest.raises(AssertionError):
+        ED.sar_softargmax_case(1, "onehot")
+    monkeypatch.undo()
+    monkeypatch.setattr(ED, "SAR_M2P_SALT", 0)                   # a dense joint row with three tied maxima
+    with pytest.raises(AssertionError):
+        ED.sar_softargmax_case(1, "dense")
+    monkeypatch.undo()
+    monkeypatch.setattr(ED, "SAR_POST_K", (1000.0, 512.0, 512.0, 256.0))      # a focal length that is no power of two
+    with pytest.raises(AssertionError):
+        ED.sar_post_case()
 
 
 # ------------------------------------------------------------------------------------------------ the data and the report
