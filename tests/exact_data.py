@@ -17,8 +17,14 @@ The SAR hand-mesh head (section "SAR hand-mesh head") takes the GEMM integers th
 bound of an fp16 output added (|acc + bias| <= 2048), and has data of its own for the soft-argmax (few-hot logits whose softmax
 is exactly 1 / m on a hashed support) and the post-processing (dyadic coordinates, transforms, roots and depth maps).
 
-Plain helper module (imported like sar_rule.py); torch-CPU only, nothing here touches the compiled library.
+The kernels behind the networks (sections "MANO tail", "Detect decode", "RootNet layout kernels") have data and rules of their
+own: a dyadic MANO model with signed-permutation rotations, for which mano_rule asserts stage by stage that every sum is exact
+in any order; three-valued logits whose fp32 sigmoid is exactly 1/2, 1 or 0 for the decode; integer features over a
+power-of-two HW for the pooled linear layer; values every output type holds for the two layout kernels.
+
+Plain helper module (imported like sar_rule.py); torch and numpy on the CPU only, nothing here touches the compiled library.
 """
+import numpy as np
 import torch
 
 from hamer_yolo_amd import synth
@@ -685,6 +691,456 @@ def sar_post_case(with_root=True, with_depth=True):
     assert seen == {"inside", "border", "outside"} and sum(h["flip"] for h in SAR_POST_HANDS) == 2
     assert torch.equal(uvd.float().double(), uvd) and torch.equal(xyz.float().double(), xyz)
     return coords, depth, SAR_POST_HANDS, uvd.float(), xyz.float()
+
+
+# ------------------------------------------------------------------------------------------------ MANO tail
+# csrc/mano.hip on a dyadic model: every model parameter is a hashed integer over a power-of-two quantum, betas are small
+# integers and every joint rotation is one of the 24 proper signed-permutation matrices, so every intermediate of the kernel
+# is an fp32 value whatever the order of a sum and with or without FMA contraction.  mano_rule states the operation in
+# float64 and asserts exactly that, stage by stage; the camera tail is the kernel's sequence of single fp32 operations.
+MANO_B = [1, 5, 67]
+MANO_V = [745, 778, 800]                  # the API's edges (744 < n_verts <= 800) and MANO's own count
+MANO_NCHUNK = 4                           # workgroups (vertex ranges) per hand
+MANO_TIP_OWNER = (3, 1, 2, 2, 3)          # the range that skins tip vertex (744, 320, 443, 554, 671), the same at all three V
+MANO_FOCAL, MANO_IMAGE = 5000.0, 256.0
+MANO_C0 = 625.0 / 16.0                    # image_size * c0 = 10000 / 2^m: the + 1e-9f is absorbed and tz = 2^m
+MANO_DEGENERATE = (5, 778)                # (B, V) of the degenerate-pose case
+MANO_DEGENERATE_JOINTS = {"a1 = 0": (0, 4), "a2 = t a1": (0, 8)}       # (hand, joint)
+MANO_T = [0.5, -0.5, 1.0, -1.0, 1.5, -1.5, 3.0, -3.0]
+MANO_LBS_PATTERNS = [[1.0, 0.0, 0.0, 0.0], [0.5, 0.5, 0.0, 0.0], [0.5, 0.25, 0.25, 0.0], [0.25, 0.25, 0.25, 0.25]]
+F32_TINY = float(np.float32(1e-12))       # the kernel's norm floor, 1e-12f
+MANO_FAULTS = ["wrong parent table", "joint map rotated", "tips off by one", "posedirs as [3V][135]", "shapedirs as [10][3V]",
+               "rotation transposed", "pose feature from joint 0", "lbs_weights as [16][V]", "joints from v_posed", "A without G J",
+               "one range unposed", "child before parent", "cam columns rotated"]
+MANO_UNPOSED_RANGE = 1
+
+
+def mano_ranges(V):
+    """The four vertex ranges of the kernel: [k * ceil(V / 4), min(V, (k + 1) * ceil(V / 4)))."""
+    vper = (V + MANO_NCHUNK - 1) // MANO_NCHUNK
+    return [(k * vper, min(V, (k + 1) * vper)) for k in range(MANO_NCHUNK)]
+
+
+def mano_rotation_table():
+    """The 24 proper signed-permutation matrices as (i, s1, j, s2): columns b1 = s1 e_i, b2 = s2 e_j, b3 = b1 x b2; and which of
+    them are symmetric (10 are: a transposed matrix passes on those)."""
+    table = [(i, s1, (i + dj) % 3, s2) for i in range(3) for dj in (1, 2) for s1 in (1, -1) for s2 in (1, -1)]
+    sym = []
+    for i, s1, j, s2 in table:
+        b1, b2 = torch.zeros(3), torch.zeros(3)
+        b1[i], b2[j] = s1, s2
+        m = torch.stack([b1, b2, torch.linalg.cross(b1, b2)], 1)
+        assert abs(float(torch.linalg.det(m)) - 1) < 1e-6
+        sym.append(bool(torch.equal(m, m.t())))
+    return table, sym
+
+
+def mano_exact_model(V, seed=0):
+    """v_template k / 64 (|k| <= 8), shapedirs k / 64 (|k| <= 2), posedirs k / 64 (|k| <= 1); a J_regressor row is eight hashed
+    vertices of weight 1 / 8; an lbs_weights row is one of MANO_LBS_PATTERNS on four hashed joints (weights add where they meet)."""
+    sd = _shape_seed(V, seed)
+    mp = {"v_template": ints("exact.mano.vt", (V, 3), -8, 8, sd) / 64, "shapedirs": ints("exact.mano.sd", (V, 3, 10), -2, 2, sd) / 64,
+          "posedirs": ints("exact.mano.pd", (135, 3 * V), -1, 1, sd) / 64}
+    pick = ints("exact.mano.jreg", (16, 8), 0, V - 1, sd).long()
+    mp["J_regressor"] = torch.zeros(16, V).scatter_add_(1, pick, torch.full((16, 8), 0.125))
+    pat = torch.tensor(MANO_LBS_PATTERNS)[ints("exact.mano.lbs.pattern", (V,), 0, 3, sd).long()]
+    mp["lbs_weights"] = torch.zeros(V, 16).scatter_add_(1, ints("exact.mano.lbs.joint", (V, 4), 0, 15, sd).long(), pat)
+    assert torch.equal(mp["J_regressor"].sum(1), torch.ones(16)) and torch.equal(mp["lbs_weights"].sum(1), torch.ones(V))
+    owner = tuple(next(k for k, (lo, hi) in enumerate(mano_ranges(V)) if lo <= t < hi) for t in synth.MANO_TIP_VERTS)
+    assert owner == MANO_TIP_OWNER and V > max(synth.MANO_TIP_VERTS), (V, owner)
+    assert V != 745 or synth.MANO_TIP_VERTS[0] == mano_ranges(V)[3][1] - 1        # tip 744: the last vertex of the last workgroup
+    return mp
+
+
+def mano_exact_case(B, V, seed=0, degenerate=False):
+    """(model, pose6d (B, 96), betas (B, 10), cam (B, 3), rot (B, 16) indices into mano_rotation_table).  Joint (b, j) takes a
+    hashed rotation -- three in four from the 14 asymmetric ones -- that differs from every ancestor's in its finger and from
+    hand b - 1's at the same joint, so hands 0 and 1 differ at every level of every finger and no parent / child mix-up is
+    absorbed.  Its 6-D code is not normalised: a1 = s1 2^p e_i, a2 = s2 2^q e_j + t e_i with t != 0 on a hashed half.  cam:
+    c0 = MANO_C0 / 2^m, c1 and c2 multiples of 1 / 64; the last row of a batch has c0 = 0 (a lone hand keeps an ordinary
+    camera).  degenerate: MANO_DEGENERATE_JOINTS get a1 = 0 (and t = 0) and a2 = 1.5 a1."""
+    sd = _shape_seed(B, V, seed)
+    table, sym = mano_rotation_table()
+    asym = [k for k in range(24) if not sym[k]]
+    h = ints("exact.mano.rot", (B, 16), 0, (1 << 20) - 1, sd).long().tolist()
+    rot = [[0] * 16 for _ in range(B)]
+    for b in range(B):
+        for j in range(16):
+            cand = list(range(24)) if h[b][j] % 4 == 0 else asym
+            banned, a = set(), synth.MANO_PARENTS[j]
+            while a >= 0:
+                banned.add(rot[b][a])
+                a = synth.MANO_PARENTS[a]
+            if b:
+                banned.add(rot[b - 1][j])
+            k = (h[b][j] // 4) % len(cand)
+            while cand[k] in banned:
+                k = (k + 1) % len(cand)
+            rot[b][j] = cand[k]
+    p = ints("exact.mano.p", (B, 16), -1, 2, sd)
+    q = ints("exact.mano.q", (B, 16), -2, 1, sd)
+    t = torch.tensor(MANO_T)[ints("exact.mano.t", (B, 16), 0, len(MANO_T) - 1, sd).long()] * ints("exact.mano.t.on", (B, 16), 0, 1, sd)
+    pose = torch.zeros(B, 16, 6)
+    for b in range(B):
+        for j in range(16):
+            i, s1, jj, s2 = table[rot[b][j]]
+            pose[b, j, i] = s1 * 2.0 ** float(p[b, j])
+            pose[b, j, 3 + jj] = s2 * 2.0 ** float(q[b, j])
+            pose[b, j, 3 + i] = t[b, j]
+    if degenerate:
+        b, j = MANO_DEGENERATE_JOINTS["a1 = 0"]
+        pose[b, j, :3] = 0.0
+        pose[b, j, 3 + table[rot[b][j]][0]] = 0.0
+        b, j = MANO_DEGENERATE_JOINTS["a2 = t a1"]
+        pose[b, j, 3:] = 1.5 * pose[b, j, :3]
+    else:
+        assert float((t != 0).float().mean()) > 0.25 or B == 1
+    betas = ints("exact.mano.betas", (B, 10), -2, 2, sd)
+    cam = torch.cat([MANO_C0 / 2.0 ** ints("exact.mano.cam.m", (B, 1), 0, 3, sd), ints("exact.mano.cam.xy", (B, 2), -64, 64, sd) / 64], 1)
+    if B > 1:
+        cam[B - 1, 0] = 0.0
+    return mano_exact_model(V, seed), pose.reshape(B, 96), betas, cam, torch.tensor(rot)
+
+
+def _stage(exact, what, q, eq, *factors, add=()):
+    """einsum(eq, factors) + the addends, in float64.  With `exact` it asserts what makes an fp32 kernel's result the same in any
+    summation order and with or without FMA contraction: every factor is a multiple of its own quantum, the product of those
+    quanta and every addend a multiple of q -- so every term of every sum is a multiple of q -- and sum |terms| / q < 2^24."""
+    val = torch.einsum(eq, *[t for t, _ in factors])
+    for a in add:
+        val = val + a
+    if exact:
+        qq = 1.0
+        for t, qt in factors:
+            assert torch.equal(t / qt, (t / qt).round()), (what, "a factor off its quantum", qt)
+            qq *= qt
+        assert (qq / q) == round(qq / q) and qq >= q, (what, qq, q)
+        mag = torch.einsum(eq, *[t.abs() for t, _ in factors])
+        for a in add:
+            assert torch.equal(a / q, (a / q).round()), (what, "an addend off the quantum", q)
+            mag = mag + a.abs()
+        assert float(mag.max()) / q < EXACT_LIMIT, (what, float(mag.max()) / q)
+    return val
+
+
+def mano_rot6d_rule(pose6d, exact=True):
+    """The kernel's Gram-Schmidt step by step in float64 -> (N, 3, 3), columns (b1, b2, b1 x b2); norms floored at 1e-12f.
+    `exact`: every squared norm is 0 or the square of an fp32 number, and every value on the way is an fp32 value."""
+    x = pose6d.double().reshape(-1, 6)
+    a1, a2 = x[:, :3], x[:, 3:]
+
+    def unit(v, what):
+        ss = (v * v).sum(1, keepdim=True)
+        n = ss.sqrt()
+        if exact:
+            assert torch.equal(n * n, ss) and torch.equal(n.float().double(), n) and float(ss.max()) * 2.0 ** 16 < EXACT_LIMIT, what
+            assert torch.equal(v * v * 2.0 ** 16, (v * v * 2.0 ** 16).round()), what
+        out = v / n.clamp_min(F32_TINY)
+        assert not exact or torch.equal(out.float().double(), out), what
+        return out
+
+    b1 = unit(a1, "a1")
+    d = (b1 * a2).sum(1, keepdim=True)
+    u = a2 - d * b1
+    if exact:
+        for t in (b1 * a2, d, d * b1, u):
+            assert torch.equal(t * 256, (t * 256).round()) and float(t.abs().max()) * 256 < EXACT_LIMIT
+    b2 = unit(u, "a2 - (b1 . a2) b1")
+    return torch.stack([b1, b2, torch.linalg.cross(b1, b2, dim=1)], -1) + 0.0       # + 0.0: no negative zeros
+
+
+def mano_rule(mp, pose6d, betas, cam, focal=MANO_FOCAL, image_size=MANO_IMAGE, fault=None, exact=True):
+    """hm_mano_forward stated plainly -> fp32 rotmats (B, 16, 3, 3), verts (B, V, 3), joints (B, 21, 3), cam_t (B, 3),
+    kp2d (B, 21, 2).  Everything up to the joints is float64 through _stage, which (exact=True) asserts the exactness of
+    v_shaped, J, the pose feature, v_posed, the chain, A, the blended transform and the skinned vertex.  The camera tail is the
+    kernel's own sequence of single, correctly rounded fp32 operations in numpy.float32: tz = 2 focal / (image_size c0 + 1e-9f)
+    (the product is exact on this data, so a contracted FMA rounds the same), px = jx + c1, pz = jz + tz,
+    (px / pz) * (focal / image_size).  `fault` names one deliberate mistake of MANO_FAULTS (tests/test_exact_data_host.py)."""
+    assert fault is None or fault in MANO_FAULTS
+    B, V = pose6d.shape[0], mp["v_template"].shape[0]
+    vt, sd, pd, jr, w = (mp[k].double() for k in ("v_template", "shapedirs", "posedirs", "J_regressor", "lbs_weights"))
+    if fault == "posedirs as [3V][135]":
+        pd = pd.reshape(3 * V, 135).t()
+    if fault == "shapedirs as [10][3V]":
+        sd = sd.reshape(10, 3 * V).t().reshape(V, 3, 10)
+    if fault == "lbs_weights as [16][V]":
+        w = w.reshape(16, V).t()
+    parents = list(range(-1, 15)) if fault == "wrong parent table" else synth.MANO_PARENTS
+    R = mano_rot6d_rule(pose6d, exact).reshape(B, 16, 3, 3)
+    if fault == "rotation transposed":
+        R = R.transpose(-1, -2)
+    eye = torch.eye(3, dtype=torch.float64)
+    vs = _stage(exact, "v_shaped", 1 / 64, "vcl,bl->bvc", (sd, 1 / 64), (betas.double(), 1.0), add=(vt[None],))
+    first = 0 if fault == "pose feature from joint 0" else 1
+    pf = _stage(exact, "pose feature", 1.0, "bjrc->bjrc", (R[:, first:first + 15], 1.0), add=(-eye.expand(B, 15, 3, 3),)).reshape(B, 135)
+    vp = _stage(exact, "v_posed", 1 / 64, "bp,po->bo", (pf, 1.0), (pd, 1 / 64), add=(vs.reshape(B, 3 * V),)).reshape(B, V, 3)
+    if fault == "one range unposed":
+        lo, hi = mano_ranges(V)[MANO_UNPOSED_RANGE]
+        vp[:, lo:hi] = vs[:, lo:hi]
+    J = _stage(exact, "J", 1 / 512, "jv,bvc->bjc", (jr, 1 / 8), (vp if fault == "joints from v_posed" else vs, 1 / 64))
+    GR, Gt = [None] * 16, [None] * 16
+    for j in range(16):
+        par = parents[j]
+        if par < 0:
+            GR[j], Gt[j] = R[:, j], J[:, j]
+            continue
+        pR, pt = (eye.expand(B, 3, 3), torch.zeros(B, 3, dtype=torch.float64)) if fault == "child before parent" else (GR[par], Gt[par])
+        rel = _stage(exact, "J - J[parent]", 1 / 512, "bc->bc", (J[:, j], 1 / 512), add=(-J[:, par],))
+        GR[j] = _stage(exact, "chain rotation", 1.0, "bik,bkc->bic", (pR, 1.0), (R[:, j], 1.0))
+        Gt[j] = _stage(exact, "chain translation", 1 / 512, "bik,bk->bi", (pR, 1.0), (rel, 1 / 512), add=(pt,))
+    GR, Gt = torch.stack(GR, 1), torch.stack(Gt, 1)
+    At = Gt if fault == "A without G J" else _stage(exact, "A", 1 / 512, "bjik,bjk->bji", (GR, 1.0), (-J, 1 / 512), add=(Gt,))
+    A = torch.cat([GR, At[..., None]], -1).reshape(B, 16, 12)
+    T = _stage(exact, "blended transform", 1 / 2048, "vj,bje->bve", (w, 1 / 4), (A, 1 / 512)).reshape(B, V, 3, 4)
+    verts = _stage(exact, "skinned vertex", 1 / 2048, "bvik,bvk->bvi", (T[..., :3], 1 / 4), (vp, 1 / 64), add=(T[..., 3],))
+    tips = torch.tensor(synth.MANO_TIP_VERTS) - (1 if fault == "tips off by one" else 0)
+    jmap = torch.tensor(synth.MANO_JOINT_MAP)
+    if fault == "joint map rotated":
+        jmap = jmap.roll(1)
+    joints = torch.cat([Gt, verts[:, tips]], 1)[:, jmap]
+    if exact:
+        for t in (R, verts, joints):
+            assert torch.equal(t.float().double(), t)
+    f32 = np.float32
+    c = cam.numpy().astype(f32)
+    if fault == "cam columns rotated":
+        c = c[:, [1, 2, 0]]
+    jn = joints.float().numpy()
+    with np.errstate(over="ignore"):
+        tz = (f32(2.0) * f32(focal)) / (f32(image_size) * c[:, 0] + f32(1e-9))
+    if exact:
+        den = f32(image_size) * c[:, 0]
+        live = c[:, 0] != 0
+        assert np.array_equal((den + f32(1e-9))[live], den[live]), "the + 1e-9f is not absorbed"
+        tz64 = 2.0 * focal / den[live].astype(np.float64)
+        assert np.array_equal(tz64.astype(f32).astype(np.float64), tz64) and np.array_equal(tz[live].astype(np.float64), tz64), "tz is rounded"
+    cam_t = np.stack([c[:, 1], c[:, 2], tz], 1)
+    pz = jn[:, :, 2] + tz[:, None]
+    f = f32(focal) / f32(image_size)
+    kp2d = np.stack([((jn[:, :, 0] + c[:, 1:2]) / pz) * f, ((jn[:, :, 1] + c[:, 2:3]) / pz) * f], -1)
+    assert cam_t.dtype == f32 and kp2d.dtype == f32
+    return {"rotmats": R.float(), "verts": verts.float(), "joints": joints.float(), "cam_t": torch.from_numpy(cam_t), "kp2d": torch.from_numpy(kp2d)}
+
+
+# ------------------------------------------------------------------------------------------------ Detect decode
+# csrc/yolo.hip decode_kernel: pred row row0 + (a ny + y) nx + x, column c = f(sigmoid(raw[(y nx + x) ldraw + a no + c])).
+# Exact data: every logit is a hashed choice among 0, +128 and -128; in fp32 expf(128) = +inf and expf(-128) = 0 (no fast-math),
+# so the sigmoid 1 / (1 + expf(-r)) is exactly 1/2, 1 or 0, and with integer anchors and power-of-two strides
+# xy = (2 s - 1/2 + grid) stride and wh = (2 s)^2 anchor are exact.
+DECODE_GRIDS = [(1, 1), (3, 4), (5, 7), (17, 19)]        # (ny, nx); the last: 969 rows, three full workgroups and a partial one
+DECODE_NC = [1, 3, 80]
+DECODE_ROW0 = [0, 17]
+DECODE_NB = [1, 3]
+DECODE_PAD = [0, 8]                                      # ldraw = 3 no + pad, NaN in the padding columns
+DECODE_TAIL_ROWS = 5                                     # rows of an image's slab after the last row written
+DECODE_SENTINEL = -54321.0
+DECODE_FAULTS = ["x and y grid swapped", "anchor w and h swapped", "anchor by p % 3", "-1/2 dropped", "rows in (y, x, a) order",
+                 "row0 ignored", "raw as [c][a]", "raw image stride zero", "pred image stride zero"]
+# Goes into every seed of the three-valued logits.  The (1, 1) grid has three rows and nc = 1 six columns each; a fault must
+# change more than half of them at every shape (tests/test_exact_data_host.py), and this is the first salt under which it does.
+DECODE_SALT = 2
+
+
+def decode_cases():
+    """Every (nb, ny, nx, nc, ldraw, row0, rows per image, level) of the exact GPU test; the anchor level cycles so that every grid
+    meets all three."""
+    out = []
+    for nb in DECODE_NB:
+        for gi, (ny, nx) in enumerate(DECODE_GRIDS):
+            for ci, nc in enumerate(DECODE_NC):
+                for pad in DECODE_PAD:
+                    for row0 in DECODE_ROW0:
+                        out.append((nb, ny, nx, nc, 3 * (5 + nc) + pad, row0, row0 + 3 * ny * nx + DECODE_TAIL_ROWS, (gi + ci + len(out)) % 3))
+    return out
+
+
+def decode_level(level):
+    from hamer_yolo_amd.yolo import arch
+    return float(arch.STRIDES[level]), [float(v) for v in arch.ANCHORS[level]]
+
+
+def sigmoid_f32(raw):
+    """1 / (1 + exp(-r)) in numpy.float32, one correctly rounded operation after the other (exp overflows to +inf on purpose)."""
+    r = raw.numpy().astype(np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        return torch.from_numpy(np.float32(1.0) / (np.float32(1.0) + np.exp(-r)))
+
+
+def decode_exact_case(nb, ny, nx, nc, ldraw, row0, stride_rows, seed=0):
+    """raw (nb, ny nx, ldraw) fp32: 0, +128 or -128 by a hash of the flat index in the 3 no columns read, NaN in the padding.
+    The three are equally likely but in the w and h columns, where -128 (a sigmoid of 0 and a box of size 0 whatever the
+    anchor) is one in eight, so that nearly every row tells the anchors apart."""
+    no = 5 + nc
+    assert ldraw >= 3 * no and stride_rows >= row0 + 3 * ny * nx
+    sd = _shape_seed(nb, ny, nx, nc, ldraw, row0, seed, DECODE_SALT)
+    h = ints("exact.decode.raw", (nb, ny * nx, ldraw), 0, 23, sd).long()
+    col = torch.arange(ldraw) % no
+    wh = ((col == 2) | (col == 3)) & (torch.arange(ldraw) < 3 * no)
+    pick = torch.where(wh[None, None, :], torch.where(h % 8 == 0, 2, (h // 8) % 2), h % 3)
+    raw = torch.tensor([0.0, 128.0, -128.0])[pick]
+    raw[:, :, 3 * no:] = float("nan")
+    return raw
+
+
+def decode_rule(s, ny, nx, nc, row0, stride_rows, level, fault=None, exact=True):
+    """Detect's decode (yolo.py:148-184) in float64 on the sigmoids s (nb, ny nx, ldraw) of the raw logits -> pred
+    (nb, stride_rows, no) float64, DECODE_SENTINEL in every row that is not written.  Row row0 + (a ny + y) nx + x takes
+    s[p ldraw + a no + c], p = y nx + x: xy = (2 s - 1/2 + (x, y)) stride, wh = (2 s)^2 anchor_a, the rest s.
+    `exact`: every value is an fp32 value (and, being a short dyadic number, is reached without a rounding)."""
+    assert fault is None or fault in DECODE_FAULTS
+    stride, anch = decode_level(level)
+    nb, n, no = s.shape[0], ny * nx, 5 + nc
+    s = s.double()
+    a, p, c = torch.meshgrid(torch.arange(3), torch.arange(n), torch.arange(no), indexing="ij")
+    y, x = p // nx, p % nx
+    col = c * 3 + a if fault == "raw as [c][a]" else a * no + c
+    img = torch.zeros(nb, dtype=torch.int64) if fault == "raw image stride zero" else torch.arange(nb)
+    sv = s[img[:, None, None, None], p[None], col[None]]                      # (nb, 3, n, no)
+    if fault == "x and y grid swapped":
+        x, y = y, x
+    aa = p % 3 if fault == "anchor by p % 3" else a
+    aw, ah = torch.tensor(anch[0::2], dtype=torch.float64)[aa], torch.tensor(anch[1::2], dtype=torch.float64)[aa]
+    if fault == "anchor w and h swapped":
+        aw, ah = ah, aw
+    half = 0.0 if fault == "-1/2 dropped" else 0.5
+    v = torch.where(c == 0, (sv * 2 - half + x) * stride, torch.where(c == 1, (sv * 2 - half + y) * stride,
+                    torch.where(c == 2, (sv * 2) ** 2 * aw, torch.where(c == 3, (sv * 2) ** 2 * ah, sv))))
+    r0 = 0 if fault == "row0 ignored" else row0
+    row = (r0 + p * 3 + a if fault == "rows in (y, x, a) order" else r0 + a * n + p)[:, :, 0]
+    pred = torch.full((nb, stride_rows, no), DECODE_SENTINEL, dtype=torch.float64)
+    for b in range(nb):
+        pred[0 if fault == "pred image stride zero" else b, row] = v[b]
+    if exact:
+        assert torch.equal(pred.float().double(), pred) and torch.equal(pred * 4, (pred * 4).round()) and float(pred.abs().max()) * 4 < EXACT_LIMIT
+    return pred
+
+
+# General logits: hashed over +-8 on the 2^-23 grid, one in 32 replaced by +-30 or +-100.  The reference of the closeness test
+# is the same formula in float64 and the bound is in fp32 ulps of the float64 value: twice the largest error of torch's CPU fp32
+# evaluation of the formula on these very inputs, plus 2 ulp for a different expf -- taken per group of columns (xy, wh, and
+# confidence with the classes), each of which is at most the one bound over all columns.  In the x and y columns a logit within
+# DECODE_XY_CLEAR of -ln 3 is moved up by 1: there the sigmoid is 1/4, 2 s - 1/2 crosses zero in grid cell 0 and an ulp of the
+# value measures the cancellation, not the arithmetic (unmoved, the CPU evaluation itself is 577 ulp off at one such element).
+DECODE_GENERAL = [(3, 17, 19, 3, 3 * 8 + 8, 17, 0), (3, 17, 19, 80, 3 * 85, 0, 1), (1, 5, 7, 1, 3 * 6, 0, 2)]     # nb, ny, nx, nc, ldraw, row0, level
+DECODE_XY_CLEAR = 0.5
+DECODE_GROUPS = {"xy": slice(0, 2), "wh": slice(2, 4), "conf": slice(4, None)}
+# Measured by tests/test_exact_data_host.py::test_decode_general_bound_is_the_measured_one, which fails if the CPU evaluation
+# exceeds a value or stays below half of it.  The 26.6 of the confidences is one logit of -100: 1 / (1 + e^100) = 3.7e-44 is 26.5
+# steps of 2^-149 and fp32 gives 0, its expf(100) being +inf.
+DECODE_CPU_ULP = {"xy": 3.7, "wh": 3.6, "conf": 26.6}
+DECODE_ULP_BOUND = {k: 2 * v + 2 for k, v in DECODE_CPU_ULP.items()}
+
+
+def decode_general_case(nb, ny, nx, nc, ldraw):
+    sd = _shape_seed(nb, ny, nx, nc, ldraw)
+    raw = synth.uniform("decode.general.raw", (nb, ny * nx, ldraw), 8.0, seed=sd)
+    col = torch.arange(ldraw) % (5 + nc)
+    near = ((raw + float(np.log(3.0))).abs() < DECODE_XY_CLEAR) & (col < 2)[None, None, :]
+    raw = torch.where(near, raw + 1.0, raw)
+    big = torch.tensor([30.0, -30.0, 100.0, -100.0])[ints("decode.general.big", raw.shape, 0, 3, sd).long()]
+    raw = torch.where(ints("decode.general.at", raw.shape, 0, 31, sd) == 0, big, raw)
+    raw[:, :, 3 * (5 + nc):] = float("nan")
+    return raw
+
+
+def decode_f32_cpu(raw, ny, nx, nc, level):
+    """torch's CPU fp32 evaluation of the kernel's formula, operation for operation -> the written rows (nb, 3 ny nx, no) fp32."""
+    stride, anch = decode_level(level)
+    nb, n, no = raw.shape[0], ny * nx, 5 + nc
+    assert raw.dtype == torch.float32
+    s = (1.0 / (1.0 + torch.exp(-raw[:, :, :3 * no]))).reshape(nb, n, 3, no).permute(0, 2, 1, 3)
+    p = torch.arange(n)
+    x, y = (p % nx).float()[None, None, :], (p // nx).float()[None, None, :]
+    aw, ah = torch.tensor(anch[0::2])[None, :, None], torch.tensor(anch[1::2])[None, :, None]
+    v = s.clone()
+    v[..., 0], v[..., 1] = (s[..., 0] * 2.0 - 0.5 + x) * stride, (s[..., 1] * 2.0 - 0.5 + y) * stride
+    t2, t3 = s[..., 2] * 2.0, s[..., 3] * 2.0
+    v[..., 2], v[..., 3] = (t2 * t2) * aw, (t3 * t3) * ah
+    assert v.dtype == torch.float32
+    return v.reshape(nb, 3 * n, no)
+
+
+def ulp32(v):
+    """The spacing of fp32 at the float64 value v: 2^(floor(log2 |v|) - 23), 2^-149 below the normal range."""
+    e = torch.frexp(v.double().abs())[1].double() - 1
+    e = torch.where(v == 0, torch.full_like(e, -126.0), e)
+    return torch.exp2(e.clamp_min(-126.0) - 23)
+
+
+def ulp_error(got, ref):
+    """max |got - ref| / ulp32(ref) over finite ref."""
+    return float(((got.double() - ref.double()).abs() / ulp32(ref)).max())
+
+
+# ------------------------------------------------------------------------------------------------ RootNet layout kernels
+# hm_gap_linear: depth[b] = (sum_c mean_p feat[b, p, c] w[c] + bias) k_value[b].  Features -3..3, w -4..4, an integer bias, HW a
+# power of two and k_value a multiple of 1/4: every column sum is an integer, s / HW and every product a multiple of 1 / HW.
+GAP_C = [8, 200, 256, 264, 1024, 2048]     # < 256 leaves waves with nothing; 200 and 264 a partial 256-channel sweep
+GAP_HW = [16, 64]
+GAP_B = [1, 3]
+GAP_SENTINEL = -777.0
+GAP_FAULTS = ["feature as [C][HW]", "w rotated", "k_value rotated", "image stride zero"]
+GAP_CLOSE = (3, 49, 2048)                  # (B, HW, C) of the closeness case
+NHWC8_SHAPES = [(1, 1, 1), (1, 5, 7), (3, 16, 17), (2, 33, 31)]      # B HW = 1, 35, 816, 2046: below, and across multiples of 256
+# (img_h, img_w_full, x0, win_w, patch, pad) of hm_patch_im2col: the full width without padding; the production window; a window
+# that ends at the image's right edge (its padding is zero, not the neighbour's pixels); patch 8 in a non-square image; a narrow one
+IM2COL_CASES = [(256, 256, 0, 256, 16, 0), (256, 256, 32, 192, 16, 2), (256, 256, 64, 192, 16, 2), (48, 80, 8, 40, 8, 3), (40, 24, 0, 24, 8, 0)]
+IM2COL_B = [1, 3]
+IM2COL_OUTSIDE = 32768.0                   # the pixels outside the window (an fp16 and bf16 value)
+
+
+def gap_case(B, HW, C):
+    """feat (B, HW, C) -3..3, w (C,) -4..4, bias (an integer), k_value (B,) distinct multiples of 1/4 in 1/4..3, all fp32, and
+    depth (B,) fp32.  Asserts sum |s| |w| + HW |bias| < 2^24 in units of 1 / HW and that the final product is an fp32 value."""
+    assert HW & (HW - 1) == 0
+    sd = _shape_seed(B, HW, C)
+    feat = ints("exact.gap.feat", (B, HW, C), -3, 3, sd)
+    w = ints("exact.gap.w", (C,), -4, 4, sd)
+    bias = float(ints("exact.gap.bias", (1,), -9, 9, sd))
+    kv = ((int(ints("exact.gap.k", (1,), 0, 11, sd)) + torch.arange(B)) % 12 + 1).float() / 4
+    return feat, w, bias, kv, gap_rule(feat, w, bias, kv)
+
+
+def gap_rule(feat, w, bias, kv, fault=None, exact=True):
+    """int64 column sums, one float64 quotient by HW (a power of two) -> depth (B,) fp32."""
+    assert fault is None or fault in GAP_FAULTS
+    B, HW, C = feat.shape
+    f = feat.long()
+    if fault == "feature as [C][HW]":
+        f = f.reshape(B, C, HW).transpose(1, 2)
+    if fault == "image stride zero":
+        f = f[:1].expand(B, HW, C)
+    wl = w.long().roll(1) if fault == "w rotated" else w.long()
+    k = kv.roll(1) if fault == "k_value rotated" else kv
+    s = f.sum(1)                                                                   # (B, C)
+    num = (s * wl).sum(1)
+    if exact:
+        assert int(((s.abs() * wl.abs()).sum(1)).max()) + HW * abs(bias) < EXACT_LIMIT
+    depth = (num.double() / HW + bias) * k.double()
+    assert not exact or torch.equal(depth.float().double(), depth)
+    return depth.float()
+
+
+def nhwc8_case(B, H, W):
+    """x (B, 3, H, W) fp32: hashed multiples of 1/16 in -8..8, values of fp32, fp16 and bf16 alike."""
+    x = ints("exact.nhwc8.x", (B, 3, H, W), -127, 127, _shape_seed(B, H, W)) / 16
+    assert torch.equal(x.half().float(), x) and torch.equal(x.bfloat16().float(), x)
+    return x
+
+
+def im2col_case(B, img_h, img_w_full, x0, win_w, patch, pad):
+    """img (B, 3, img_h, img_w_full) fp32 on the 2^-23 grid of [-2, 2), IM2COL_OUTSIDE in every column outside the window."""
+    img = synth.uniform("exact.im2col.img", (B, 3, img_h, img_w_full), 2.0, seed=_shape_seed(img_h, img_w_full, x0, win_w, patch, pad))
+    img[..., :x0] = IM2COL_OUTSIDE
+    img[..., x0 + win_w:] = IM2COL_OUTSIDE
+    return img
+
+
+def im2col_rule(img, x0, win_w, patch, pad, dtype):
+    """F.unfold of the window rounded to `dtype` -> (B gh gw, 3 patch patch) fp32."""
+    win = img[..., x0:x0 + win_w].to(dtype).float()
+    ref = torch.nn.functional.unfold(win, kernel_size=patch, stride=patch, padding=pad)
+    return ref.transpose(1, 2).reshape(-1, 3 * patch * patch)
 
 
 # ------------------------------------------------------------------------------------------------ the comparison

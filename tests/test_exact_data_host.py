@@ -15,6 +15,10 @@ The SAR hand-mesh head (section "SAR hand-mesh head") gets the GEMM catalogue at
 alone can make (the 32-wide K loop, the transposed read's halves, the SAIGB scatter), and catalogues of their own for the
 few-hot soft-argmax data and the dyadic post-processing data; the fp32 rule of tests/sar_rule.py must reproduce both closed forms.
 
+The MANO tail, the Detect decode and the RootNet layout kernels (the last sections) have rules that take a `fault` argument:
+each fault of their catalogues is applied to the rule at every case the GPU tests run and must change more than half of the
+rows of the output it concerns; the decode's closeness bound is measured here, on the CPU, against float64.
+
 Large problems are checked on a 256 x 256 subset of the output spread evenly over the rows and columns (so over every tile);
 a fault is an index map, applied to the full operand's indices before the subset is taken.  A fault that is the identity
 map at a shape (a rotation of K-tiles when K is one tile, a flip of a 1 x 1 kernel) is no fault there and is passed over;
@@ -1107,6 +1111,232 @@ def test_sar_builders_refuse_data_that_is_not_exact(monkeypatch):
     monkeypatch.setattr(ED, "SAR_POST_K", (1000.0, 512.0, 512.0, 256.0))      # a focal length that is no power of two
     with pytest.raises(AssertionError):
         ED.sar_post_case()
+
+
+# ------------------------------------------------------------------------------------------------ MANO tail
+def _rows_changed(got, ref, width):
+    return (got.reshape(-1, width) != ref.reshape(-1, width)).any(1)
+
+
+MANO_CASES = [(B, V, False) for B in ED.MANO_B for V in ED.MANO_V] + [ED.MANO_DEGENERATE + (True,)]
+# fault -> the output it concerns and the width of one of its rows
+MANO_CONCERNS = {"wrong parent table": ("joints", 3), "joint map rotated": ("joints", 3), "tips off by one": ("joints", 3),
+                 "posedirs as [3V][135]": ("verts", 3), "shapedirs as [10][3V]": ("verts", 3), "rotation transposed": ("rotmats", 9),
+                 "pose feature from joint 0": ("verts", 3), "lbs_weights as [16][V]": ("verts", 3), "joints from v_posed": ("joints", 3),
+                 "A without G J": ("verts", 3), "one range unposed": ("verts", 3), "child before parent": ("joints", 3),
+                 "cam columns rotated": ("kp2d", 2)}
+
+
+@pytest.mark.parametrize("B,V,degenerate", MANO_CASES)
+def test_mano_data_is_exact_and_sees_every_fault(B, V, degenerate):
+    """mano_rule's stage assertions hold on the case (they run inside the call), and each fault of MANO_FAULTS changes more
+    than half of the rows of the output it concerns: all five tip joints of every hand for the tip fault, more than half of
+    the unposed range for the one-range fault, every cam_t row as well for the camera fault."""
+    from hamer_yolo_amd import synth
+    mp, pose, betas, cam, _ = ED.mano_exact_case(B, V, degenerate=degenerate)
+    ref = ED.mano_rule(mp, pose, betas, cam)
+    assert set(MANO_CONCERNS) == set(ED.MANO_FAULTS)
+    tip_rows = torch.tensor([i for i, s in enumerate(synth.MANO_JOINT_MAP) if s >= 16])
+    for fault in ED.MANO_FAULTS:
+        got = ED.mano_rule(mp, pose, betas, cam, fault=fault, exact=False)
+        key, width = MANO_CONCERNS[fault]
+        changed = _rows_changed(got[key], ref[key], width).reshape(B, -1)
+        if fault == "tips off by one":
+            assert bool(changed[:, tip_rows].all()) and not bool(_rows_changed(got["verts"], ref["verts"], 3).any()), (fault, B, V)
+            continue
+        if fault == "one range unposed":
+            lo, hi = ED.mano_ranges(V)[ED.MANO_UNPOSED_RANGE]
+            assert float(changed[:, lo:hi].float().mean()) > HALF and not bool(changed[:, :lo].any()) and not bool(changed[:, hi:].any())
+            continue
+        assert float(changed.float().mean()) > HALF, (fault, B, V, float(changed.float().mean()))
+        if fault == "cam columns rotated":
+            assert bool(_rows_changed(got["cam_t"], ref["cam_t"], 3).all())
+
+
+def test_mano_case_is_what_the_issue_asks_for():
+    """Rotations: all 24 proper signed permutations occur, every joint differs from all its ancestors, hands 0 and 1 differ at
+    every joint; the 6-D codes are not normalised and half of them carry a t e_i term; the camera rows give tz = 2^m but for
+    the one row with c0 = 0; the tips are owned as MANO_TIP_OWNER says at every V."""
+    import numpy as np
+    from hamer_yolo_amd import synth
+    from hamer_yolo_amd.hamer.utils.geometry import rot6d_to_rotmat
+    table, sym = ED.mano_rotation_table()
+    assert len(set(table)) == 24 and sum(sym) == 10
+    seen = set()
+    for B, V, _ in MANO_CASES[:-1]:
+        mp, pose, betas, cam, rot = ED.mano_exact_case(B, V)
+        seen |= set(rot.reshape(-1).tolist())
+        for j in range(1, 16):
+            a = synth.MANO_PARENTS[j]
+            while a >= 0:
+                assert bool((rot[:, j] != rot[:, a]).all())
+                a = synth.MANO_PARENTS[a]
+        assert B == 1 or bool((rot[0] != rot[1]).all())
+        x = pose.reshape(B * 16, 6)
+        n1, dot = x[:, :3].norm(dim=1), (x[:, :3] * x[:, 3:]).sum(1)
+        assert B == 1 or (float((n1 != 1).float().mean()) > HALF and 0.25 < float((dot != 0).float().mean()) < 0.75)
+        R = ED.mano_rot6d_rule(pose).reshape(B, 16, 3, 3)
+        assert torch.equal(R.float(), rot6d_to_rotmat(pose).reshape(B, 16, 3, 3))             # the project's CPU reference, bit for bit
+        assert torch.equal(R @ R.transpose(-1, -2), torch.eye(3, dtype=torch.float64).expand(B, 16, 3, 3))
+        out = ED.mano_rule(mp, pose, betas, cam)
+        tz = out["cam_t"][:, 2].double()
+        zero = cam[:, 0] == 0
+        assert int(zero.sum()) == (1 if B > 1 else 0)
+        assert torch.equal(tz[~zero], 2 * ED.MANO_FOCAL / (ED.MANO_IMAGE * cam[~zero, 0].double())) and torch.equal(torch.log2(tz[~zero]), torch.log2(tz[~zero]).round())
+        assert not bool(zero.any()) or float(tz[zero]) == float(np.float32(10000.0) / np.float32(1e-9))
+        assert bool(out["kp2d"].isfinite().all()) and (B == 1 or float((out["kp2d"] != 0).float().mean()) > 0.9)
+        owner = [next(k for k, (lo, hi) in enumerate(ED.mano_ranges(V)) if lo <= t < hi) for t in synth.MANO_TIP_VERTS]
+        assert tuple(owner) == ED.MANO_TIP_OWNER
+    assert seen == set(range(24))
+    assert ED.mano_ranges(745)[3] == (561, 745) and ED.mano_ranges(800)[3] == (600, 800)
+
+
+def test_mano_degenerate_poses_are_exact():
+    """a1 = 0 gives columns (0, a2 / |a2|, 0) and a2 = t a1 gives (a1 / |a1|, 0, 0): the rule, with the kernel's floor of 1e-12f,
+    equals the project's rot6d_to_rotmat on the CPU, and the whole forward stays exact (the stage assertions run)."""
+    from hamer_yolo_amd.hamer.utils.geometry import rot6d_to_rotmat
+    B, V = ED.MANO_DEGENERATE
+    mp, pose, betas, cam, _ = ED.mano_exact_case(B, V, degenerate=True)
+    out = ED.mano_rule(mp, pose, betas, cam)
+    R = out["rotmats"]
+    assert torch.equal(R, rot6d_to_rotmat(pose).reshape(B, 16, 3, 3) + 0.0)
+    b, j = ED.MANO_DEGENERATE_JOINTS["a1 = 0"]
+    assert not bool(pose.reshape(B, 16, 6)[b, j, :3].any())
+    assert not bool(R[b, j, :, 0].any()) and not bool(R[b, j, :, 2].any()) and float(R[b, j, :, 1].abs().sum()) == 1
+    b, j = ED.MANO_DEGENERATE_JOINTS["a2 = t a1"]
+    assert torch.equal(pose.reshape(B, 16, 6)[b, j, 3:], 1.5 * pose.reshape(B, 16, 6)[b, j, :3])
+    assert float(R[b, j, :, 0].abs().sum()) == 1 and not bool(R[b, j, :, 1:].any())
+    plain = ED.mano_rule(*ED.mano_exact_case(B, V)[:4])
+    assert float(_rows_changed(out["verts"][0], plain["verts"][0], 3).float().mean()) > HALF      # the degenerate joints reach the mesh
+
+
+def test_mano_builders_refuse_data_that_is_not_exact():
+    mp, pose, betas, cam, _ = ED.mano_exact_case(5, 778)
+    bad = dict(mp, v_template=mp["v_template"] + 1.0 / 3)
+    with pytest.raises(AssertionError):
+        ED.mano_rule(bad, pose, betas, cam)
+    with pytest.raises(AssertionError):
+        ED.mano_rule(mp, pose, betas * 2.0 ** 22, cam)                   # multiples of the quantum, but past 2^24 of them
+    tilted = pose.clone()
+    tilted[0, :3] = 1.0                                            # a1 = (1, 1, 1): its norm is no fp32 value
+    with pytest.raises(AssertionError):
+        ED.mano_rule(mp, tilted, betas, cam)
+    with pytest.raises(AssertionError):
+        ED.mano_rule(mp, pose, betas, cam + torch.tensor([1e-3, 0.0, 0.0]))      # image_size * c0 is no longer exact
+
+
+# ------------------------------------------------------------------------------------------------ Detect decode
+def test_decode_sigmoid_has_three_exact_values():
+    import numpy as np
+    f = np.float32
+    with np.errstate(over="ignore"):
+        assert np.exp(f(128.0)) == np.inf and np.exp(f(-128.0)) == 0 and np.exp(f(128.0)).dtype == f
+        vals = [f(1) / (f(1) + np.exp(-f(r))) for r in (0.0, 128.0, -128.0)]
+    assert vals == [0.5, 1.0, 0.0] and all(v.dtype == f for v in vals)
+    assert ED.sigmoid_f32(torch.tensor([0.0, 128.0, -128.0])).tolist() == [0.5, 1.0, 0.0]
+
+
+def _decode_applies(fault, nb, ny, nx, row0):
+    if fault in ("x and y grid swapped", "anchor w and h swapped"):
+        return (ny, nx) != (1, 1)
+    if fault == "rows in (y, x, a) order":
+        return ny * nx > 1                                               # the identity map on a single cell
+    if fault == "row0 ignored":
+        return row0 != 0
+    if fault in ("raw image stride zero", "pred image stride zero"):
+        return nb > 1
+    return True
+
+
+def test_decode_data_is_exact_and_sees_every_fault():
+    """Every case of the exact GPU test: the rule's values are short dyadic fp32 numbers (asserted inside), and every fault that
+    applies changes more than half of the rows it concerns -- the rows the right or the wrong decode writes; images 1.. for the
+    image-stride faults.  Every grid meets all three anchor levels and every fault applies somewhere."""
+    met, levels = set(), {}
+    cases = ED.decode_cases()
+    assert len(cases) == len(set(cases)) == 96
+    for nb, ny, nx, nc, ldraw, row0, rows, level in cases:
+        levels.setdefault((ny, nx), set()).add(level)
+        raw = ED.decode_exact_case(nb, ny, nx, nc, ldraw, row0, rows)
+        assert bool(raw[:, :, 3 * (5 + nc):].isnan().all()) and set(raw[:, :, :3 * (5 + nc)].reshape(-1).tolist()) <= {0.0, 128.0, -128.0}
+        s = ED.sigmoid_f32(raw)
+        ref = ED.decode_rule(s, ny, nx, nc, row0, rows, level)
+        n = 3 * ny * nx
+        assert bool((ref[:, :row0] == ED.DECODE_SENTINEL).all()) and bool((ref[:, row0 + n:] == ED.DECODE_SENTINEL).all())
+        assert not bool((ref[:, row0:row0 + n] == ED.DECODE_SENTINEL).any()) and rows > row0 + n
+        for fault in ED.DECODE_FAULTS:
+            if not _decode_applies(fault, nb, ny, nx, row0):
+                continue
+            got = ED.decode_rule(s, ny, nx, nc, row0, rows, level, fault=fault, exact=False)
+            first = 1 if "image stride" in fault else 0
+            touched = ((ref != ED.DECODE_SENTINEL) | (got != ED.DECODE_SENTINEL)).any(2)[first:]
+            changed = (ref != got).any(2)[first:]
+            frac = float(changed[touched].float().mean())
+            assert frac > HALF, (fault, nb, ny, nx, nc, ldraw, row0, level, frac)
+            met.add(fault)
+    assert met == set(ED.DECODE_FAULTS) and all(v == {0, 1, 2} for v in levels.values())
+
+
+def test_decode_general_bound_is_the_measured_one():
+    """The closeness bound of the general-logit GPU test: the largest error, in fp32 ulps of the float64 value, of torch's CPU fp32
+    evaluation of the formula on the test's own inputs is DECODE_CPU_ULP per column group (not more, and not less than half), and
+    the bound is twice that plus 2.  A decode with one anchor's width off by 1 % misses it by orders of magnitude."""
+    worst = {k: 0.0 for k in ED.DECODE_GROUPS}
+    for nb, ny, nx, nc, ldraw, row0, level in ED.DECODE_GENERAL:
+        raw = ED.decode_general_case(nb, ny, nx, nc, ldraw)
+        live = raw[:, :, :3 * (5 + nc)]
+        assert float(live.abs().max()) == 100.0 and 0.01 < float((live.abs() > 8).float().mean()) < 0.06
+        n = 3 * ny * nx
+        ref = ED.decode_rule(torch.sigmoid(raw.double()), ny, nx, nc, 0, n, level, exact=False)
+        got = ED.decode_f32_cpu(raw, ny, nx, nc, level)
+        for k, cols in ED.DECODE_GROUPS.items():
+            worst[k] = max(worst[k], ED.ulp_error(got[..., cols], ref[..., cols]))
+        off = ref.clone()
+        off[:, :ny * nx, 2] *= 1.01
+        assert ED.ulp_error(off.float()[..., 2:4], ref[..., 2:4]) > 1000 * ED.DECODE_ULP_BOUND["wh"]
+    for k in worst:
+        assert worst[k] <= ED.DECODE_CPU_ULP[k] <= 2 * worst[k], (k, worst)
+        assert ED.DECODE_ULP_BOUND[k] == 2 * ED.DECODE_CPU_ULP[k] + 2
+    v = torch.tensor([1.0, 1.5, 2.0, 3.0e-39, 0.0, -6.0], dtype=torch.float64)
+    assert ED.ulp32(v).tolist() == [2.0 ** -23, 2.0 ** -23, 2.0 ** -22, 2.0 ** -149, 2.0 ** -149, 2.0 ** -21]
+
+
+# ------------------------------------------------------------------------------------------------ RootNet layout kernels
+def test_gap_data_is_exact_and_sees_every_fault():
+    """Every (B, HW, C) of the exact GPU test: the builder's bound holds (asserted inside gap_rule), and each fault changes more
+    than half of the depths (all of them but one at B = 3); the batch faults apply where B > 1."""
+    met = set()
+    for B in ED.GAP_B:
+        for HW in ED.GAP_HW:
+            for C in ED.GAP_C:
+                feat, w, bias, kv, depth = ED.gap_case(B, HW, C)
+                assert len(set(kv.tolist())) == B and torch.equal(kv * 4, (kv * 4).round()) and bias == round(bias)
+                for fault in ED.GAP_FAULTS:
+                    if fault in ("k_value rotated", "image stride zero") and B == 1:
+                        continue
+                    got = ED.gap_rule(feat, w, bias, kv, fault=fault, exact=False)
+                    changed = (got != depth)[1:] if fault == "image stride zero" else got != depth
+                    assert float(changed.float().mean()) > HALF, (fault, B, HW, C)
+                    met.add(fault)
+    assert met == set(ED.GAP_FAULTS)
+    with pytest.raises(AssertionError):
+        ED.gap_rule(feat * 2.0 ** 12, w, bias, kv)
+
+
+def test_layout_cases_are_what_the_issue_asks_for():
+    assert [B * H * W for B, H, W in ED.NHWC8_SHAPES] == [1, 35, 816, 2046]
+    for shape in ED.NHWC8_SHAPES:
+        x = ED.nhwc8_case(*shape)
+        assert float((x.reshape(-1)[1:] != x.reshape(-1)[:-1]).float().mean()) > HALF or x.numel() == 3
+    for img_h, img_w, x0, win_w, patch, pad in ED.IM2COL_CASES:
+        img = ED.im2col_case(3, img_h, img_w, x0, win_w, patch, pad)
+        inside = img[..., x0:x0 + win_w]
+        assert float(inside.abs().max()) < 2 and bool((img[..., :x0] == ED.IM2COL_OUTSIDE).all()) and bool((img[..., x0 + win_w:] == ED.IM2COL_OUTSIDE).all())
+        ref = ED.im2col_rule(img, x0, win_w, patch, pad, torch.float32)
+        gh, gw = (img_h + 2 * pad - patch) // patch + 1, (win_w + 2 * pad - patch) // patch + 1
+        assert ref.shape == (3 * gh * gw, 3 * patch * patch) and float(ref.abs().max()) < 2
+        assert (float((ref == 0).float().mean()) > 0) == (pad > 0)
+    assert (256, 256, 32, 192, 16, 2) in ED.IM2COL_CASES and any(x0 + w == full and x0 > 0 for _, full, x0, w, _, _ in ED.IM2COL_CASES)
 
 
 # ------------------------------------------------------------------------------------------------ the data and the report
