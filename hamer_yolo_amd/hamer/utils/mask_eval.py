@@ -93,6 +93,48 @@ def mask_counts(pred_id: torch.Tensor, mask: torch.Tensor, queries: Sequence, ra
     return counts
 
 
+def box_query_table(queries) -> np.ndarray:
+    """``queries``, a sequence of (frame, label), as the (Q, 2) int32 table hm_mask_boxes reads.  A frame outside the batch is
+    legal there (its row is the empty one), so nothing but the int32 range is checked."""
+    q = np.asarray([tuple(int(v) for v in row) for row in queries], np.int64).reshape(-1, 2)
+    if q.size and (np.abs(q) >= 2 ** 31).any():
+        raise ValueError("mask_boxes: a query value does not fit int32")
+    return np.ascontiguousarray(q.astype(np.int32))
+
+
+def mask_boxes(mask: torch.Tensor, queries, boxes: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One hm_mask_boxes call (csrc/mask_boxes.hip): the tight box and the pixel count of a label per query.  ``mask``
+    (N, H, W) uint8, a contiguous tensor on a GPU; ``queries``: a sequence of (frame, label) -- label -1: any non-zero label --
+    or a (Q, 2) int32 tensor already on the mask's device (no upload then).  Returns (Q, 5) int32 on the device, or fills
+    ``boxes``: x1, y1, x2, y2, count, and -1, -1, -1, -1, 0 where the label is absent or the frame outside the batch.
+    Enqueued on the current stream without synchronising.  There is no CPU path."""
+    if not torch.is_tensor(mask) or not mask.is_cuda:
+        raise ValueError("mask_boxes: mask must be a tensor on a GPU; there is no CPU path")
+    if mask.dtype != torch.uint8 or mask.dim() != 3 or 0 in mask.shape or not mask.is_contiguous():
+        raise ValueError(f"mask_boxes: mask must be a contiguous uint8 (N, H, W) tensor, got {mask.dtype} {tuple(mask.shape)}")
+    N, H, W = (int(v) for v in mask.shape)
+    dev = mask.device
+    if torch.is_tensor(queries):
+        if not (queries.device == dev and queries.dtype == torch.int32 and queries.dim() == 2 and queries.shape[1] == 2
+                and queries.is_contiguous()):
+            raise ValueError(f"mask_boxes: a query tensor must be contiguous int32 (Q, 2) on {dev}")
+        qd = queries
+    else:
+        table = box_query_table(queries)
+        qd = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True) if len(table) else torch.empty(0, 2, dtype=torch.int32, device=dev)
+    Q = int(qd.shape[0])
+    if boxes is None:
+        boxes = torch.empty(Q, 5, dtype=torch.int32, device=dev)
+    elif not (torch.is_tensor(boxes) and boxes.device == dev and boxes.dtype == torch.int32 and tuple(boxes.shape) == (Q, 5)
+              and boxes.is_contiguous()):
+        raise ValueError(f"mask_boxes: boxes must be a contiguous int32 tensor of shape ({Q}, 5) on {dev}")
+    if Q == 0:
+        return boxes
+    with torch.cuda.device(dev):
+        L.check(L.load().hm_mask_boxes(L.ptr(mask), N, H, W, L.ptr(qd), Q, L.ptr(boxes), L.current_stream()), "hm_mask_boxes")
+    return boxes
+
+
 def jf_from_counts(counts) -> Dict[str, np.ndarray]:
     """``J``, ``F``, ``precision`` and ``recall`` of (Q, 8) counts (a device tensor -- one copy -- or a numpy array) as float64
     arrays, by the rule: J = 1 when both areas are empty, else inter / union; P = pred_matched / pred_boundary and R =

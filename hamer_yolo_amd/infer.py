@@ -7,7 +7,10 @@ Kept in Python (drop-in): ``hamer_inference`` (:117-528), ``matrix_to_axis_angle
 (:1479-1536).  Pixel and tensor work is HIP: one ``hm_crop_batch`` launch for all hands of a frame
 (the reference crops hand by hand on the CPU and copies the frame per hand, :208) and one
 ``hm_hamer_forward`` enqueue for the batch.  ``get_mesh_renderer`` / ``get_image`` / ``image_fusion`` draw with the z-buffered
-GPU renderer (render.render_views).  Out of scope: ONNX export/compare, pyrender's own lighting.
+GPU renderer (render.render_views).  ``process_batch_manopara_with_mask`` (:1099-1220) is the reference's loop by default and,
+with ``batched=True`` (command line: ``--masks DIR``), the folder pipeline with mask_boxes.MaskBoxes in the detector's place: the
+hand boxes of a pass of label masks come from one ``hm_mask_boxes`` launch, and with an intrinsics folder every hand gets its
+own frame's K.  Out of scope: ONNX export/compare, pyrender's own lighting.
 """
 from __future__ import annotations
 
@@ -526,7 +529,7 @@ def shard_paths(paths: List[str], rank: int = 0, world: int = 1) -> List[str]:
 def iter_folder_results(image_paths, hamer, detector, k_real=None, frames_per_step: int = FRAMES_PER_STEP, in_flight: int = 2,
                         decode_threads: Optional[int] = None, depth_model=None, hands_per_forward: int = HANDS_PER_FORWARD,
                         det_frames: Optional[int] = None, rank: int = 0, world: int = 1, stats: Optional[Dict] = None,
-                        overlap_detector: bool = True, balance_tail: bool = True, det_ramp=None):
+                        overlap_detector: bool = True, balance_tail: bool = True, det_ramp=None, frame_k=None):
     """Yields ``(path, detection_list, hands)`` per image that has detections, in path order; ``hands`` is a dict of host
     numpy arrays for that image's hands in detection order: betas (n,10), global_orient (n,1,3,3), hand_pose (n,15,3,3),
     cam_t (n,3), do_flip (n,), plus the axis-angle forms pose_global (n,3) and pose_hand (n,45).
@@ -539,7 +542,15 @@ def iter_folder_results(image_paths, hamer, detector, k_real=None, frames_per_st
     ``balance_tail=False``: the folder's last hands go out as forwards of ``hands_per_forward`` and one remainder (up to 1.25 x)
     instead of equal parts on all streams.
     ``overlap_detector=False`` puts the detector passes on the first HaMeR stream (with ``in_flight=1``: a strictly serial
-    GPU timeline, what bench.py's per-launch profile pass wants)."""
+    GPU timeline, what bench.py's per-launch profile pass wants).
+    ``detector`` may be any box source with the detector's pass protocol.  One with ``wants_paths`` (mask_boxes.MaskBoxes) is
+    also handed the pass's file paths (``detect_frames_enqueue(frames, paths=[...])``) and has its ``prefetch(path, (H, W), slot,
+    slots)`` called by the decode threads behind each frame's decode (``slot`` / ``slots``: the frame's place in the ring of
+    page-locked frame slots and the ring's size).
+    ``frame_k`` (the mask-driven driver's intrinsics directory): a callable ``path -> 3x3 K or None``, asked once per file that
+    has hands; it replaces ``k_real``.  A forward's hands whose frames have a K get theirs as one ``(B, 3, 3)`` tensor; hands of
+    frames without one use the default camera, which is another formula -- so a batch that holds both kinds is split into two
+    forwards (order kept within each) and the two kinds never share a camera step."""
     from collections import deque
     from concurrent.futures import ThreadPoolExecutor
     image_paths = shard_paths(list(image_paths), rank, world)
@@ -574,6 +585,8 @@ def iter_folder_results(image_paths, hamer, detector, k_real=None, frames_per_st
     queue = deque()                                                   # (file index, detection index, frame tensor)
     det_jobs, batches = deque(), deque()
     hands_per_frame = 4.0                                             # running estimate, for how far ahead the detector runs
+    with_paths = bool(getattr(detector, "wants_paths", False))
+    prefetch = getattr(detector, "prefetch", None) if with_paths else None
 
     def decode(index, path):
         """One file -> (HxWx3 BGR array or None, its page-locked slot as a tensor or None, rows bottom-up?)."""
@@ -588,6 +601,8 @@ def iter_folder_results(image_paths, hamer, detector, k_real=None, frames_per_st
         im = _imread_bgr(path, alloc, raw)
         if trace is not None and index % 8 == 7:
             mark(f"decoded file {index}")
+        if prefetch is not None and im is not None:
+            prefetch(path, im.shape[:2], index % ring.n, ring.n)
         if im is not None and not taken:                              # not decoded in place (PIL path): one copy into the slot
             got = ring.slot(index, im.shape)
             if got is not None:
@@ -626,7 +641,9 @@ def iter_folder_results(image_paths, hamer, detector, k_real=None, frames_per_st
                 frames = [d[j] for j in range(len(items))]
             else:
                 frames = [torch.from_numpy(np.ascontiguousarray(im[::-1] if rev else im)).to(dev) for _, im, _, rev in items]
-            if hasattr(detector, "detect_frames_enqueue"):
+            if with_paths:
+                token = detector.detect_frames_enqueue(frames, paths=[image_paths[fi] for fi, _, _, _ in items])
+            elif hasattr(detector, "detect_frames_enqueue"):
                 token = detector.detect_frames_enqueue(frames)
             else:
                 token = None
@@ -660,6 +677,8 @@ def iter_folder_results(image_paths, hamer, detector, k_real=None, frames_per_st
         found = 0
         for (fi, _, _, _), fr, dl in zip(items, frames, kept):
             files[fi] = {"dets": dl, "rows": [None] * len(dl), "out": len(dl)}
+            if frame_k is not None and dl:
+                files[fi]["k"] = frame_k(image_paths[fi])
             for j in range(len(dl)):
                 queue.append((fi, j, fr))
             found += len(dl)
@@ -678,36 +697,54 @@ def iter_folder_results(image_paths, hamer, detector, k_real=None, frames_per_st
     # ------------------------------------------------------------------ HaMeR batches
     def batch_enqueue(hands, stream):
         """`hands`: [(file, detection, frame)] in queue order -> crops, (RootNet,) HaMeR forward and camera step on `stream`.
-        (Their frames are on the device: a hand enters the queue only behind its pass's host sync, see det_harvest.)"""
-        frames, dets_lists = [], []
-        for fi, j, fr in hands:
-            if not frames or frames[-1] is not fr:
-                frames.append(fr); dets_lists.append([])
-            dets_lists[-1].append(files[fi]["dets"][j])
+        (Their frames are on the device: a hand enters the queue only behind its pass's host sync, see det_harvest.)
+        With `frame_k` the hands of frames with a K and those of frames without one go through a forward each."""
+        if frame_k is None:
+            groups = [(hands, k_real)]
+        else:
+            with_k = [h for h in hands if files[h[0]].get("k") is not None]
+            without = [h for h in hands if files[h[0]].get("k") is None]
+            groups = [(without, None)] if without else []
+            if with_k:
+                ks = torch.from_numpy(np.stack([np.asarray(files[fi]["k"], np.float32) for fi, _, _ in with_k]))
+                groups.insert(0, (with_k, hamer._up(ks) if hasattr(hamer, "_up") else ks))
+        parts = []
         with stream_ctx(stream):
-            depth = depth_model.estimate_root_depths_frames(frames, k_real, dets_lists) if depth_model is not None else None
-            out, _ = hamer.estimate_from_frames(frames, dets_lists, k_real, depth_refine=depth)
-            mp = out['pred_mano_params']
-            dev_res = {'betas': mp['betas'], 'global_orient': mp['global_orient'], 'hand_pose': mp['hand_pose'],
-                       'cam_t': out['pred_cam_t_full'], 'do_flip': out['do_flip']}
+            for part, k in groups:
+                frames, dets_lists = [], []
+                for fi, j, fr in part:
+                    if not frames or frames[-1] is not fr:
+                        frames.append(fr); dets_lists.append([])
+                    dets_lists[-1].append(files[fi]["dets"][j])
+                depth = depth_model.estimate_root_depths_frames(frames, k, dets_lists) if depth_model is not None else None
+                out, _ = hamer.estimate_from_frames(frames, dets_lists, k, depth_refine=depth)
+                mp = out['pred_mano_params']
+                parts.append(([(fi, j) for fi, j, _ in part],
+                              {'betas': mp['betas'], 'global_orient': mp['global_orient'], 'hand_pose': mp['hand_pose'],
+                               'cam_t': out['pred_cam_t_full'], 'do_flip': out['do_flip']}, frames))   # (frames: alive until finish)
             done = new_event()
             done.record(stream)          # (its own event: a stream synchronise would also wait for the NEXT batch queued on that stream)
-        st["forwards"] += 1
-        st["forward_sizes"].append(len(hands))
+        for part, _ in groups:
+            st["forwards"] += 1
+            st["forward_sizes"].append(len(part))
         mark(f"batch_enqueued {len(hands)}")
-        return {"done": done, "hands": [(fi, j) for fi, j, _ in hands], "dev": dev_res, "frames": frames}   # (frames: alive until finish)
+        return {"done": done, "hands": [(fi, j) for fi, j, _ in hands], "parts": parts}
 
     def batch_finish(job):
         job["done"].synchronize()
         mark(f"batch_done {len(job['hands'])}")
-        res = {k: v.detach().cpu().numpy() for k, v in job["dev"].items()}
-        n = res['betas'].shape[0]
-        res['pose_global'] = rodrigues_log_batch(res['global_orient'].reshape(n, 3, 3))
-        res['pose_hand'] = rodrigues_log_batch(res['hand_pose'].reshape(n * 15, 3, 3)).reshape(n, 45)
-        for r, (fi, j) in enumerate(job["hands"]):
-            files[fi]["rows"][j] = {k: v[r] for k, v in res.items()}
-            files[fi]["out"] -= 1
-        st["hands"] += n
+        done = []                                  # (every part's arrays first, then the commit: a part that raises leaves no rows)
+        for hands, dev_res, _ in job["parts"]:
+            res = {k: v.detach().cpu().numpy() for k, v in dev_res.items()}
+            n = res['betas'].shape[0]
+            res['pose_global'] = rodrigues_log_batch(res['global_orient'].reshape(n, 3, 3))
+            res['pose_hand'] = rodrigues_log_batch(res['hand_pose'].reshape(n * 15, 3, 3)).reshape(n, 45)
+            done.append((hands, res, n))
+        for hands, res, n in done:
+            for r, (fi, j) in enumerate(hands):
+                files[fi]["rows"][j] = {k: v[r] for k, v in res.items()}
+                files[fi]["out"] -= 1
+            st["hands"] += n
 
     def batch_failed(hands, stream, err):
         """A batch that raised: redo it frame by frame so that one bad box costs its own frame's hands only."""
@@ -983,10 +1020,24 @@ def flip_axis_angle(rvec):
     return np.array([rvec[0], rvec[1], rvec[2]], dtype=rvec.dtype)
 
 
-def process_batch_manopara_with_mask(input_folder, mask_folder, output_folder, intrinsics_path=None, hamer=None):
+def process_batch_manopara_with_mask(input_folder, mask_folder, output_folder, intrinsics_path=None, hamer=None, batched=False,
+                                     left_label=None, rank: Optional[int] = None, world: Optional[int] = None, **pipeline):
     """infer.py:1099-1220: no detector -- the hand box is the bounding box of label 3 in ``<mask_folder>/<stem>.npy``,
     always treated as a right hand; intrinsics from one txt file or from ``<intrinsics_path>/<stem>.txt`` per frame.
-    Saves ``<stem>.npy`` with the same record as process_batch_manopara."""
+    Saves ``<stem>.npy`` with the same record as process_batch_manopara.
+
+    ``batched=False`` is the reference's loop, file after file, and returns None.  ``batched=True`` writes the same files from the
+    pipeline of ``iter_folder_results`` with a ``mask_boxes.MaskBoxes`` as its box source: the boxes of a pass of masks come from
+    one hm_mask_boxes launch, the hands go through forwards of ``hands_per_forward``, with an intrinsics directory every hand
+    gets its own frame's K (frames without a txt use the default camera, in a forward of their own).  A frame whose label
+    exists but yields no hand (a single-pixel label has no crop) gets the loop's ``{'left': None, 'right': None}``; a frame
+    without a mask or without the label writes nothing.  ``left_label=L`` (batched only) adds a ``'left'`` record from label L,
+    ``right_label`` (a pipeline keyword, default 3) names the right hand's label.  Sharded by ``rank`` / ``world`` like the
+    other drivers; returns this rank's stats dict.  Further keywords go to ``iter_folder_results``."""
+    if batched:
+        return _mask_driver_batched(input_folder, mask_folder, output_folder, intrinsics_path, hamer, left_label, rank, world, **pipeline)
+    if left_label is not None or pipeline or rank is not None or world is not None:
+        raise ValueError("left_label, rank / world and the pipeline keywords need batched=True")
     os.makedirs(output_folder, exist_ok=True)
     fixed_k, intrinsics_dir = None, None
     if intrinsics_path:
@@ -1024,6 +1075,44 @@ def process_batch_manopara_with_mask(input_folder, mask_folder, output_folder, i
         except Exception as e:
             print(f"Error processing file {img_path}: {e}")
             continue
+
+
+def _mask_driver_batched(input_folder, mask_folder, output_folder, intrinsics_path, hamer, left_label, rank, world,
+                         right_label: int = 3, **pipeline):
+    """process_batch_manopara_with_mask(batched=True): the loop's files from the folder pipeline (see there)."""
+    from .mask_boxes import MaskBoxes
+    os.makedirs(output_folder, exist_ok=True)
+    fixed_k, frame_k = None, None
+    if intrinsics_path:
+        if os.path.isfile(intrinsics_path):
+            fixed_k = load_intrinsics(intrinsics_path)
+        elif os.path.isdir(intrinsics_path):
+            def frame_k(img_path):
+                txt_path = os.path.join(intrinsics_path, os.path.splitext(os.path.basename(img_path))[0] + ".txt")
+                return load_intrinsics(txt_path) if os.path.exists(txt_path) else None
+        else:
+            print(f"[Warning] invalid intrinsics path: {intrinsics_path}")
+    source = MaskBoxes(mask_folder, right_label=right_label, left_label=left_label)
+    if hamer is None:
+        hamer = hamer_inference(hamer_opt)
+    rank, world = _rank_world(rank, world)
+    stats: Dict = {}
+    written = set()
+    for img_path, detection_list, hands in iter_folder_results(_list_images(input_folder), hamer, source, fixed_k, rank=rank,
+                                                               world=world, stats=stats, frame_k=frame_k, **pipeline):
+        image_results = {'left': None, 'right': None}
+        for i, bbox in enumerate(detection_list):
+            image_results[bbox[0]] = _record_from(hands, i, bbox[0] == 'right')
+        np.save(os.path.join(output_folder, os.path.splitext(os.path.basename(img_path))[0] + ".npy"), image_results)
+        written.add(img_path)
+    # a frame whose label exists but gave no hand (a box without an area has no crop): the loop's estimate raises inside its
+    # try and the record is saved with both hands None
+    for img_path in source.labelled:
+        if img_path not in written:
+            np.save(os.path.join(output_folder, os.path.splitext(os.path.basename(img_path))[0] + ".npy"), {'left': None, 'right': None})
+            written.add(img_path)
+    stats["files"] = len(written)
+    return stats
 
 
 def write_obj(path: str, vertices: np.ndarray, faces: np.ndarray):
@@ -1122,7 +1211,36 @@ def _parser() -> argparse.ArgumentParser:
     _precise_hamer_args(ap)
     _antialias_args(ap)
     _render_args(ap)
+    _mask_args(ap)
     return ap
+
+
+def _mask_args(ap: argparse.ArgumentParser) -> None:
+    ap.add_argument('--masks', type=str, default=None, metavar="DIR",
+                    help="take the hand boxes from the label masks DIR/<name>.npy instead of the detector (the batched "
+                         "process_batch_manopara_with_mask); --intrinsics may then also be a folder of <name>.txt, one K per frame")
+    ap.add_argument('--mask-label', type=int, default=3, help="with --masks: the label of the (right) hand's pixels (default 3, the reference's)")
+    ap.add_argument('--left-mask-label', type=int, default=None, metavar="L",
+                    help="with --masks: also box label L as a left hand, for masks that tell the hands apart (default: right hands only)")
+
+
+def mask_args(ap: argparse.ArgumentParser, args) -> None:
+    """Usage errors of the mask options: ``--masks`` replaces the detector, so a detector option next to it is one; the two
+    labels need ``--masks`` and must fit a byte; an intrinsics folder serves the records only (the drawing steps take one K)."""
+    if not args.masks:
+        if args.left_mask_label is not None or args.mask_label != 3:
+            ap.error("--mask-label / --left-mask-label need --masks DIR")
+        return
+    for flag, on in (("--yolo-weights", args.yolo_weights is not None), ("--precise-detector", args.precise_detector),
+                     ("--tta-detector", args.tta_detector)):
+        if on:
+            ap.error(f"--masks takes the boxes from the masks: {flag} has no detector to act on")
+    for name in ("mask_label", "left_mask_label"):
+        v = getattr(args, name)
+        if v is not None and not 0 <= v <= 255:
+            ap.error(f"--{name.replace('_', '-')} must be in 0..255")
+    if args.intrinsics and os.path.isdir(args.intrinsics) and (args.render or args.hand_maps):
+        ap.error("--render / --hand-maps draw with one camera: give --intrinsics a file, not a folder")
 
 
 def _tta_args(ap: argparse.ArgumentParser) -> None:
@@ -1207,7 +1325,9 @@ def main(argv=None):
     ap = _parser()
     args = ap.parse_args(argv)
     keypoint_kw = render_keypoint_args(ap, args)
-    k_real = load_intrinsics(args.intrinsics) if args.intrinsics else None
+    mask_args(ap, args)
+    per_frame_k = bool(args.masks and args.intrinsics and os.path.isdir(args.intrinsics))      # (a folder of <name>.txt: records only)
+    k_real = load_intrinsics(args.intrinsics) if args.intrinsics and not per_frame_k else None
     if args.ckpt:
         hamer_opt.ckpt_path = args.ckpt
     if args.yolo_weights:
@@ -1223,7 +1343,11 @@ def main(argv=None):
     if world > 1 and torch.cuda.is_available():
         torch.cuda.set_device(local)
     hamer = hamer_inference(hamer_opt)
-    stats = process_batch_manopara(args.input, args.output, k_real, hamer=hamer, rank=rank, world=world)
+    if args.masks:
+        stats = process_batch_manopara_with_mask(args.input, args.masks, args.output, args.intrinsics, hamer=hamer, batched=True,
+                                                 left_label=args.left_mask_label, rank=rank, world=world, right_label=args.mask_label)
+    else:
+        stats = process_batch_manopara(args.input, args.output, k_real, hamer=hamer, rank=rank, world=world)
     if world > 1:
         gather_job_stats(stats)
         if rank == 0:

@@ -47,6 +47,7 @@ EXPORTS = [
     "hm_tta_sizes", "hm_tta_tables", "hm_tta_scale", "hm_yolo_decode_batch_tta",
     "hm_mesh_score", "hm_pck_auc_workspace_bytes", "hm_pck_auc",
     "hm_mask_score_workspace_bytes", "hm_mask_score",
+    "hm_mask_boxes",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -116,6 +117,11 @@ class PckAucArgs(C.Structure):
 class MaskQuery(C.Structure):
     """hm_mask_query: pred = id_lo <= pred_id < id_hi, gt = mask == label (label -1: mask != 0), both of frame ``frame``."""
     _fields_ = [(n, C.c_int32) for n in ("frame", "id_lo", "id_hi", "label")]
+
+
+class BoxQuery(C.Structure):
+    """hm_box_query: the pixels of frame ``frame`` with mask == label (label -1: mask != 0)."""
+    _fields_ = [(n, C.c_int32) for n in ("frame", "label")]
 
 
 class VitBlock(C.Structure):
@@ -307,6 +313,7 @@ def load() -> C.CDLL:
     lib.hm_mask_score_workspace_bytes.argtypes = [i, i, i, i]
     lib.hm_mask_score_workspace_bytes.restype = C.c_size_t
     lib.hm_mask_score.argtypes = [vp, vp, i, i, i, vp, i, i, vp, vp, C.c_size_t, vp]
+    lib.hm_mask_boxes.argtypes = [vp, i, i, i, vp, i, vp, vp]
     lib.hm_skeleton_overlay_workspace_bytes.argtypes = [i, i, i, i]
     lib.hm_skeleton_overlay_workspace_bytes.restype = C.c_size_t
     lib.hm_skeleton_overlay.argtypes = [vp, i, i, i, vp, i, C.POINTER(Skeleton), i, C.POINTER(C.c_uint8), i, vp, vp, C.c_size_t, vp]

@@ -916,6 +916,26 @@ size_t hm_mask_score_workspace_bytes(int Q, int H, int W, int radius);   /* 0 fo
 int hm_mask_score(const int32_t* pred_id, const uint8_t* mask, int N, int H, int W, const hm_mask_query* queries /* device */,
                   int Q, int radius, int64_t* counts /* device [Q][8] */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Mask boxes: the tight bounding box and the pixel count of a label in a label mask, for many (frame, label) queries in
+ * one call: csrc/mask_boxes.hip.  It is what get_bbox_from_npy (infer.py:1040-1072) takes from `np.where(mask == label)`, and
+ * what feeds the batched mask-driven folder driver its hand boxes (hamer_yolo_amd/mask_boxes.py).
+ *
+ * mask [N][H][W] uint8 is a batch of label images.  A pixel belongs to query q when mask == label, or mask != 0 when
+ * label == -1 (hm_mask_query's convention; any other label outside 0..255 is in no byte).  boxes[q] = x1, y1, x2, y2, count:
+ * the least / greatest column, the least / greatest row and the number of such pixels of frame `frame`.  No such pixel, or a
+ * frame outside 0..N-1 (which is not read), gives -1, -1, -1, -1, 0.  All five values of every query are written on every
+ * call (callers do not clear them).  Several queries may name one frame.  A query's row depends on its own frame alone: not on
+ * Q, the order of the queries, the rest of the batch or the grid (integer min / max / add atomics behind an initialisation
+ * that is part of the call).  The frame is read as H * W consecutive bytes in 16-byte vectors from the first aligned address,
+ * with up to 15 single bytes before and after: W, H * W and the mask's address need not be multiples of anything.
+ * Asynchronous on `stream`: two kernels, no host synchronisation, no allocation.  Q == 0 succeeds and launches nothing
+ * (queries and boxes may then be NULL).  HM_ERR_ARG before any device work: a null pointer, N, H or W < 1, N H W >= 2^31,
+ * Q < 0, queries or boxes not 4-byte aligned.
+ * Measured on an MI355X: tools/bench_mask_driver.py, profiles/mask_boxes_bench.log ("The mask-driven folder driver"). */
+typedef struct hm_box_query { int32_t frame, label; } hm_box_query;
+int hm_mask_boxes(const uint8_t* mask /* [N][H][W] */, int N, int H, int W, const hm_box_query* queries /* device */, int Q,
+                  int32_t* boxes /* device [Q][5]: x1, y1, x2, y2, count */, void* stream);
+
 /* ---- Detector evaluation (yolo/yolov7/test.py and utils/metrics.py): csrc/det_eval.hip.  The caller owns every buffer, the
  * calls are asynchronous on `stream`, nothing synchronises or allocates, argument errors return HM_ERR_ARG before any device
  * work.  All fp32 / fp64 arithmetic is plain IEEE in the order written (no FMA contraction, no fast-math).
