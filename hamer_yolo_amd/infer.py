@@ -1212,7 +1212,35 @@ def _parser() -> argparse.ArgumentParser:
     _antialias_args(ap)
     _render_args(ap)
     _mask_args(ap)
+    _depth_args(ap)
     return ap
+
+
+def _depth_args(ap: argparse.ArgumentParser) -> None:
+    ap.add_argument('--depth-maps', type=str, default=None, metavar="DIR",
+                    help="after the records are written, move every hand along the ray of its origin onto the sensor depth map "
+                         "DIR/<name>.png (16-bit) or DIR/<name>.npy, registered to the frame (evaluate_depth.refine_folder); needs --intrinsics")
+    ap.add_argument('--depth-scale', type=float, default=0.001, metavar="S", help="with --depth-maps: metres per raw unit (default 0.001)")
+
+
+def depth_args(ap: argparse.ArgumentParser, args) -> None:
+    """Usage errors of the depth options: ``--depth-maps`` needs the real camera, ``--depth-scale`` needs ``--depth-maps``."""
+    if not args.depth_maps:
+        if args.depth_scale != 0.001:
+            ap.error("--depth-scale needs --depth-maps DIR")
+        return
+    if not args.intrinsics:
+        ap.error("--depth-maps needs --intrinsics: a depth residual under the default camera means nothing")
+    if not args.depth_scale > 0:
+        ap.error("--depth-scale must be > 0")
+
+
+def refine_records(args, hamer, rank: int, world: int) -> None:
+    """The ``--depth-maps`` step of the drivers: the records of ``--output`` are rewritten in place with depth-refined cam_t."""
+    from . import evaluate_depth as ED
+    r = ED.refine_folder(args.output, args.depth_maps, args.output, hamer, ED.load_cameras(args.intrinsics), unit=args.depth_scale,
+                         image_folder=args.input, rank=rank, world=world)
+    print(f"{r['refined']} of {r['hands']} hands moved onto {args.depth_maps}" + (f" (rank {rank})" if world > 1 else ""))
 
 
 def _mask_args(ap: argparse.ArgumentParser) -> None:
@@ -1326,6 +1354,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     keypoint_kw = render_keypoint_args(ap, args)
     mask_args(ap, args)
+    depth_args(ap, args)
     per_frame_k = bool(args.masks and args.intrinsics and os.path.isdir(args.intrinsics))      # (a folder of <name>.txt: records only)
     k_real = load_intrinsics(args.intrinsics) if args.intrinsics and not per_frame_k else None
     if args.ckpt:
@@ -1354,6 +1383,10 @@ def main(argv=None):
             print(f"{stats['global_frames']} files, {stats['global_hands']} hands over {world} ranks: {stats['per_rank']}")
         import torch.distributed as dist
         dist.barrier()
+    if args.depth_maps:
+        refine_records(args, hamer, rank, world)
+        if world > 1:
+            dist.barrier()
     if args.obj and rank == 0:
         reconstruct_and_save_obj_with_wrapper(args.output, args.obj, hamer)
     if args.render:

@@ -69,7 +69,7 @@ def _pack_meshes(meshes: Sequence[dict], dev: torch.device, N: int, color=None):
         v = torch.as_tensor(m["vertices"]).to(dev, torch.float64).reshape(-1, 3)
         f = torch.as_tensor(m["faces"]).to(dev, torch.int32).reshape(-1, 3)
         ck = (id(m["faces"]), v.shape[0])
-        if f.numel() and ck not in checked:
+        if f.numel() and ck not in checked and not m.get("faces_checked"):     # a caller that checked them itself says so
             if v.shape[0] == 0 or int(f.min()) < 0 or int(f.max()) >= v.shape[0]:
                 raise ValueError(f"mesh {i}: face corner outside its {v.shape[0]} vertices")
             checked[ck] = m["faces"]

@@ -936,6 +936,52 @@ typedef struct hm_box_query { int32_t frame, label; } hm_box_query;
 int hm_mask_boxes(const uint8_t* mask /* [N][H][W] */, int N, int H, int W, const hm_box_query* queries /* device */, int Q,
                   int32_t* boxes /* device [Q][5]: x1, y1, x2, y2, count */, void* stream);
 
+/* ---- Depth residuals: the predicted hands' z-buffer against a sensor depth map: csrc/depth_eval.hip.  Per query a histogram of
+ * `sensor - predicted` over the pixels its meshes cover, six pixel counts and four statistics; from the median follows the
+ * shift of a hand along its viewing ray (hamer/utils/depth_eval.py refine_cam_t).
+ *
+ * pred_depth [N][H][W] f32 (metres, 0 where uncovered) and pred_id [N][H][W] i32 (mesh row or -1) are what hm_mesh_render
+ * writes; sensor [N][H][W] u16 holds raw sensor units, 0 = no measurement; mask [N][H][W] u8 is a label image or NULL;
+ * labels [Q] i32 or NULL gives per query -2 (no mask test), -1 (mask != 0) or 0..255 (mask == label; any other value: no pixel
+ * passes); a NULL mask or NULL labels means no mask test.  mesh_query [n_meshes] i32 names the query a mesh's pixels count for,
+ * or -1 for none; several meshes may share a query (a frame's union of hands).  unit: metres per raw unit; a raw value outside
+ * raw_lo..raw_hi counts as no measurement; bin_m: the bin width in metres; bins: even, 2..4096.
+ *
+ * Rule per pixel p, all arithmetic fp64 and exactly as written: the unit is compiled with contraction off
+ * (#pragma clang fp contract(off)), so no product is fused into a sum.
+ *   1  id = pred_id[p]; the pixel is skipped unless 0 <= id < n_meshes and q = mesh_query[id] is in 0..Q-1
+ *   2  counts[q][0] (covered) += 1
+ *   3  a mask test applies and the pixel fails it: counts[q][1] (off mask) += 1, stop
+ *   4  raw == 0, raw < raw_lo or raw > raw_hi: counts[q][2] (no measurement) += 1, stop
+ *   5  r = (double)raw * unit - (double)pred_depth[p]
+ *   6  k = (long long)floor(r / bin_m) + bins / 2
+ *   7  k < 0: counts[q][3] (below: something nearer than the hand) += 1; k >= bins: counts[q][4] (above) += 1; otherwise
+ *      hist[q][k] += 1 and counts[q][5] (in range) += 1.  (floor(...) below -2^40 is below, at or past 2^40 or NaN is above.)
+ * hist u32 [Q][bins], counts i64 [Q][8] (entries 6 and 7 are written 0) and stats f64 [Q][4] are all written on every call
+ * (callers do not clear them).  stats, from hist and counts alone, with centre(k) = ((double)(k - bins / 2) + 0.5) * bin_m:
+ *   0  the LOWER median: n = below + in_range + above, rank m = (n + 1) / 2 counted from 1, the below pixels first and the above
+ *      pixels last; centre(k) of the bin that holds rank m; NaN when n == 0 or the rank falls in below or above
+ *   1  mean = S1 / in_range, 2 mean absolute = S2 / in_range, 3 rms = sqrt(S3 / in_range), where over the occupied bins in
+ *      ascending k, from 0: S1 += (double)hist[k] * centre(k); S2 += (double)hist[k] * fabs(centre(k));
+ *      S3 += (double)hist[k] * (centre(k) * centre(k)); all three NaN when in_range == 0.
+ * A query's numbers depend on its own pixels and the scalars alone: not on Q, N, the order of the meshes or the grid (the sums
+ * are integer atomics; a workgroup adds its pixels up in LDS first and the pixels it has no room for straight to memory -- the
+ * same integers either way).  Asynchronous on `stream`: three kernels, ONE pass over the pixels for all queries, no host
+ * synchronisation, no allocation; the workspace keeps each query's range of occupied bins.  Q == 0 succeeds and launches
+ * nothing (mesh_query and the outputs may then be NULL).  HM_ERR_ARG before any device work: a null pointer, N, H or W < 1,
+ * N H W >= 2^31, Q or n_meshes < 0, bins odd or outside 2..4096, unit or bin_m not finite and > 0, raw_lo > raw_hi,
+ * workspace_bytes below the query, counts or stats not 8-byte aligned, hist, workspace or a 32-bit input not 4-byte aligned.
+ * Measured on an MI355X (tools/bench_depth_eval.py, profiles/depth_eval_bench.log; per call, host submission included, 1080 x 1920,
+ * four meshes per frame, every hand pixel in one bin): 16 frames with one query per frame 0.546 ms, with one per mesh 0.401 ms;
+ * 64 frames 0.901 / 0.678 ms (the same histograms from torch ops on the device 3.96 / 14.6 / 15.3 / 58.5 ms); bound by its
+ * atomics, not by memory (0.24-0.78 TB/s of pred_id; hm_mask_boxes reads masks at 2.1-4.5 TB/s): DESIGN.md section 10.3. */
+size_t hm_depth_residuals_workspace_bytes(int Q, int bins);   /* 0 for an illegal Q or bins; positive otherwise */
+int hm_depth_residuals(const float* pred_depth, const int32_t* pred_id, const uint16_t* sensor, const uint8_t* mask /* or NULL */,
+                       const int32_t* labels /* device [Q] or NULL */, int N, int H, int W, const int32_t* mesh_query /* device */,
+                       int n_meshes, int Q, double unit, int raw_lo, int raw_hi, double bin_m, int bins,
+                       uint32_t* hist /* device [Q][bins] */, int64_t* counts /* device [Q][8] */, double* stats /* device [Q][4] */,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Detector evaluation (yolo/yolov7/test.py and utils/metrics.py): csrc/det_eval.hip.  The caller owns every buffer, the
  * calls are asynchronous on `stream`, nothing synchronises or allocates, argument errors return HM_ERR_ARG before any device
  * work.  All fp32 / fp64 arithmetic is plain IEEE in the order written (no FMA contraction, no fast-math).
