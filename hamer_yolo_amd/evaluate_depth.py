@@ -2,7 +2,7 @@
 
     python -m hamer_yolo_amd.evaluate_depth --pred <records dir> --depth-maps <depth dir> --intrinsics <K.txt or dir>
                                             [--depth-scale 0.001] [--masks DIR --label 3] [--images DIR] [--json out.json]
-                                            [--refine-to DIR]
+                                            [--refine-to DIR [--refine-mode ray|rigid]]
 
 ``--pred`` holds the ``<stem>.npy`` hand records the folder job writes and ``--depth-maps`` one depth map per frame, registered
 to the colour frame: ``<stem>.png`` (16-bit, raw units of ``--depth-scale`` metres) or ``<stem>.npy`` (uint16: raw units;
@@ -14,7 +14,11 @@ residuals") and DESIGN.md section 10.3.
 
 ``--refine-to DIR`` writes the records again with every hand moved along the ray of its origin by the median residual (two
 rounds of render, score, shift: ``hamer.utils.depth_eval.refine_cam_t``); the records gain ``cam_t_unrefined``,
-``depth_residual_m``, ``depth_pixels`` and ``depth_refined``.
+``depth_residual_m``, ``depth_pixels`` and ``depth_refined``.  ``--refine-mode rigid`` goes on from there with a rigid
+point-to-plane fit of every hand to the sensor's surface about its wrist joint (six rounds of render, fit, move:
+``hamer.utils.depth_eval.fit_rigid``): the rotation is folded into ``pose_global`` (and ``theta[:3]``),
+the translation into ``cam_t``, and the records also gain ``pose_global_unrefined``, ``depth_fit_rms_m``, ``depth_fit_pixels``
+and ``depth_fit``.
 
 A depth map takes the size of its frame (``--images``: the frames' headers; without, the depth map's own size is the frame's).
 A frame whose depth map, mask or camera is missing or of another size is skipped and named.
@@ -33,6 +37,8 @@ import numpy as np
 FRAMES_PER_PASS = 16
 THRESHOLDS_M = (0.005, 0.010, 0.020)
 NEW_KEYS = ("cam_t_unrefined", "depth_residual_m", "depth_pixels", "depth_refined")
+FIT_KEYS = ("pose_global_unrefined", "depth_fit_rms_m", "depth_fit_pixels", "depth_fit")      # --refine-mode rigid adds these
+REFINE_MODES = ("ray", "rigid")
 
 
 def find_depth(depth_folder: str, stem: str) -> Optional[str]:
@@ -230,27 +236,90 @@ def _refined_record(data: Dict, moved: Dict) -> Dict:
     return out
 
 
+def _exp_so3(w) -> np.ndarray:
+    """Rodrigues' formula, fp64: a rotation vector (3,) -> (3, 3)."""
+    w = np.asarray(w, np.float64).reshape(3)
+    th = float(np.sqrt((w * w).sum()))
+    Kx = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    a, b = (1.0 - th * th / 6.0, 0.5 - th * th / 24.0) if th < 1e-8 else (np.sin(th) / th, (1.0 - np.cos(th)) / (th * th))
+    return np.eye(3) + a * Kx + b * (Kx @ Kx)
+
+
+def _log_so3(R) -> np.ndarray:
+    """The rotation vector (3,) of a rotation matrix, fp64; angles up to pi (at pi the axis comes from R + I)."""
+    R = np.asarray(R, np.float64)
+    w = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s, c = 0.5 * float(np.sqrt((w * w).sum())), 0.5 * (float(np.trace(R)) - 1.0)
+    th = float(np.arctan2(s, c))
+    if s >= 1e-6:
+        return w * (th / (2.0 * s))
+    if c > 0:
+        return 0.5 * w
+    col = (R + np.eye(3))[:, int(np.argmax(np.diag(R)))]
+    return col / np.linalg.norm(col) * th
+
+
+def fold_rotation(pose_global, rotation, is_right: bool) -> np.ndarray:
+    """The global orientation (3,) fp64 of a record whose placed mesh was turned by ``rotation`` (3, 3) about its placed wrist
+    joint.  MANO turns the hand about that joint, so for a right hand the new orientation is log(R exp(pose_global)); a left
+    hand's mesh is mirrored by M = diag(-1, 1, 1) after MANO, so R acts on MANO's output as M R M."""
+    M = np.diag([1.0 if is_right else -1.0, 1.0, 1.0])
+    return _log_so3(M @ np.asarray(rotation, np.float64) @ M @ _exp_so3(pose_global))
+
+
+def _fitted_record(data: Dict, moved: Dict, fitted: Dict) -> Dict:
+    """``_refined_record`` plus FIT_KEYS on every hand; ``fitted``: side -> (rotation (3, 3), rms, pixels, applied) of the
+    fitted hands.  An applied rotation goes into ``pose_global`` and, where the record has one, ``theta[:3]``."""
+    out = _refined_record(data, moved)
+    for t in ("right", "left"):
+        if out.get(t) is None:
+            continue
+        h = out[t]
+        old = h["pose_global"]
+        h.setdefault("pose_global_unrefined", old)
+        h["depth_fit_rms_m"], h["depth_fit_pixels"], h["depth_fit"] = float("nan"), 0, False
+        if t in fitted:
+            R, rms, pixels, applied = fitted[t]
+            if applied:
+                new = fold_rotation(old, R, bool(h["is_right"]))
+                h["pose_global"] = new.astype(np.asarray(old).dtype).reshape(np.asarray(old).shape)
+                if h.get("theta") is not None:
+                    theta = np.array(h["theta"])
+                    theta.reshape(-1)[:3] = h["pose_global"].reshape(-1)
+                    h["theta"] = theta
+            h["depth_fit_rms_m"], h["depth_fit_pixels"], h["depth_fit"] = float(rms), int(pixels), bool(applied)
+    return out
+
+
 def refine_folder(npy_folder, depth_folder, out_folder, hamer, k_real, unit: float = 0.001, mask_folder=None, label: int = 3,
                   iterations: int = 2, min_pixels: int = 200, min_fraction: float = 0.25, image_folder=None, rank: int = 0,
-                  world: int = 1, frames_per_pass: int = FRAMES_PER_PASS) -> Dict:
+                  world: int = 1, frames_per_pass: int = FRAMES_PER_PASS, mode: str = "ray", fit_iterations: int = 6) -> Dict:
     """Write every record of ``npy_folder`` to ``out_folder`` (which may be the same folder) with its hands moved along the
     rays of their origins onto the depth maps: ``refine_cam_t`` per pass, with the pass structure and arguments of
     ``score_folder``.  Every hand gains ``cam_t_unrefined`` (its cam_t before), ``depth_residual_m`` (the last median; NaN
     when it was not scored), ``depth_pixels`` (the valid pixels behind it) and ``depth_refined``; every other key keeps its
     type and, for a hand that was not moved, its bytes.  A record whose frame is skipped is written with those defaults.
-    Returns ``{'records', 'hands', 'refined', 'skipped', 'n_skipped'}``."""
+    ``mode='rigid'`` goes on from the ray rounds with ``fit_iterations`` rounds of ``fit_rigid`` about every hand's wrist
+    joint (joint 0 of MANO, mirrored for a left hand, plus cam_t) and folds the fit into the record: ``pose_global`` (and
+    ``theta[:3]``) takes the rotation (``fold_rotation``), ``cam_t`` the translation, and every hand also gains FIT_KEYS:
+    ``pose_global_unrefined``, ``depth_fit_rms_m`` (the last point-to-plane rms; NaN when no pixel was used),
+    ``depth_fit_pixels`` and ``depth_fit`` (a rigid step was applied).  ``mode='ray'`` writes what it always wrote.
+    Returns ``{'records', 'hands', 'refined', 'skipped', 'n_skipped'}``, in rigid mode also ``'fitted'``."""
     import torch
     from . import render
     from .hamer.utils import depth_eval as DE
-    from .infer import mano_hand_vertices
+    from .infer import mano_hand_joints_vertices, mano_hand_vertices
     _check(k_real, label, unit)
+    if mode not in REFINE_MODES:
+        raise ValueError(f"mode must be one of {REFINE_MODES}, got {mode!r}")
     os.makedirs(out_folder, exist_ok=True)
     jobs = _jobs(npy_folder, depth_folder, image_folder, rank, world)
     dev = hamer.device
     faces = torch.as_tensor(np.asarray(hamer.mano.faces, np.int32), device=dev)
     moved: Dict[int, Dict] = {}
+    fitted: Dict[int, Dict] = {}
     skipped: List[str] = []
-    n_hands = n_refined = 0
+    n_hands = n_refined = n_fitted = 0
     try:
         with ThreadPoolExecutor(render._encode_threads()) as pool:
             for (H, W), part, sensor, masks, K in _passes(jobs, k_real, depth_folder, mask_folder, image_folder, unit,
@@ -258,8 +327,24 @@ def refine_folder(npy_folder, depth_folder, out_folder, hamer, k_real, unit: flo
                 hands = [(n, i, t) for n, i in enumerate(part) for t in jobs[i][3]]
                 recs = [jobs[i][2][t] for _, i, t in hands]
                 sign = torch.tensor([[1.0, 1.0, 1.0] if h["is_right"] else [-1.0, 1.0, 1.0] for h in recs], device=dev)
-                verts = mano_hand_vertices(hamer, recs) * sign[:, None, :]
                 cam_t = torch.tensor(np.stack([np.asarray(h["cam_t"], np.float32).reshape(3) for h in recs]), device=dev)
+                if mode == "rigid":
+                    joints, verts = mano_hand_joints_vertices(hamer, recs)
+                    pivot = (joints[:, 0, :] * sign).to(torch.float64) + cam_t.to(torch.float64)
+                    r = DE.fit_rigid(H, W, K, verts * sign[:, None, :], faces, cam_t, pivot, [n for n, _, _ in hands],
+                                     torch.from_numpy(sensor).to(dev), unit=unit, ray_iterations=iterations,
+                                     iterations=fit_iterations, min_pixels=min_pixels, min_fraction=min_fraction,
+                                     mask=None if masks is None else torch.from_numpy(masks).to(dev),
+                                     labels=None if masks is None else [int(label)] * len(hands))
+                    new, med, pix, upd, rot, rms, used, fit = (r[k].cpu().numpy() for k in ("cam_t", "median", "valid", "updated",
+                                                                                            "rotation", "rms", "used", "fitted"))
+                    for j, (_, i, t) in enumerate(hands):
+                        moved.setdefault(i, {})[t] = (new[j], med[j], pix[j], upd[j])
+                        fitted.setdefault(i, {})[t] = (rot[j], rms[j], used[j], fit[j])
+                    n_refined += int(upd.sum())
+                    n_fitted += int(fit.sum())
+                    continue
+                verts = mano_hand_vertices(hamer, recs) * sign[:, None, :]
                 r = DE.refine_cam_t(H, W, K, verts, faces, cam_t, [n for n, _, _ in hands], torch.from_numpy(sensor).to(dev),
                                     unit=unit, iterations=iterations, min_pixels=min_pixels, min_fraction=min_fraction,
                                     mask=None if masks is None else torch.from_numpy(masks).to(dev),
@@ -270,11 +355,16 @@ def refine_folder(npy_folder, depth_folder, out_folder, hamer, k_real, unit: flo
                 n_refined += int(upd.sum())
         for i, job in enumerate(jobs):
             n_hands += len(job[3])
-            np.save(os.path.join(out_folder, job[0] + ".npy"), _refined_record(job[2], moved.get(i, {})))
+            rec = _refined_record(job[2], moved.get(i, {})) if mode == "ray" else _fitted_record(job[2], moved.get(i, {}), fitted.get(i, {}))
+            np.save(os.path.join(out_folder, job[0] + ".npy"), rec)
     finally:
         render.release_workspaces()
         DE.release_workspaces()
-    return {"records": len(jobs), "hands": n_hands, "refined": n_refined, "skipped": skipped, "n_skipped": len(skipped)}
+        DE.release_fit_workspaces()
+    out = {"records": len(jobs), "hands": n_hands, "refined": n_refined, "skipped": skipped, "n_skipped": len(skipped)}
+    if mode == "rigid":
+        out["fitted"] = n_fitted
+    return out
 
 
 def format_line(result: Dict) -> str:
@@ -295,6 +385,9 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument('--label', type=int, default=3, help="with --masks: the mask value of hand pixels (the reference's masks use 3)")
     ap.add_argument('--images', type=str, default=None, help="folder of the frames (headers only: the size a depth map must have)")
     ap.add_argument('--refine-to', type=str, default=None, metavar="DIR", help="also write the records with depth-refined cam_t into DIR")
+    ap.add_argument('--refine-mode', type=str, default="ray", choices=REFINE_MODES,
+                    help="with --refine-to: ray (default) moves every hand along the ray of its origin; rigid goes on with a "
+                         "point-to-plane fit of all six degrees of freedom about the wrist and folds it into pose_global and cam_t")
     ap.add_argument('--json', type=str, default=None, help="also write the result, per-hand rows included, to this file")
     ap.add_argument('--ckpt', type=str, default=None, help="hamer.ckpt path or synthetic:<seed> (default: config/hamer_config.py); only its MANO model is used")
     return ap
@@ -316,7 +409,7 @@ def main(argv=None):
     kw = dict(unit=args.depth_scale, mask_folder=args.masks, label=args.label, image_folder=args.images)
     result = score_folder(args.pred, args.depth_maps, hamer, k_real, **kw)
     if args.refine_to:
-        result["refine"] = refine_folder(args.pred, args.depth_maps, args.refine_to, hamer, k_real, **kw)
+        result["refine"] = refine_folder(args.pred, args.depth_maps, args.refine_to, hamer, k_real, mode=args.refine_mode, **kw)
         print(f"{result['refine']['refined']} of {result['refine']['hands']} hands refined into {args.refine_to}")
     if args.json:
         with open(args.json, "w") as f:

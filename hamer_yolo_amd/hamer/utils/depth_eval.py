@@ -266,3 +266,191 @@ def refine_cam_t(H: int, W: int, K, vertices: torch.Tensor, faces, cam_t: torch.
         cur = torch.where(ok[:, None], moved, cur)
         updated = updated | ok
     return {"cam_t": cur, "median": median, "valid": valid, "updated": updated}
+
+
+# ---------------------------------------------------------------------------------------------------------------- depth fit
+FIT_COUNT_NAMES = ("covered", "off_mask", "no_measurement", "gated", "no_normal", "rejected", "used", "reserved7")
+
+_fit_ws: Dict[tuple, torch.Tensor] = {}    # (device index, stream) -> hm_depth_fit's workspace, grown on demand
+
+
+def release_fit_workspaces() -> None:
+    """Drop depth_fit's cached workspaces (288 bytes per query each)."""
+    _fit_ws.clear()
+
+
+def _cameras(K, N: int, dev) -> torch.Tensor:
+    """(N, 4) float64 fx, fy, cx, cy on ``dev`` of K (3, 3) or (N, 3, 3), an array or a tensor (a device tensor is not copied
+    to the host)."""
+    Kt = K.to(dev, torch.float64) if torch.is_tensor(K) else torch.from_numpy(np.asarray(K, np.float64)).to(dev)
+    if tuple(Kt.shape) == (3, 3):
+        Kt = Kt[None].expand(N, 3, 3)
+    if tuple(Kt.shape) != (N, 3, 3):
+        raise ValueError(f"depth_fit: K must be (3, 3) or ({N}, 3, 3), got {tuple(Kt.shape)}")
+    return torch.stack([Kt[:, 0, 0], Kt[:, 1, 1], Kt[:, 0, 2], Kt[:, 1, 2]], 1).contiguous()
+
+
+def depth_fit(pred_depth: torch.Tensor, pred_id: torch.Tensor, sensor: torch.Tensor, mesh_query, Q: int, K, pivot: torch.Tensor, *,
+              unit: float, gate_m: float = 0.03, edge_m: float = 0.005, reach_m: float = 0.5, damping: float = 1e-3,
+              lever_m: float = 0.05, min_pixels: int = 200, raw_range=(1, 65535), mask: Optional[torch.Tensor] = None,
+              labels=None) -> Dict[str, torch.Tensor]:
+    """One hm_depth_fit call: per query the normal equations of a point-to-plane fit of the predicted surface to the sensor's,
+    and their solution.  The maps, ``mesh_query``, ``Q``, ``unit``, ``raw_range``, ``mask`` and ``labels`` are
+    ``depth_residuals``'; ``K`` (3, 3) or (N, 3, 3); ``pivot`` (Q, 3) float64 on the maps' GPU: the point each query's rotation
+    turns about.  A pixel takes part when its residual is within ``gate_m``, its four neighbours belong to the same mesh within
+    ``edge_m`` of its depth, and it lies within ``reach_m`` of the pivot.  ``damping`` (per used pixel; rotations weighted by
+    ``lever_m`` squared) keeps unobserved directions at rest; below ``min_pixels`` used pixels a query is not solved.
+    Returns ``{'sums': (Q, 28) int64, 'counts': (Q, 8) int64 (FIT_COUNT_NAMES), 'solution': (Q, 8) float64 (omega, t, rms,
+    solved)}`` on the device: the motion is ``p -> p + omega x (p - pivot) + t``.  Enqueued on the current stream without
+    synchronising; the workspace is cached per device and stream (``release_fit_workspaces``).  There is no CPU path."""
+    if not all(torch.is_tensor(t) for t in (pred_depth, pred_id, sensor)):
+        raise ValueError("depth_fit: pred_depth, pred_id and sensor must be tensors")
+    dev = pred_id.device
+    if not (pred_id.is_cuda and pred_depth.device == dev and sensor.device == dev):
+        raise ValueError("depth_fit: pred_depth, pred_id and sensor must be on one GPU; there is no CPU path")
+    if pred_depth.dtype != torch.float32 or pred_id.dtype != torch.int32 or sensor.dtype not in (torch.uint16, torch.int16):
+        raise ValueError(f"depth_fit: expected float32, int32 and uint16, got {pred_depth.dtype}, {pred_id.dtype}, {sensor.dtype}")
+    shape = tuple(pred_id.shape)
+    if pred_id.dim() != 3 or 0 in shape or tuple(pred_depth.shape) != shape or tuple(sensor.shape) != shape:
+        raise ValueError(f"depth_fit: pred_depth {tuple(pred_depth.shape)} / pred_id {shape} / sensor {tuple(sensor.shape)}: "
+                         "expected three (N, H, W)")
+    if not (pred_depth.is_contiguous() and pred_id.is_contiguous() and sensor.is_contiguous()):
+        raise ValueError("depth_fit: pred_depth, pred_id and sensor must be contiguous")
+    if (mask is None) != (labels is None):
+        raise ValueError("depth_fit: mask and labels are given both or neither")
+    if mask is not None and not (torch.is_tensor(mask) and mask.device == dev and mask.dtype == torch.uint8
+                                 and tuple(mask.shape) == shape and mask.is_contiguous()):
+        raise ValueError(f"depth_fit: mask must be a contiguous uint8 tensor of shape {shape} on {dev}")
+    Q, min_pixels = int(Q), int(min_pixels)
+    if Q < 0:
+        raise ValueError("depth_fit: Q must not be negative")
+    if not (np.isfinite(unit) and unit > 0):
+        raise ValueError("depth_fit: unit must be finite and > 0")
+    if not (0 < gate_m <= 0.25 and 0 < edge_m < np.inf and 0 < reach_m <= 1 and 0 <= damping < np.inf and 0 < lever_m < np.inf
+            and min_pixels >= 1):
+        raise ValueError("depth_fit: expected gate_m in (0, 0.25], edge_m > 0, reach_m in (0, 1], damping >= 0, lever_m > 0 "
+                         "and min_pixels >= 1")
+    raw_lo, raw_hi = int(raw_range[0]), int(raw_range[1])
+    if raw_lo > raw_hi:
+        raise ValueError("depth_fit: raw_range must be (lo, hi) with lo <= hi")
+    if not (torch.is_tensor(pivot) and pivot.device == dev and pivot.dtype == torch.float64 and tuple(pivot.shape) == (Q, 3)
+            and pivot.is_contiguous()):
+        raise ValueError(f"depth_fit: pivot must be a contiguous float64 tensor of shape ({Q}, 3) on {dev}")
+    N, H, W = shape
+    cams = _cameras(K, N, dev)
+    mq = _int32_on(mesh_query, dev, None, "mesh_query")
+    lab = None
+    if labels is not None:
+        if not torch.is_tensor(labels) and any(not -2 <= int(v) <= 255 for v in np.asarray(labels).reshape(-1)):
+            raise ValueError("depth_fit: a label must be -2, -1 or 0..255")
+        lab = _int32_on(labels, dev, Q, "labels")
+    out = {"sums": torch.empty(Q, 28, dtype=torch.int64, device=dev), "counts": torch.empty(Q, 8, dtype=torch.int64, device=dev),
+           "solution": torch.empty(Q, 8, dtype=torch.float64, device=dev)}
+    if Q == 0:
+        return out
+    lib = L.load()
+    need = int(lib.hm_depth_fit_workspace_bytes(Q))
+    with torch.cuda.device(dev):
+        stream = L.current_stream()
+        key = (dev.index if dev.index is not None else torch.cuda.current_device(), stream)
+        ws = _fit_ws.get(key)
+        if ws is None or ws.numel() * 8 < need:
+            _fit_ws.pop(key, None)
+            ws = _fit_ws[key] = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        L.check(lib.hm_depth_fit(L.ptr(pred_depth), L.ptr(pred_id), L.ptr(sensor), L.ptr(mask), L.ptr(lab), N, H, W,
+                                 L.ptr(mq) if mq.numel() else None, int(mq.numel()), Q, L.ptr(cams), L.ptr(pivot), float(unit),
+                                 raw_lo, raw_hi, float(gate_m), float(edge_m), float(reach_m), float(damping), float(lever_m),
+                                 min_pixels, L.ptr(out["sums"]), L.ptr(out["counts"]), L.ptr(out["solution"]), L.ptr(ws),
+                                 ws.numel() * 8, stream), "hm_depth_fit")
+    return out
+
+
+def exp_so3(omega: torch.Tensor) -> torch.Tensor:
+    """Rodrigues' formula on the device, fp64: (B, 3) rotation vectors -> (B, 3, 3); the series below 1e-8 rad."""
+    w = omega.to(torch.float64)
+    th = torch.sqrt((w * w).sum(-1))[:, None, None]
+    z = torch.zeros_like(w[:, 0])
+    Kx = torch.stack([torch.stack([z, -w[:, 2], w[:, 1]], -1), torch.stack([w[:, 2], z, -w[:, 0]], -1),
+                      torch.stack([-w[:, 1], w[:, 0], z], -1)], -2)
+    small = th < 1e-8
+    ths = torch.where(small, torch.ones_like(th), th)
+    a = torch.where(small, 1.0 - th * th / 6.0, torch.sin(ths) / ths)
+    b = torch.where(small, 0.5 - th * th / 24.0, (1.0 - torch.cos(ths)) / (ths * ths))
+    return torch.eye(3, dtype=torch.float64, device=w.device) + a * Kx + b * (Kx @ Kx)
+
+
+def fit_rigid(H: int, W: int, K, vertices: torch.Tensor, faces, cam_t: torch.Tensor, pivot: torch.Tensor,
+              frame_index: Sequence[int], sensor: torch.Tensor, *, unit: float, ray_iterations: int = 2, iterations: int = 6,
+              max_rot_rad: float = 0.5, max_shift_m: float = 0.1, gate_m: float = 0.03, edge_m: float = 0.005,
+              reach_m: float = 0.5, damping: float = 1e-3, lever_m: float = 0.05, min_pixels: int = 200, min_fraction: float = 0.25,
+              znear: float = 0.05, mask: Optional[torch.Tensor] = None, labels=None, bin_m: float = 0.0005, bins: int = 4096,
+              raw_range=(1, 65535)) -> Dict[str, torch.Tensor]:
+    """Fit hands rigidly -- all six degrees of freedom -- to the sensor's depth.  Arguments as ``refine_cam_t``, and ``pivot``
+    (B, 3): the point of each hand, in the camera frame, its rotation turns about (the wrist joint plus ``cam_t`` folds the
+    result into a MANO record).  First ``ray_iterations`` rounds of ``refine_cam_t`` bring the hands inside the gate (the
+    pivot moves with its hand); then per iteration ``render_views`` of the placed vertices (depth and mesh_id), ONE
+    ``depth_fit`` call with one query per hand, and on the device, in fp64,
+
+        R <- exp(omega) R;   placed <- exp(omega) (placed - pivot) + pivot + t;   pivot <- pivot + t
+
+    for the hands that were solved with |omega| <= ``max_rot_rad`` and |t| <= ``max_shift_m``.  Nothing inside the loops
+    synchronises with the host.  Returns ``{'rotation': (B, 3, 3) float64 (the product of the applied steps), 'cam_t': (B, 3)
+    like cam_t (the ray rounds' plus the sum of the applied t), 'pivot': (B, 3) float64, 'placed': (B, V, 3) float64 (the fitted
+    vertices: rotation (vertices + ray cam_t - ray pivot) + pivot), 'rms': (B,) float64 and 'used': (B,) int64 of the last
+    iteration, 'updated': (B,) bool (a ray or a rigid step was applied), 'fitted': (B,) bool (a rigid step was), 'median' and
+    'valid': the ray rounds' last (NaN and 0 without any)}``; a hand that never had a step applied keeps its bytes."""
+    from ... import render
+    if not (torch.is_tensor(vertices) and torch.is_tensor(cam_t) and torch.is_tensor(pivot) and vertices.is_cuda
+            and cam_t.device == vertices.device and pivot.device == vertices.device):
+        raise ValueError("fit_rigid: vertices, cam_t and pivot must be tensors on one GPU; there is no CPU path")
+    B = int(cam_t.shape[0])
+    if vertices.dim() != 3 or int(vertices.shape[0]) != B or tuple(cam_t.shape) != (B, 3) or tuple(pivot.shape) != (B, 3) \
+            or len(frame_index) != B:
+        raise ValueError("fit_rigid: expected vertices (B, V, 3), cam_t (B, 3), pivot (B, 3) and B frame indices")
+    dev = vertices.device
+    N = int(sensor.shape[0])
+    faces = torch.as_tensor(faces).to(dev, torch.int32).reshape(-1, 3)
+    if faces.numel() and (int(faces.min()) < 0 or int(faces.max()) >= int(vertices.shape[1])):      # once, before the loops
+        raise ValueError(f"fit_rigid: face corner outside the {int(vertices.shape[1])} vertices")
+    cams = _cameras(K, N, dev)
+    if int(ray_iterations) > 0:
+        ray = refine_cam_t(H, W, K, vertices, faces, cam_t, frame_index, sensor, unit=unit, iterations=int(ray_iterations),
+                           min_pixels=min_pixels, min_fraction=min_fraction, znear=znear, mask=mask, labels=labels, bin_m=bin_m,
+                           bins=bins, raw_range=raw_range)
+        cam_ray, updated, median, valid = ray["cam_t"], ray["updated"], ray["median"], ray["valid"]
+    else:
+        cam_ray, updated = cam_t, torch.zeros(B, dtype=torch.bool, device=dev)
+        median = torch.full((B,), float("nan"), dtype=torch.float64, device=dev)
+        valid = torch.zeros(B, dtype=torch.int64, device=dev)
+    cam64 = cam_ray.to(torch.float64)
+    pv = (pivot.to(torch.float64) + (cam64 - cam_t.to(torch.float64))).contiguous()
+    placed = vertices.to(torch.float64) + cam64[:, None, :]
+    Kn = torch.zeros(N, 3, 3, dtype=torch.float64, device=dev)                                     # depth_fit takes K as (N, 3, 3)
+    Kn[:, 0, 0], Kn[:, 1, 1], Kn[:, 0, 2], Kn[:, 1, 2], Kn[:, 2, 2] = cams[:, 0], cams[:, 1], cams[:, 2], cams[:, 3], 1.0
+    query = torch.arange(B, dtype=torch.int32, device=dev)
+    lab = None if labels is None else _int32_on(labels, dev, B, "labels")
+    R = torch.eye(3, dtype=torch.float64, device=dev)[None].repeat(B, 1, 1)
+    shift = torch.zeros(B, 3, dtype=torch.float64, device=dev)
+    fitted = torch.zeros(B, dtype=torch.bool, device=dev)
+    rms = torch.full((B,), float("nan"), dtype=torch.float64, device=dev)
+    used = torch.zeros(B, dtype=torch.int64, device=dev)
+    for _ in range(int(iterations)):
+        meshes = [{"frame": int(f), "vertices": placed[j], "faces": faces, "faces_checked": True} for j, f in enumerate(frame_index)]
+        r = render.render_views(H, W, K, meshes, outputs=("depth", "mesh_id"), znear=znear, views=N, device=dev)
+        s = depth_fit(r["depth"], r["mesh_id"], sensor, query, B, Kn, pv, unit=unit, gate_m=gate_m, edge_m=edge_m, reach_m=reach_m,
+                      damping=damping, lever_m=lever_m, min_pixels=min_pixels, raw_range=raw_range, mask=mask, labels=lab)
+        sol = s["solution"]
+        w, t = sol[:, :3], sol[:, 3:6]
+        ok = (sol[:, 7] > 0.5) & (torch.sqrt((w * w).sum(1)) <= float(max_rot_rad)) & (torch.sqrt((t * t).sum(1)) <= float(max_shift_m))
+        E = exp_so3(w)
+        moved = torch.einsum("bij,bvj->bvi", E, placed - pv[:, None, :]) + pv[:, None, :] + t[:, None, :]
+        placed = torch.where(ok[:, None, None], moved, placed)
+        R = torch.where(ok[:, None, None], E @ R, R)
+        step = torch.where(ok[:, None], t, torch.zeros_like(t))
+        shift = shift + step
+        pv = (pv + step).contiguous()
+        fitted = fitted | ok
+        rms, used = sol[:, 6], s["counts"][:, 6]
+    out_t = torch.where(fitted[:, None], (cam64 + shift).to(cam_t.dtype), cam_ray)
+    return {"rotation": R, "cam_t": out_t, "pivot": pv, "placed": placed, "rms": rms, "used": used,
+            "updated": updated | fitted, "fitted": fitted, "median": median, "valid": valid}

@@ -1221,6 +1221,9 @@ def _depth_args(ap: argparse.ArgumentParser) -> None:
                     help="after the records are written, move every hand along the ray of its origin onto the sensor depth map "
                          "DIR/<name>.png (16-bit) or DIR/<name>.npy, registered to the frame (evaluate_depth.refine_folder); needs --intrinsics")
     ap.add_argument('--depth-scale', type=float, default=0.001, metavar="S", help="with --depth-maps: metres per raw unit (default 0.001)")
+    ap.add_argument('--depth-fit', type=str, default="ray", choices=("ray", "rigid"),
+                    help="with --depth-maps: ray (default) moves a hand along the ray of its origin; rigid goes on with a point-to-plane "
+                         "fit of all six degrees of freedom about the wrist, folded into pose_global and cam_t (evaluate_depth --refine-mode)")
 
 
 def depth_args(ap: argparse.ArgumentParser, args) -> None:
@@ -1228,6 +1231,8 @@ def depth_args(ap: argparse.ArgumentParser, args) -> None:
     if not args.depth_maps:
         if args.depth_scale != 0.001:
             ap.error("--depth-scale needs --depth-maps DIR")
+        if args.depth_fit != "ray":
+            ap.error("--depth-fit needs --depth-maps DIR")
         return
     if not args.intrinsics:
         ap.error("--depth-maps needs --intrinsics: a depth residual under the default camera means nothing")
@@ -1239,7 +1244,7 @@ def refine_records(args, hamer, rank: int, world: int) -> None:
     """The ``--depth-maps`` step of the drivers: the records of ``--output`` are rewritten in place with depth-refined cam_t."""
     from . import evaluate_depth as ED
     r = ED.refine_folder(args.output, args.depth_maps, args.output, hamer, ED.load_cameras(args.intrinsics), unit=args.depth_scale,
-                         image_folder=args.input, rank=rank, world=world)
+                         image_folder=args.input, rank=rank, world=world, mode=args.depth_fit)
     print(f"{r['refined']} of {r['hands']} hands moved onto {args.depth_maps}" + (f" (rank {rank})" if world > 1 else ""))
 
 

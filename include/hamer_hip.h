@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32) and the additive fp32 HaMeR entry points (hm_gemm_f32, hm_vit_attention_f32; hm_hamer_forward, hm_patch_im2col and hm_cross_attention take HM_DTYPE_F32) and the additive ConvNeXt SAR entry points (hm_dwconv7_ln, hm_ln_patchify2, hm_stem4_im2col, hm_sar_saigb_ch) and the additive attention test hook (hm_attention_grid, HM_OPT_ATT_GRID) and the additive hand-metric entry point (hm_pose_eval); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
+#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32) and the additive fp32 HaMeR entry points (hm_gemm_f32, hm_vit_attention_f32; hm_hamer_forward, hm_patch_im2col and hm_cross_attention take HM_DTYPE_F32) and the additive ConvNeXt SAR entry points (hm_dwconv7_ln, hm_ln_patchify2, hm_stem4_im2col, hm_sar_saigb_ch) and the additive attention test hook (hm_attention_grid, HM_OPT_ATT_GRID) and the additive hand-metric entry point (hm_pose_eval) and the additive depth-fit entry points (hm_depth_fit_workspace_bytes, hm_depth_fit: the existing tests pin 402); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
 
 enum { HM_DTYPE_BF16 = 0, HM_DTYPE_F16 = 1,
        HM_DTYPE_F32 = 2 /* same value as HM_OUT_F32.  The fp32 YOLOv7 route (its section below) and the precise HaMeR route
@@ -981,6 +981,62 @@ int hm_depth_residuals(const float* pred_depth, const int32_t* pred_id, const ui
                        int n_meshes, int Q, double unit, int raw_lo, int raw_hi, double bin_m, int bins,
                        uint32_t* hist /* device [Q][bins] */, int64_t* counts /* device [Q][8] */, double* stats /* device [Q][4] */,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Depth fit: the rigid motion that brings the predicted hands' z-buffer onto a sensor depth map: csrc/depth_fit.hip.  Per
+ * query the 6 x 6 normal equations of a point-to-plane fit over the pixels its meshes cover, seven pixel counts, and their
+ * damped Cholesky solution (hamer/utils/depth_eval.py depth_fit and fit_rigid).
+ *
+ * pred_depth, pred_id, sensor, mask, labels, mesh_query, n_meshes, Q, unit, raw_lo and raw_hi are hm_depth_residuals' and mean
+ * the same.  cameras [N][4] f64 on the device: fx, fy, cx, cy of every frame; pivot [Q][3] f64 on the device: the point each
+ * query's rotation turns about, in the camera frame.  gate_m in (0, 0.25], edge_m > 0, reach_m in (0, 1], damping >= 0,
+ * lever_m > 0 (all finite), min_pixels >= 1.
+ *
+ * Rule per pixel e = (n H + v) W + u, all arithmetic fp64 and exactly as written, sums left to right: the unit is compiled with
+ * contraction off (#pragma clang fp contract(off)), so no product is fused into a sum.
+ *   1  id = pred_id[e]; the pixel is skipped unless 0 <= id < n_meshes and q = mesh_query[id] is in 0..Q-1; counts[q][0]
+ *      (covered) += 1
+ *   2  a mask test applies and the pixel fails it: counts[q][1] (off mask) += 1, stop
+ *   3  raw == 0, raw < raw_lo or raw > raw_hi: counts[q][2] (no measurement) += 1, stop
+ *   4  d = (double)pred_depth[e]; rz = (double)raw * unit - d; fabs(rz) <= gate_m is false (so for a NaN too): counts[q][3]
+ *      (gated) += 1, stop
+ *   5  the four neighbours (u-1, v), (u+1, v), (u, v-1), (u, v+1), depths dl, dr, du, dd: one lies outside the image (u < 1,
+ *      u + 1 >= W, v < 1 or v + 1 >= H: a neighbour never comes from the next row or frame), or its pred_id != id, or
+ *      fabs(dn - d) <= edge_m is false: counts[q][4] (no normal) += 1, stop
+ *   6  rx = ((double)u - cx) / fx, rxl and rxr the same of (double)(u - 1) and (double)(u + 1); ry = ((double)v - cy) / fy,
+ *      ryu and ryd the same of v - 1 and v + 1;
+ *      a = (dr * rxr - dl * rxl, dr * ry - dl * ry, dr - dl);  b = (dd * rx - du * rx, dd * ryd - du * ryu, dd - du);
+ *      n = a x b = (ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx);  l2 = nx * nx + ny * ny + nz * nz;
+ *      m = (d * rx - pivot[q][0], d * ry - pivot[q][1], d - pivot[q][2]);  mm = mx * mx + my * my + mz * mz;
+ *      J = (my * nz - mz * ny, mz * nx - mx * nz, mx * ny - my * nx, nx, ny, nz);  rho = (nx * rx + ny * ry + nz) * rz;
+ *      l2 > 0 && l2 <= DBL_MAX is false, or mm > reach_m * reach_m, or rho * rho > l2: counts[q][5] (rejected) += 1, stop
+ *   7  counts[q][6] (used) += 1 and sums[q] += 28 integers: llrint((J_i * J_j) / l2 * 2^30) for the 21 pairs i <= j row by row
+ *      ((0,0), (0,1) .. (0,5), (1,1) ..), llrint((J_i * rho) / l2 * 2^30) for i = 0..5, llrint((rho * rho) / l2 * 2^30).
+ * The normal is never normalised (the weight 1 / l2 does it) and there is no square root: one correctly rounded division per
+ * term, so the integers are the same wherever the rule is evaluated; |m| <= 1 and rho^2 <= l2 keep every term within 2^30, so
+ * an int64 sum cannot overflow below 2^31 pixels.  A query's sums and counts depend on its own pixels and the scalars alone: not
+ * on Q, N, the order of the meshes or the grid.
+ * The solve, per query from its integers: used = counts[q][6]; M symmetric with M_ij = (double)sums[k] * 2^-30 for the 21
+ * pairs, then M_ii = M_ii + (damping * (double)used) * (lever_m * lever_m) for i < 3 and M_ii + damping * (double)used for the
+ * rest; g_i = (double)sums[21 + i] * 2^-30.  Cholesky M = L L^T column by column, j = 0..5: s = M_jj, s = s - L_jk * L_jk for
+ * k = 0..j-1, L_jj = sqrt(s); then for i = j+1..5: s = M_ij, s = s - L_ik * L_jk for k = 0..j-1, L_ij = s / L_jj.  Forward
+ * y_i = (g_i - L_i0 y_0 - .. - L_i,i-1 y_i-1) / L_ii for i = 0..5; backward x_i = (y_i - L_i+1,i x_i+1 - .. - L_5i x_5) / L_ii
+ * for i = 5..0.  solution [Q][8] = omega (x_0..2), t (x_3..5), rms = sqrt(((double)sums[27] * 2^-30) / (double)used) (NaN when
+ * used == 0) and 1.0 for solved; a query with used < min_pixels or an s of a diagonal that is not > 0 is not solved: omega =
+ * t = 0 and the flag 0.  The fitted motion is p -> p + omega x (p - pivot) + t: it minimises, linearised, the squared distances
+ * of the moved surface points to the sensor's points on the same rays, measured along the surface normals.
+ * sums i64 [Q][28], counts i64 [Q][8] (entry 7 is written 0) and solution are all written on every call (callers do not clear
+ * them).  Asynchronous on `stream`: three kernels, ONE pass over the pixels for all queries, no host synchronisation, no
+ * allocation; the workspace (36 int64 per query) is where the sums are added up.  Q == 0 succeeds and launches nothing
+ * (mesh_query, cameras, pivot and the outputs may then be NULL).  HM_ERR_ARG before any device work: a null pointer, N, H or
+ * W < 1, N H W >= 2^31, Q or n_meshes < 0, unit not finite and > 0, raw_lo > raw_hi, a scalar outside its range above,
+ * workspace_bytes below the query, a 64-bit buffer not 8-byte aligned, a 32-bit input not 4-byte aligned. */
+size_t hm_depth_fit_workspace_bytes(int Q);   /* 0 for Q < 0; positive otherwise */
+int hm_depth_fit(const float* pred_depth, const int32_t* pred_id, const uint16_t* sensor, const uint8_t* mask /* or NULL */,
+                 const int32_t* labels /* device [Q] or NULL */, int N, int H, int W, const int32_t* mesh_query /* device */,
+                 int n_meshes, int Q, const double* cameras /* device [N][4] */, const double* pivot /* device [Q][3] */,
+                 double unit, int raw_lo, int raw_hi, double gate_m, double edge_m, double reach_m, double damping, double lever_m,
+                 int min_pixels, int64_t* sums /* device [Q][28] */, int64_t* counts /* device [Q][8] */,
+                 double* solution /* device [Q][8] */, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Detector evaluation (yolo/yolov7/test.py and utils/metrics.py): csrc/det_eval.hip.  The caller owns every buffer, the
  * calls are asynchronous on `stream`, nothing synchronises or allocates, argument errors return HM_ERR_ARG before any device
