@@ -8,46 +8,37 @@
 //
 // Three kernels on the stream, no host synchronisation, no allocation:
 //   init   writes all of hist and counts (zeros) and the per-query range of occupied bins in the workspace (empty).
-//   scan   ONE pass over the N * H * W pixels for all queries.  The pixels are walked as consecutive int32 of pred_id, not row
-//          by row: from the first 16-byte aligned address on, a thread reads four 16-byte vectors per round (all four loads are
-//          issued before any is looked at) and a workgroup of 256 threads does DR_ROUNDS rounds, 32768 pixels; the up to 3
-//          pixels before the first aligned address and behind the last whole vector are read one by one by the first
-//          workgroup.  A vector of four -1 -- nearly all of them -- costs that load: pred_depth, sensor and mask are read for
-//          covered pixels only.  Covered pixels are added up in LDS before anything goes to memory: a workgroup keeps
-//          DR_SLOTS queries (claimed first come, first served), per query the six counts and a window of DR_WINDOW bins placed
-//          around the first residual it meets.  A pixel whose query found no slot, or whose bin lies outside its slot's window,
-//          adds straight to memory instead; both ways add the same integers.  Within a wave the 64 pixels of a step are first
-//          grouped by query with ballots: the counts of a group are popcounts added by one lane, and so are the pixels of the
-//          first two bins met, so a flat patch of one hand is a handful of LDS atomics and not 64 queued on one address.  At
-//          the end the workgroup adds its non-zero LDS cells to memory, one atomic each, and the range of bins it touched.
+//   scan   ONE pass over the N * H * W pixels for all queries on depth_scan.h's walk, gate, query slots and groups of a wave
+//          (shared with depth_fit.hip).  Covered pixels are added up in LDS before anything goes to memory: a workgroup keeps
+//          DR_SLOTS queries, per query the six counts and a window of DR_WINDOW bins placed around the first residual it meets.
+//          A pixel whose query found no slot, or whose bin lies outside its slot's window, adds straight to memory instead; both
+//          ways add the same integers.  Within a group the counts are popcounts added by one lane, and so are the pixels of the
+//          first two bins met, so a flat patch of one hand is a handful of LDS atomics and not 64 queued on one address.  At the
+//          end the workgroup adds its non-zero LDS cells to memory, one atomic each, and the range of bins it touched.
 //   stats  one wave per query: the occupied range of its histogram goes to LDS and lane 0 walks it in ascending order.
 #include <math.h>
-#include <stdint.h>
 #include "common.h"
-#include "hamer_hip_internal.h"
+#include "depth_scan.h"
 
 #pragma clang fp contract(off)
 
 namespace {
+using namespace depth_scan;
 
-constexpr int DR_THREADS = 256, DR_UNROLL = 4, DR_ROUNDS = 8, DR_SLOTS = 4, DR_WINDOW = 512, DR_MAX_BINS = 4096;
-constexpr long long DR_VECS = (long long)DR_THREADS * DR_UNROLL * DR_ROUNDS;      // 16-byte vectors per workgroup: 32768 pixels
-enum { DR_COVERED = 0, DR_OFF_MASK = 1, DR_NO_MEASUREMENT = 2, DR_BELOW = 3, DR_ABOVE = 4, DR_IN_RANGE = 5 };
+constexpr int DR_SLOTS = 4, DR_WINDOW = 512, DR_MAX_BINS = 4096;
+enum { DR_BELOW = MEASURED, DR_ABOVE = 4, DR_IN_RANGE = 5 };  // the counts behind COVERED, OFF_MASK and NO_MEASUREMENT
 
-struct DepthParams {
-  const float* depth; const int32_t* id; const uint16_t* sensor; const uint8_t* mask; const int32_t* labels;
-  const int32_t* mesh_query;
-  long long total;                                        // N * H * W, below 2^31
-  int n_meshes, Q, bins, raw_lo, raw_hi;
-  double unit, bin_m;
+struct DepthParams : Maps {
+  int bins;
+  double bin_m;
   unsigned int* hist;                                     // [Q][bins]
   unsigned long long* counts;                             // [Q][8]
   double* stats;                                          // [Q][4]
   int* range;                                             // workspace [Q][2]: the least and the greatest occupied bin
 };
 
-__global__ __launch_bounds__(DR_THREADS) void depth_init_kernel(const DepthParams p) {
-  const long long i = (long long)blockIdx.x * DR_THREADS + threadIdx.x;
+__global__ __launch_bounds__(THREADS) void depth_init_kernel(const DepthParams p) {
+  const long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
   if (i < (long long)p.Q * p.bins) p.hist[i] = 0u;
   if (i < (long long)p.Q * 8) p.counts[i] = 0ull;
   if (i < (long long)p.Q * 2) p.range[i] = (i & 1) ? -1 : 0x7fffffff;
@@ -61,39 +52,15 @@ struct DepthLds {
   int lo[DR_SLOTS], hi[DR_SLOTS];                         // the range of non-zero window bins, found while they are added to memory
 };
 
-// the slot of query q in this workgroup, claiming a free one; -1 when all are taken by others
-__device__ __forceinline__ int find_slot(DepthLds& s, int q) {
-#pragma unroll
-  for (int i = 0; i < DR_SLOTS; ++i) {
-    int v = *(volatile int*)&s.query[i];
-    if (v == 0) {
-      const int old = atomicCAS(&s.query[i], 0, q + 1);
-      v = old == 0 ? q + 1 : old;
-    }
-    if (v == q + 1) return i;
-  }
-  return -1;
-}
-
-// what the rule makes of one pixel: its query (-1: the pixel is skipped), the count it ends in (DR_OFF_MASK .. DR_IN_RANGE) and its bin
+// what the rule makes of one pixel: its query (-1: the pixel is skipped), the count it ends in (OFF_MASK .. DR_IN_RANGE) and its bin
 struct Pixel { int q, where, k; };
 
 // one pixel by the rule of include/hamer_hip.h: e < total is its index, id its value of pred_id.  Nothing is added here.
 __device__ __forceinline__ Pixel classify(const DepthParams& p, long long e, int id) {
-  Pixel px = {-1, DR_OFF_MASK, 0};
-  if (id < 0 || id >= p.n_meshes) return px;
-  const int q = p.mesh_query[id];
-  if (q < 0 || q >= p.Q) return px;
-  px.q = q;
-  const int label = (p.mask && p.labels) ? p.labels[q] : -2;
-  if (label != -2) {
-    const int m = (int)p.mask[e];
-    if (!(label == -1 ? m != 0 : m == label)) return px;
-  }
-  const int raw = (int)p.sensor[e];
-  px.where = DR_NO_MEASUREMENT;
-  if (raw == 0 || raw < p.raw_lo || raw > p.raw_hi) return px;
-  const double r = (double)raw * p.unit - (double)p.depth[e];
+  const Gate g = gate(p, (size_t)e, id);
+  Pixel px = {g.q, g.stage, 0};
+  if (g.q < 0 || g.stage != MEASURED) return px;
+  const double r = (double)g.raw * p.unit - (double)p.depth[e];
   const double t = floor(r / p.bin_m);
   // |t| past 2^40 is outside every histogram; a NaN (of a NaN pred_depth, which the renderer never writes) counts as above
   px.where = DR_ABOVE;
@@ -125,24 +92,16 @@ __device__ __forceinline__ void add_hist(const DepthParams& p, DepthLds& s, int 
   if (k > *(volatile int*)(range + 1)) atomicMax(range + 1, k);
 }
 
-// Adds one pixel per lane.  The WHOLE wave calls this (lanes without a pixel pass q = -1).  Neighbouring pixels mostly belong
-// to one query and often to one bin, where one atomic per lane would queue 64 deep on one LDS address: so the lanes of a query
-// are counted with ballots and added by one lane, and the lanes that share the first two bins met are added together too; the
-// other bins get one atomic per lane.
+// Adds one pixel per lane; the WHOLE wave calls this (depth_scan.h, for_each_query).  Neighbouring pixels often share a bin too:
+// the lanes that share the first two bins met are counted with ballots and added by one lane, not queued 64 deep on one address.
 __device__ __forceinline__ void tally(const DepthParams& p, DepthLds& s, const Pixel px, int lane) {
-  unsigned long long todo = __ballot(px.q >= 0);
-  while (todo) {                                                          // wave-uniform: one turn per query among the 64 pixels
-    const int leader = __ffsll((long long)todo) - 1;
-    const int q = __shfl(px.q, leader);
-    const bool mine = px.q == q;
-    const unsigned long long group = __ballot(mine);
-    todo &= ~group;
+  for_each_query(px.q, [&](int leader, int q, bool mine, unsigned long long group) {
     int slot = -1, base = -1;
     const bool in_range = mine && px.where == DR_IN_RANGE;
     const unsigned long long placed = __ballot(in_range);
     const int k_first = placed ? __shfl(px.k, __ffsll((long long)placed) - 1) : 0;
     if (lane == leader) {
-      slot = find_slot(s, q);
+      slot = find_slot(s.query, q);
       if (slot >= 0) {
         base = *(volatile int*)&s.base[slot];
         if (base < 0 && placed) {                                         // the window goes around the first residual met
@@ -153,13 +112,13 @@ __device__ __forceinline__ void tally(const DepthParams& p, DepthLds& s, const P
           base = old < 0 ? b : old;
         }
       }
-      add_count(p, s, slot, q, DR_COVERED, __popcll(group));
+      add_count(p, s, slot, q, COVERED, __popcll(group));
       add_count(p, s, slot, q, DR_IN_RANGE, __popcll(placed));
     }
     slot = __shfl(slot, leader);
     base = __shfl(base, leader);
 #pragma unroll
-    for (int which = DR_OFF_MASK; which <= DR_ABOVE; ++which) {
+    for (int which = OFF_MASK; which <= DR_ABOVE; ++which) {
       const int n = __popcll(__ballot(mine && px.where == which));
       if (lane == leader) add_count(p, s, slot, q, which, n);
     }
@@ -176,52 +135,35 @@ __device__ __forceinline__ void tally(const DepthParams& p, DepthLds& s, const P
       left = left && !same;
     }
     if (left) add_hist(p, s, slot, base, q, px.k, 1);
-  }
+  });
 }
 
-__global__ __launch_bounds__(DR_THREADS) void depth_scan_kernel(const DepthParams p) {
+__global__ __launch_bounds__(THREADS) void depth_scan_kernel(const DepthParams p) {
   __shared__ DepthLds s;
   const int t = (int)threadIdx.x, lane = t & 63;
-  for (int i = t; i < DR_SLOTS * DR_WINDOW; i += DR_THREADS) (&s.hist[0][0])[i] = 0u;
+  for (int i = t; i < DR_SLOTS * DR_WINDOW; i += THREADS) (&s.hist[0][0])[i] = 0u;
   if (t < DR_SLOTS * 8) (&s.cnt[0][0])[t] = 0u;
   if (t < DR_SLOTS) { s.query[t] = 0; s.base[t] = -1; s.lo[t] = 0x7fffffff; s.hi[t] = -1; }
   __syncthreads();
 
-  long long head = (long long)((16u - (unsigned)((uintptr_t)p.id & 15u)) & 15u) >> 2;      // pixels before the first aligned address
-  if (head > p.total) head = p.total;
-  const long long nvec = (p.total - head) >> 2;
-  const long long tail0 = head + (nvec << 2);                                                // first pixel behind the last whole vector
-  const int4* __restrict__ vec = reinterpret_cast<const int4*>(p.id + head);
-  const long long v0 = (long long)blockIdx.x * DR_VECS;
-  for (int round = 0; round < DR_ROUNDS; ++round) {
-    int4 v[DR_UNROLL];
-    long long at[DR_UNROLL];
+  const Walk w = walk_of(p.id, p.total);
+  for (int round = 0; round < ROUNDS; ++round) {
+    int4 v[UNROLL];
+    const long long e0 = load_round(w, round, t, v);
 #pragma unroll
-    for (int u = 0; u < DR_UNROLL; ++u) {
-      at[u] = v0 + ((long long)round * DR_UNROLL + u) * DR_THREADS + t;
-      v[u] = make_int4(-1, -1, -1, -1);
-      if (at[u] < nvec) v[u] = vec[at[u]];                                                   // head + 4 at + 3 < tail0 <= total
-    }
-#pragma unroll
-    for (int u = 0; u < DR_UNROLL; ++u) {
+    for (int u = 0; u < UNROLL; ++u) {
       const bool covered = (v[u].x & v[u].y & v[u].z & v[u].w) != -1;
       if (!__ballot(covered)) continue;                                                      // the wave's 256 pixels are uncovered
-      const long long e = head + (at[u] << 2);                                               // (not used by a lane past nvec: its ids are -1)
+      const long long e = e0 + (long long)u * (4 * THREADS);
       tally(p, s, classify(p, e, v[u].x), lane); tally(p, s, classify(p, e + 1, v[u].y), lane);
       tally(p, s, classify(p, e + 2, v[u].z), lane); tally(p, s, classify(p, e + 3, v[u].w), lane);
     }
   }
-  if (blockIdx.x == 0 && t < 64) {
-    // the scalar head (lanes 0..3) and tail (lanes 4..7) of the first wave
-    long long e = -1;
-    if (t < 4) e = t < head ? (long long)t : -1;
-    else if (t < 8) e = tail0 + (t - 4) < p.total ? tail0 + (t - 4) : -1;
-    tally(p, s, classify(p, e < 0 ? 0 : e, e < 0 ? -1 : p.id[e]), lane);
-  }
+  scan_edges(w, p.id, t, [&](long long e, int id) { tally(p, s, classify(p, e, id), lane); });
   __syncthreads();
 
   // what the workgroup gathered goes to memory: one atomic per non-zero cell
-  for (int i = t; i < DR_SLOTS * DR_WINDOW; i += DR_THREADS) {
+  for (int i = t; i < DR_SLOTS * DR_WINDOW; i += THREADS) {
     const unsigned int n = (&s.hist[0][0])[i];
     if (n == 0u) continue;
     const int slot = i / DR_WINDOW, k = s.base[slot] + (i - slot * DR_WINDOW);
@@ -276,8 +218,6 @@ __global__ __launch_bounds__(64) void depth_stats_kernel(const DepthParams p) {
   out[3] = sqrt(s3 / d);
 }
 
-bool positive_finite(double v) { return v > 0.0 && v < INFINITY; }
-
 }  // namespace
 
 extern "C" size_t hm_depth_residuals_workspace_bytes(int Q, int bins) {
@@ -289,38 +229,28 @@ extern "C" int hm_depth_residuals(const float* pred_depth, const int32_t* pred_i
                                   const int32_t* labels, int N, int H, int W, const int32_t* mesh_query, int n_meshes, int Q,
                                   double unit, int raw_lo, int raw_hi, double bin_m, int bins, uint32_t* hist, int64_t* counts,
                                   double* stats, void* workspace, size_t workspace_bytes, void* stream_) {
-  if (N < 1 || H < 1 || W < 1) return hm_set_error(HM_ERR_ARG, "hm_depth_residuals: N, H and W must be positive");
-  if ((long long)N * H * W >= (1ll << 31)) return hm_set_error(HM_ERR_ARG, "hm_depth_residuals: N * H * W must be below 2^31");
-  if (Q < 0 || n_meshes < 0) return hm_set_error(HM_ERR_ARG, "hm_depth_residuals: Q and n_meshes must not be negative");
-  if (bins < 2 || bins > DR_MAX_BINS || (bins & 1)) return hm_set_error(HM_ERR_ARG, "hm_depth_residuals: bins must be even and in 2..4096");
-  if (!positive_finite(unit) || !positive_finite(bin_m)) return hm_set_error(HM_ERR_ARG, "hm_depth_residuals: unit and bin_m must be finite numbers > 0");
-  if (raw_lo > raw_hi) return hm_set_error(HM_ERR_ARG, "hm_depth_residuals: raw_lo must not exceed raw_hi");
-  if (!pred_depth || !pred_id || !sensor) return hm_set_error(HM_ERR_ARG, "hm_depth_residuals: null pred_depth, pred_id or sensor");
-  if (Q == 0) return HM_OK;                                              // nothing to score: no launch, nothing else is read
-  if ((n_meshes > 0 && !mesh_query) || !hist || !counts || !stats || !workspace)
-    return hm_set_error(HM_ERR_ARG, "hm_depth_residuals: null mesh_query, hist, counts, stats or workspace");
-  if (workspace_bytes < hm_depth_residuals_workspace_bytes(Q, bins))
-    return hm_set_error(HM_ERR_ARG, "hm_depth_residuals: workspace too small (hm_depth_residuals_workspace_bytes)");
-  if (((uintptr_t)counts & 7) || ((uintptr_t)stats & 7) || ((uintptr_t)hist & 3) || ((uintptr_t)workspace & 3))
-    return hm_set_error(HM_ERR_ARG, "hm_depth_residuals: counts and stats must be 8-byte aligned, hist and workspace 4-byte");
-  if (((uintptr_t)pred_depth & 3) || ((uintptr_t)pred_id & 3) || ((uintptr_t)sensor & 1) || ((uintptr_t)labels & 3) || ((uintptr_t)mesh_query & 3))
-    return hm_set_error(HM_ERR_ARG, "hm_depth_residuals: pred_depth, pred_id, labels and mesh_query must be 4-byte aligned, sensor 2-byte");
   DepthParams p;
   p.depth = pred_depth; p.id = pred_id; p.sensor = sensor; p.mask = mask; p.labels = labels; p.mesh_query = mesh_query;
-  p.total = (long long)N * H * W; p.n_meshes = n_meshes; p.Q = Q; p.bins = bins; p.raw_lo = raw_lo; p.raw_hi = raw_hi;
-  p.unit = unit; p.bin_m = bin_m;
+  p.n_meshes = n_meshes; p.Q = Q; p.bins = bins; p.raw_lo = raw_lo; p.raw_hi = raw_hi; p.unit = unit; p.bin_m = bin_m;
   p.hist = hist; p.counts = (unsigned long long*)counts; p.stats = stats; p.range = (int*)workspace;
+  const char* scalars = (bins < 2 || bins > DR_MAX_BINS || (bins & 1)) ? "bins must be even and in 2..4096"
+      : (!positive_finite(unit) || !positive_finite(bin_m))            ? "unit and bin_m must be finite numbers > 0" : nullptr;
+  const char* buffers = ((n_meshes > 0 && !mesh_query) || !hist || !counts || !stats || !workspace)
+          ? "null mesh_query, hist, counts, stats or workspace"
+      : workspace_bytes < hm_depth_residuals_workspace_bytes(Q, bins) ? "workspace too small (hm_depth_residuals_workspace_bytes)"
+      : (((uintptr_t)counts & 7) || ((uintptr_t)stats & 7) || ((uintptr_t)hist & 3) || ((uintptr_t)workspace & 3))
+          ? "counts and stats must be 8-byte aligned, hist and workspace 4-byte" : nullptr;
+  int rc = host_checks("hm_depth_residuals", p, N, H, W, scalars, nullptr, buffers);
+  if (rc != HM_OK || Q == 0) return rc;                                  // no query, nothing to score: no launch
   const long long cells = (long long)Q * bins > (long long)Q * 8 ? (long long)Q * bins : (long long)Q * 8;
-  const long long init_blocks = (cells + DR_THREADS - 1) / DR_THREADS;
+  const long long init_blocks = (cells + THREADS - 1) / THREADS;
   if (init_blocks > 0x7fffffffll) return hm_set_error(HM_ERR_ARG, "hm_depth_residuals: Q * bins too large for one call");
-  const long long vecs = p.total >> 2;                                   // an upper bound of the whole vectors
-  const long long scan_blocks = vecs > 0 ? (vecs + DR_VECS - 1) / DR_VECS : 1;
   hipStream_t s = (hipStream_t)stream_;
   HmProfScope prof(HM_K_OTHER, 8, Q, H, W, s);
-  hipLaunchKernelGGL(depth_init_kernel, dim3((unsigned)init_blocks), dim3(DR_THREADS), 0, s, p);
-  int rc = hm_check_launch("hm_depth_residuals (init)");
+  hipLaunchKernelGGL(depth_init_kernel, dim3((unsigned)init_blocks), dim3(THREADS), 0, s, p);
+  rc = hm_check_launch("hm_depth_residuals (init)");
   if (rc != HM_OK) return rc;
-  hipLaunchKernelGGL(depth_scan_kernel, dim3((unsigned)scan_blocks), dim3(DR_THREADS), 0, s, p);
+  hipLaunchKernelGGL(depth_scan_kernel, dim3(scan_blocks(p.total)), dim3(THREADS), 0, s, p);
   rc = hm_check_launch("hm_depth_residuals (scan)");
   if (rc != HM_OK) return rc;
   hipLaunchKernelGGL(depth_stats_kernel, dim3((unsigned)Q), dim3(64), 0, s, p);

@@ -9,50 +9,40 @@
 //
 // Three kernels on the stream, no host synchronisation, no allocation:
 //   init   zeroes the workspace: per query one row of 36 int64, the 28 sums followed by the 8 counts.
-//   scan   ONE pass over the N * H * W pixels for all queries, walked as depth_eval.hip walks them: from the first 16-byte
-//          aligned address of pred_id on, a thread reads four 16-byte vectors per round (all four loads are issued before any is
-//          looked at) and a workgroup of 256 threads does DF_ROUNDS rounds, 32768 pixels; the up to 3 pixels before the first
-//          aligned address and behind the last whole vector are read one by one by the first workgroup.  A vector of four -1
-//          costs that load; everything else -- the sensor, the mask, the four neighbours, the camera, the pivot -- is read for
-//          covered pixels only, and the neighbours only for pixels that passed the gate.  Within a wave the 64 pixels of a step
-//          are grouped by query with ballots (as depth_eval.hip's tally() does): the counts of a group are popcounts, and each of
-//          the 28 terms is added across the wave with 64-bit shuffles (lanes outside the group add 0; integer adds commute, so
-//          the tree is exact) and then ONCE, by the group's first lane, to the query's row in LDS with a 64-bit LDS add.  A
-//          workgroup keeps DF_SLOTS queries (claimed first come, first served); a group whose query found no slot adds its 28
-//          wave totals straight to the workspace instead -- the same integers.  At the end the workgroup adds its non-zero
-//          LDS cells to the workspace, one 64-bit atomic each, 36 consecutive cells per slot.
+//   scan   ONE pass over the N * H * W pixels for all queries on depth_scan.h's walk, gate, query slots and groups of a wave
+//          (shared with depth_eval.hip); the four neighbours, the camera and the pivot are read only for pixels whose residual is
+//          within gate_m.  Within a group the counts are popcounts, and each of the 28 terms is added across the wave with 64-bit
+//          shuffles (lanes outside the group add 0; integer adds commute, so the tree is exact) and then ONCE, by the group's
+//          first lane, to the query's row in LDS with a 64-bit LDS add.  A workgroup keeps DF_SLOTS queries; a group whose query
+//          found no slot adds its 28 wave totals straight to the workspace instead -- the same integers.  At the end the workgroup
+//          adds its non-zero LDS cells to the workspace, one 64-bit atomic each, 36 consecutive cells per slot.
 //   solve  one thread per query: copies its row to sums and counts, builds M, factorises and solves in the header's order.
 #include <float.h>
 #include <math.h>
-#include <stdint.h>
 #include "common.h"
-#include "hamer_hip_internal.h"
+#include "depth_scan.h"
 
 #pragma clang fp contract(off)
 
 namespace {
+using namespace depth_scan;
 
-constexpr int DF_THREADS = 256, DF_UNROLL = 4, DF_ROUNDS = 8, DF_SLOTS = 4, DF_SUMS = 28, DF_CELLS = 36;
-constexpr long long DF_VECS = (long long)DF_THREADS * DF_UNROLL * DF_ROUNDS;      // 16-byte vectors per workgroup: 32768 pixels
+constexpr int DF_SLOTS = 4, DF_SUMS = 28, DF_CELLS = 36;
 constexpr double DF_SCALE = 1073741824.0, DF_INV_SCALE = 1.0 / 1073741824.0;     // 2^30 and 2^-30: exact
-enum { DF_COVERED = 0, DF_OFF_MASK = 1, DF_NO_MEASUREMENT = 2, DF_GATED = 3, DF_NO_NORMAL = 4, DF_REJECTED = 5, DF_USED = 6 };
+enum { DF_GATED = MEASURED, DF_NO_NORMAL = 4, DF_REJECTED = 5, DF_USED = 6 };     // the counts behind COVERED, OFF_MASK and NO_MEASUREMENT
 
-struct FitParams {
-  const float* depth; const int32_t* id; const uint16_t* sensor; const uint8_t* mask; const int32_t* labels;
-  const int32_t* mesh_query;
-  const double* cameras;                                  // [N][4]: fx, fy, cx, cy
-  const double* pivot;                                    // [Q][3]
-  unsigned int total, HW;                                 // N * H * W (below 2^31) and H * W
-  int H, W, n_meshes, Q, raw_lo, raw_hi, min_pixels;
-  double unit, gate_m, edge_m, reach2, damping, lever2;   // reach2 = reach_m * reach_m, lever2 = lever_m * lever_m
+struct FitParams : Maps {
+  const double* cameras; const double* pivot;             // [N][4]: fx, fy, cx, cy, and [Q][3]
+  unsigned int HW; int H, W, min_pixels;                  // HW = H * W
+  double gate_m, edge_m, reach2, damping, lever2;         // reach2 = reach_m * reach_m, lever2 = lever_m * lever_m
   unsigned long long* acc;                                // workspace [Q][36]
   long long* sums;                                        // [Q][28]
   long long* counts;                                      // [Q][8]
   double* solution;                                       // [Q][8]
 };
 
-__global__ __launch_bounds__(DF_THREADS) void fit_init_kernel(const FitParams p) {
-  const long long i = (long long)blockIdx.x * DF_THREADS + threadIdx.x;
+__global__ __launch_bounds__(THREADS) void fit_init_kernel(const FitParams p) {
+  const long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
   if (i < (long long)p.Q * DF_CELLS) p.acc[i] = 0ull;
 }
 
@@ -61,46 +51,21 @@ struct FitLds {
   int query[DF_SLOTS];                                    // q + 1 of the slot's query, 0 while it is free
 };
 
-// the slot of query q in this workgroup, claiming a free one; -1 when all are taken by others
-__device__ __forceinline__ int find_slot(FitLds& s, int q) {
-#pragma unroll
-  for (int i = 0; i < DF_SLOTS; ++i) {
-    int v = *(volatile int*)&s.query[i];
-    if (v == 0) {
-      const int old = atomicCAS(&s.query[i], 0, q + 1);
-      v = old == 0 ? q + 1 : old;
-    }
-    if (v == q + 1) return i;
-  }
-  return -1;
-}
-
-// what the rule makes of one pixel: its query (-1: the pixel is skipped), the count it ends in (DF_OFF_MASK .. DF_USED) and,
+// what the rule makes of one pixel: its query (-1: the pixel is skipped), the count it ends in (OFF_MASK .. DF_USED) and,
 // for a used pixel, J, rho and l2
 struct FitPixel { int q, where; double J[6], rho, l2; };
 
 // one pixel by the rule of include/hamer_hip.h: e < total is its index, id its value of pred_id.  Nothing is added here.
 __device__ __forceinline__ FitPixel classify(const FitParams& p, unsigned int e, int id) {
+  const Gate g = gate(p, e, id);
   FitPixel px;
-  px.q = -1; px.where = DF_OFF_MASK; px.rho = 0.0; px.l2 = 1.0;
+  px.q = g.q; px.where = g.stage; px.rho = 0.0; px.l2 = 1.0;
 #pragma unroll
   for (int i = 0; i < 6; ++i) px.J[i] = 0.0;
-  if (id < 0 || id >= p.n_meshes) return px;
-  const int q = p.mesh_query[id];
-  if (q < 0 || q >= p.Q) return px;
-  px.q = q;
-  const int label = (p.mask && p.labels) ? p.labels[q] : -2;
-  if (label != -2) {
-    const int m = (int)p.mask[e];
-    if (!(label == -1 ? m != 0 : m == label)) return px;
-  }
-  const int raw = (int)p.sensor[e];
-  px.where = DF_NO_MEASUREMENT;
-  if (raw == 0 || raw < p.raw_lo || raw > p.raw_hi) return px;
+  if (g.q < 0 || g.stage != MEASURED) return px;
   const double d = (double)p.depth[e];
-  const double rz = (double)raw * p.unit - d;
-  px.where = DF_GATED;
-  if (!(fabs(rz) <= p.gate_m)) return px;                                     // a NaN is gated
+  const double rz = (double)g.raw * p.unit - d;
+  if (!(fabs(rz) <= p.gate_m)) return px;                                     // DF_GATED; a NaN is gated
   px.where = DF_NO_NORMAL;
   const unsigned int n = e / p.HW, rem = e - n * p.HW;
   const int v = (int)(rem / (unsigned int)p.W), u = (int)(rem - (unsigned int)v * (unsigned int)p.W);
@@ -116,7 +81,7 @@ __device__ __forceinline__ FitPixel classify(const FitParams& p, unsigned int e,
   const double bx = dd * rx - du * rx, by = dd * ryd - du * ryu, bz = dd - du;
   const double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
   const double l2 = nx * nx + ny * ny + nz * nz;
-  const double* pv = p.pivot + (size_t)q * 3;
+  const double* pv = p.pivot + (size_t)g.q * 3;
   const double mx = d * rx - pv[0], my = d * ry - pv[1], mz = d - pv[2];
   const double rho = (nx * rx + ny * ry + nz) * rz;
   const double mm = mx * mx + my * my + mz * mz;
@@ -131,7 +96,9 @@ __device__ __forceinline__ FitPixel classify(const FitParams& p, unsigned int e,
 
 __device__ __forceinline__ void add_cell(const FitParams& p, FitLds& s, int slot, int q, int cell, long long n) {
   if (n == 0) return;
-  if (slot >= 0) atomicAdd(&s.acc[slot][cell], (unsigned long long)n);
+  // workgroup scope: all an LDS cell needs, and it keeps hipcc from merging both adds into ONE flat atomic on a selected address
+  // (whenever tally or for_each_query changes, count flat_atomic in fit_scan_kernel's ISA again: 0, with 70 ds_add_u64)
+  if (slot >= 0) __hip_atomic_fetch_add(&s.acc[slot][cell], (unsigned long long)n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   else atomicAdd(p.acc + (size_t)q * DF_CELLS + cell, (unsigned long long)n);
 }
 
@@ -141,26 +108,20 @@ __device__ __forceinline__ long long wave_sum(long long v) {
   return v;
 }
 
-// Adds one pixel per lane.  The WHOLE wave calls this (lanes without a pixel pass q = -1).
+// Adds one pixel per lane; the WHOLE wave calls this (depth_scan.h, for_each_query).
 __device__ __forceinline__ void tally(const FitParams& p, FitLds& s, const FitPixel& px, int lane) {
-  unsigned long long todo = __ballot(px.q >= 0);
-  while (todo) {                                                          // wave-uniform: one turn per query among the 64 pixels
-    const int leader = __ffsll((long long)todo) - 1;
-    const int q = __shfl(px.q, leader);
-    const bool mine = px.q == q;
-    const unsigned long long group = __ballot(mine);
-    todo &= ~group;
+  for_each_query(px.q, [&](int leader, int q, bool mine, unsigned long long group) {
     int slot = -1;
-    if (lane == leader) slot = find_slot(s, q);
+    if (lane == leader) slot = find_slot(s.query, q);
     slot = __shfl(slot, leader);
-    if (lane == leader) add_cell(p, s, slot, q, DF_SUMS + DF_COVERED, __popcll(group));
+    if (lane == leader) add_cell(p, s, slot, q, DF_SUMS + COVERED, __popcll(group));
 #pragma unroll
-    for (int which = DF_OFF_MASK; which <= DF_USED; ++which) {
+    for (int which = OFF_MASK; which <= DF_USED; ++which) {
       const int n = __popcll(__ballot(mine && px.where == which));
       if (lane == leader) add_cell(p, s, slot, q, DF_SUMS + which, n);
     }
     const bool use = mine && px.where == DF_USED;
-    if (!__ballot(use)) continue;
+    if (!__ballot(use)) return;
     int cell = 0;
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -178,60 +139,41 @@ __device__ __forceinline__ void tally(const FitParams& p, FitLds& s, const FitPi
     }
     const long long t = wave_sum(use ? llrint((px.rho * px.rho) / px.l2 * DF_SCALE) : 0ll);
     if (lane == leader) add_cell(p, s, slot, q, 27, t);
-  }
+  });
 }
 
-__global__ __launch_bounds__(DF_THREADS) void fit_scan_kernel(const FitParams p) {
+__global__ __launch_bounds__(THREADS) void fit_scan_kernel(const FitParams p) {
   __shared__ FitLds s;
   const int t = (int)threadIdx.x, lane = t & 63;
   if (t < DF_SLOTS * DF_CELLS) (&s.acc[0][0])[t] = 0ull;
   if (t < DF_SLOTS) s.query[t] = 0;
   __syncthreads();
 
-  long long head = (long long)((16u - (unsigned)((uintptr_t)p.id & 15u)) & 15u) >> 2;      // pixels before the first aligned address
-  if (head > (long long)p.total) head = p.total;
-  const long long nvec = ((long long)p.total - head) >> 2;
-  const long long tail0 = head + (nvec << 2);                                                // first pixel behind the last whole vector
-  const int4* __restrict__ vec = reinterpret_cast<const int4*>(p.id + head);
-  const long long v0 = (long long)blockIdx.x * DF_VECS;
-  for (int round = 0; round < DF_ROUNDS; ++round) {
-    int4 v[DF_UNROLL];
-    const long long at0 = v0 + (long long)round * DF_UNROLL * DF_THREADS + t;
+  const Walk w = walk_of(p.id, p.total);
+  for (int round = 0; round < ROUNDS; ++round) {
+    int4 v[UNROLL];
+    const long long e0 = load_round(w, round, t, v);
     unsigned int live = 0;
 #pragma unroll
-    for (int u = 0; u < DF_UNROLL; ++u) {
-      const long long at = at0 + (long long)u * DF_THREADS;
-      v[u] = make_int4(-1, -1, -1, -1);
-      if (at < nvec) v[u] = vec[at];                                                         // head + 4 at + 3 < tail0 <= total
-    }
-#pragma unroll
-    for (int u = 0; u < DF_UNROLL; ++u)
+    for (int u = 0; u < UNROLL; ++u)
       if (__ballot((v[u].x & v[u].y & v[u].z & v[u].w) != -1)) live |= 1u << u;              // wave-uniform
     if (!live) continue;                                                                     // the wave's 1024 pixels are uncovered
     // one copy of the per-pixel code for the 16 pixels of a lane: the vectors and their components are shifted through
     // `cur` with moves, so that nothing is indexed by k
     int4 cur = v[0];
 #pragma clang loop unroll(disable)
-    for (int k = 0; k < 4 * DF_UNROLL; ++k) {
+    for (int k = 0; k < 4 * UNROLL; ++k) {
       const int u = k >> 2, c = k & 3;
       if (c == 0 && k != 0) { cur = v[1]; v[1] = v[2]; v[2] = v[3]; }
       const int id = cur.x;
       cur.x = cur.y; cur.y = cur.z; cur.z = cur.w;
       if (!((live >> u) & 1u)) continue;
       if (!__ballot(id >= 0)) continue;
-      const long long e = head + ((at0 + (long long)u * DF_THREADS) << 2) + c;               // (not used by a lane past nvec: its ids are -1)
-      const FitPixel px = classify(p, (unsigned int)e, id);
+      const FitPixel px = classify(p, (unsigned int)(e0 + (long long)u * (4 * THREADS) + c), id);
       tally(p, s, px, lane);
     }
   }
-  if (blockIdx.x == 0 && t < 64) {
-    // the scalar head (lanes 0..3) and tail (lanes 4..7) of the first wave
-    long long e = -1;
-    if (t < 4) e = t < head ? (long long)t : -1;
-    else if (t < 8) e = tail0 + (t - 4) < (long long)p.total ? tail0 + (t - 4) : -1;
-    const FitPixel px = classify(p, e < 0 ? 0u : (unsigned int)e, e < 0 ? -1 : p.id[e]);
-    tally(p, s, px, lane);
-  }
+  scan_edges(w, p.id, t, [&](long long e, int id) { tally(p, s, classify(p, (unsigned int)e, id), lane); });
   __syncthreads();
 
   // what the workgroup gathered goes to memory: one atomic per non-zero cell, a slot's 36 cells side by side
@@ -312,8 +254,6 @@ __global__ __launch_bounds__(64) void fit_solve_kernel(const FitParams p) {
   out[7] = ok ? 1.0 : 0.0;
 }
 
-bool positive_finite(double v) { return v > 0.0 && v < INFINITY; }
-
 }  // namespace
 
 extern "C" size_t hm_depth_fit_workspace_bytes(int Q) {
@@ -326,44 +266,35 @@ extern "C" int hm_depth_fit(const float* pred_depth, const int32_t* pred_id, con
                             const double* cameras, const double* pivot, double unit, int raw_lo, int raw_hi, double gate_m,
                             double edge_m, double reach_m, double damping, double lever_m, int min_pixels, int64_t* sums,
                             int64_t* counts, double* solution, void* workspace, size_t workspace_bytes, void* stream_) {
-  if (N < 1 || H < 1 || W < 1) return hm_set_error(HM_ERR_ARG, "hm_depth_fit: N, H and W must be positive");
-  if ((long long)N * H * W >= (1ll << 31)) return hm_set_error(HM_ERR_ARG, "hm_depth_fit: N * H * W must be below 2^31");
-  if (Q < 0 || n_meshes < 0) return hm_set_error(HM_ERR_ARG, "hm_depth_fit: Q and n_meshes must not be negative");
-  if (!positive_finite(unit)) return hm_set_error(HM_ERR_ARG, "hm_depth_fit: unit must be a finite number > 0");
-  if (raw_lo > raw_hi) return hm_set_error(HM_ERR_ARG, "hm_depth_fit: raw_lo must not exceed raw_hi");
-  if (!(gate_m > 0.0 && gate_m <= 0.25)) return hm_set_error(HM_ERR_ARG, "hm_depth_fit: gate_m must be in (0, 0.25]");
-  if (!positive_finite(edge_m)) return hm_set_error(HM_ERR_ARG, "hm_depth_fit: edge_m must be a finite number > 0");
-  if (!(reach_m > 0.0 && reach_m <= 1.0)) return hm_set_error(HM_ERR_ARG, "hm_depth_fit: reach_m must be in (0, 1]");
-  if (!(damping >= 0.0 && damping < INFINITY)) return hm_set_error(HM_ERR_ARG, "hm_depth_fit: damping must be a finite number >= 0");
-  if (!positive_finite(lever_m)) return hm_set_error(HM_ERR_ARG, "hm_depth_fit: lever_m must be a finite number > 0");
-  if (min_pixels < 1) return hm_set_error(HM_ERR_ARG, "hm_depth_fit: min_pixels must be at least 1");
-  if (!pred_depth || !pred_id || !sensor) return hm_set_error(HM_ERR_ARG, "hm_depth_fit: null pred_depth, pred_id or sensor");
-  if (Q == 0) return HM_OK;                                              // nothing to fit: no launch, nothing else is read
-  if ((n_meshes > 0 && !mesh_query) || !cameras || !pivot || !sums || !counts || !solution || !workspace)
-    return hm_set_error(HM_ERR_ARG, "hm_depth_fit: null mesh_query, cameras, pivot, sums, counts, solution or workspace");
-  if (workspace_bytes < hm_depth_fit_workspace_bytes(Q))
-    return hm_set_error(HM_ERR_ARG, "hm_depth_fit: workspace too small (hm_depth_fit_workspace_bytes)");
-  if (((uintptr_t)sums & 7) || ((uintptr_t)counts & 7) || ((uintptr_t)solution & 7) || ((uintptr_t)workspace & 7) ||
-      ((uintptr_t)cameras & 7) || ((uintptr_t)pivot & 7))
-    return hm_set_error(HM_ERR_ARG, "hm_depth_fit: sums, counts, solution, workspace, cameras and pivot must be 8-byte aligned");
-  if (((uintptr_t)pred_depth & 3) || ((uintptr_t)pred_id & 3) || ((uintptr_t)sensor & 1) || ((uintptr_t)labels & 3) || ((uintptr_t)mesh_query & 3))
-    return hm_set_error(HM_ERR_ARG, "hm_depth_fit: pred_depth, pred_id, labels and mesh_query must be 4-byte aligned, sensor 2-byte");
   FitParams p;
   p.depth = pred_depth; p.id = pred_id; p.sensor = sensor; p.mask = mask; p.labels = labels; p.mesh_query = mesh_query;
   p.cameras = cameras; p.pivot = pivot;
-  p.total = (unsigned int)((long long)N * H * W); p.HW = (unsigned int)((long long)H * W); p.H = H; p.W = W;
+  p.HW = (unsigned int)((long long)H * W); p.H = H; p.W = W;
   p.n_meshes = n_meshes; p.Q = Q; p.raw_lo = raw_lo; p.raw_hi = raw_hi; p.min_pixels = min_pixels;
   p.unit = unit; p.gate_m = gate_m; p.edge_m = edge_m; p.reach2 = reach_m * reach_m; p.damping = damping; p.lever2 = lever_m * lever_m;
   p.acc = (unsigned long long*)workspace; p.sums = (long long*)sums; p.counts = (long long*)counts; p.solution = solution;
-  const long long init_blocks = ((long long)Q * DF_CELLS + DF_THREADS - 1) / DF_THREADS;
-  const long long vecs = (long long)p.total >> 2;                        // an upper bound of the whole vectors
-  const long long scan_blocks = vecs > 0 ? (vecs + DF_VECS - 1) / DF_VECS : 1;
+  const char* unit_text = !positive_finite(unit) ? "unit must be a finite number > 0" : nullptr;
+  const char* scalars = !(gate_m > 0.0 && gate_m <= 0.25)   ? "gate_m must be in (0, 0.25]"
+      : !positive_finite(edge_m)                            ? "edge_m must be a finite number > 0"
+      : !(reach_m > 0.0 && reach_m <= 1.0)                  ? "reach_m must be in (0, 1]"
+      : !(damping >= 0.0 && damping < INFINITY)             ? "damping must be a finite number >= 0"
+      : !positive_finite(lever_m)                           ? "lever_m must be a finite number > 0"
+      : min_pixels < 1                                      ? "min_pixels must be at least 1" : nullptr;
+  const char* buffers = ((n_meshes > 0 && !mesh_query) || !cameras || !pivot || !sums || !counts || !solution || !workspace)
+          ? "null mesh_query, cameras, pivot, sums, counts, solution or workspace"
+      : workspace_bytes < hm_depth_fit_workspace_bytes(Q) ? "workspace too small (hm_depth_fit_workspace_bytes)"
+      : (((uintptr_t)sums & 7) || ((uintptr_t)counts & 7) || ((uintptr_t)solution & 7) || ((uintptr_t)workspace & 7) ||
+         ((uintptr_t)cameras & 7) || ((uintptr_t)pivot & 7))
+          ? "sums, counts, solution, workspace, cameras and pivot must be 8-byte aligned" : nullptr;
+  int rc = host_checks("hm_depth_fit", p, N, H, W, unit_text, scalars, buffers);
+  if (rc != HM_OK || Q == 0) return rc;                                  // no query, nothing to fit: no launch
+  const long long init_blocks = ((long long)Q * DF_CELLS + THREADS - 1) / THREADS;
   hipStream_t s = (hipStream_t)stream_;
   HmProfScope prof(HM_K_OTHER, 9, Q, H, W, s);
-  hipLaunchKernelGGL(fit_init_kernel, dim3((unsigned)init_blocks), dim3(DF_THREADS), 0, s, p);
-  int rc = hm_check_launch("hm_depth_fit (init)");
+  hipLaunchKernelGGL(fit_init_kernel, dim3((unsigned)init_blocks), dim3(THREADS), 0, s, p);
+  rc = hm_check_launch("hm_depth_fit (init)");
   if (rc != HM_OK) return rc;
-  hipLaunchKernelGGL(fit_scan_kernel, dim3((unsigned)scan_blocks), dim3(DF_THREADS), 0, s, p);
+  hipLaunchKernelGGL(fit_scan_kernel, dim3(scan_blocks(p.total)), dim3(THREADS), 0, s, p);
   rc = hm_check_launch("hm_depth_fit (scan)");
   if (rc != HM_OK) return rc;
   hipLaunchKernelGGL(fit_solve_kernel, dim3((unsigned)((Q + 63) / 64)), dim3(64), 0, s, p);

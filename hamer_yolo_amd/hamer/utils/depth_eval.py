@@ -27,19 +27,62 @@ def release_workspaces() -> None:
     _ws.clear()
 
 
-def _int32_on(values, dev, n: Optional[int], what: str) -> torch.Tensor:
+def _int32_on(who: str, values, dev, n: Optional[int], what: str) -> torch.Tensor:
     if torch.is_tensor(values):
         if not (values.device == dev and values.dtype == torch.int32 and values.dim() == 1 and values.is_contiguous()):
-            raise ValueError(f"depth_residuals: a {what} tensor must be contiguous int32 (n,) on {dev}")
+            raise ValueError(f"{who}: a {what} tensor must be contiguous int32 (n,) on {dev}")
         t = values
     else:
         a = np.asarray(values, np.int64).reshape(-1)
         if a.size and (np.abs(a) >= 2 ** 31).any():
-            raise ValueError(f"depth_residuals: a {what} value does not fit int32")
+            raise ValueError(f"{who}: a {what} value does not fit int32")
         t = torch.from_numpy(np.ascontiguousarray(a.astype(np.int32))).to(dev)
     if n is not None and int(t.shape[0]) != n:
-        raise ValueError(f"depth_residuals: {what} has {int(t.shape[0])} entries, expected {n}")
+        raise ValueError(f"{who}: {what} has {int(t.shape[0])} entries, expected {n}")
     return t
+
+
+def _check_maps(who: str, pred_depth, pred_id, sensor, mask, labels, Q: int):
+    """What ``depth_residuals`` and ``depth_fit`` (``who``) ask of their maps and of Q; returns the maps' device and (N, H, W)."""
+    if not all(torch.is_tensor(t) for t in (pred_depth, pred_id, sensor)):
+        raise ValueError(f"{who}: pred_depth, pred_id and sensor must be tensors")
+    dev = pred_id.device
+    if not (pred_id.is_cuda and pred_depth.device == dev and sensor.device == dev):
+        raise ValueError(f"{who}: pred_depth, pred_id and sensor must be on one GPU; there is no CPU path")
+    if pred_depth.dtype != torch.float32 or pred_id.dtype != torch.int32 or sensor.dtype not in (torch.uint16, torch.int16):
+        raise ValueError(f"{who}: expected float32, int32 and uint16, got {pred_depth.dtype}, {pred_id.dtype}, {sensor.dtype}")
+    shape = tuple(pred_id.shape)
+    if pred_id.dim() != 3 or 0 in shape or tuple(pred_depth.shape) != shape or tuple(sensor.shape) != shape:
+        raise ValueError(f"{who}: pred_depth {tuple(pred_depth.shape)} / pred_id {shape} / sensor {tuple(sensor.shape)}: "
+                         "expected three (N, H, W)")
+    if not (pred_depth.is_contiguous() and pred_id.is_contiguous() and sensor.is_contiguous()):
+        raise ValueError(f"{who}: pred_depth, pred_id and sensor must be contiguous")
+    if (mask is None) != (labels is None):
+        raise ValueError(f"{who}: mask and labels are given both or neither")
+    if mask is not None and not (torch.is_tensor(mask) and mask.device == dev and mask.dtype == torch.uint8
+                                 and tuple(mask.shape) == shape and mask.is_contiguous()):
+        raise ValueError(f"{who}: mask must be a contiguous uint8 tensor of shape {shape} on {dev}")
+    if Q < 0:
+        raise ValueError(f"{who}: Q must not be negative")
+    return dev, shape
+
+
+def _labels_on(who: str, labels, dev, Q: int) -> Optional[torch.Tensor]:
+    if labels is None:
+        return None
+    if not torch.is_tensor(labels) and any(not -2 <= int(v) <= 255 for v in np.asarray(labels).reshape(-1)):
+        raise ValueError(f"{who}: a label must be -2, -1 or 0..255")
+    return _int32_on(who, labels, dev, Q, "labels")
+
+
+def _workspace(cache: Dict[tuple, torch.Tensor], dev, stream, need: int) -> torch.Tensor:
+    """The cached workspace of this device and stream, grown on demand."""
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), stream)
+    ws = cache.get(key)
+    if ws is None or ws.numel() * 8 < need:
+        cache.pop(key, None)
+        ws = cache[key] = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    return ws
 
 
 def depth_residuals(pred_depth: torch.Tensor, pred_id: torch.Tensor, sensor: torch.Tensor, mesh_query, Q: int, *,
@@ -53,27 +96,8 @@ def depth_residuals(pred_depth: torch.Tensor, pred_id: torch.Tensor, sensor: tor
     Returns ``{'hist': (Q, bins) int32 (the kernel's uint32; a bin holds at most N H W < 2^31), 'counts': (Q, 8) int64
     (COUNT_NAMES), 'stats': (Q, 4) float64 (lower median, mean, mean absolute, rms; NaN where undefined)}`` on the device.  Enqueued on the current stream without
     synchronising; the workspace is cached per device and stream (``release_workspaces``)."""
-    if not all(torch.is_tensor(t) for t in (pred_depth, pred_id, sensor)):
-        raise ValueError("depth_residuals: pred_depth, pred_id and sensor must be tensors")
-    dev = pred_id.device
-    if not (pred_id.is_cuda and pred_depth.device == dev and sensor.device == dev):
-        raise ValueError("depth_residuals: pred_depth, pred_id and sensor must be on one GPU; there is no CPU path")
-    if pred_depth.dtype != torch.float32 or pred_id.dtype != torch.int32 or sensor.dtype not in (torch.uint16, torch.int16):
-        raise ValueError(f"depth_residuals: expected float32, int32 and uint16, got {pred_depth.dtype}, {pred_id.dtype}, {sensor.dtype}")
-    shape = tuple(pred_id.shape)
-    if pred_id.dim() != 3 or 0 in shape or tuple(pred_depth.shape) != shape or tuple(sensor.shape) != shape:
-        raise ValueError(f"depth_residuals: pred_depth {tuple(pred_depth.shape)} / pred_id {shape} / sensor {tuple(sensor.shape)}: "
-                         "expected three (N, H, W)")
-    if not (pred_depth.is_contiguous() and pred_id.is_contiguous() and sensor.is_contiguous()):
-        raise ValueError("depth_residuals: pred_depth, pred_id and sensor must be contiguous")
-    if (mask is None) != (labels is None):
-        raise ValueError("depth_residuals: mask and labels are given both or neither")
-    if mask is not None and not (torch.is_tensor(mask) and mask.device == dev and mask.dtype == torch.uint8
-                                 and tuple(mask.shape) == shape and mask.is_contiguous()):
-        raise ValueError(f"depth_residuals: mask must be a contiguous uint8 tensor of shape {shape} on {dev}")
     Q, bins = int(Q), int(bins)
-    if Q < 0:
-        raise ValueError("depth_residuals: Q must not be negative")
+    dev, (N, H, W) = _check_maps("depth_residuals", pred_depth, pred_id, sensor, mask, labels, Q)
     if bins < 2 or bins > MAX_BINS or bins % 2:
         raise ValueError(f"depth_residuals: bins must be even and in 2..{MAX_BINS}, got {bins}")
     if not (np.isfinite(unit) and unit > 0 and np.isfinite(bin_m) and bin_m > 0):
@@ -81,26 +105,16 @@ def depth_residuals(pred_depth: torch.Tensor, pred_id: torch.Tensor, sensor: tor
     raw_lo, raw_hi = int(raw_range[0]), int(raw_range[1])
     if raw_lo > raw_hi:
         raise ValueError("depth_residuals: raw_range must be (lo, hi) with lo <= hi")
-    N, H, W = shape
-    mq = _int32_on(mesh_query, dev, None, "mesh_query")
-    lab = None
-    if labels is not None:
-        if not torch.is_tensor(labels) and any(not -2 <= int(v) <= 255 for v in np.asarray(labels).reshape(-1)):
-            raise ValueError("depth_residuals: a label must be -2, -1 or 0..255")
-        lab = _int32_on(labels, dev, Q, "labels")
+    mq = _int32_on("depth_residuals", mesh_query, dev, None, "mesh_query")
+    lab = _labels_on("depth_residuals", labels, dev, Q)
     out = {"hist": torch.empty(Q, bins, dtype=torch.int32, device=dev), "counts": torch.empty(Q, 8, dtype=torch.int64, device=dev),
            "stats": torch.empty(Q, 4, dtype=torch.float64, device=dev)}
     if Q == 0:
         return out
     lib = L.load()
-    need = int(lib.hm_depth_residuals_workspace_bytes(Q, bins))
     with torch.cuda.device(dev):
         stream = L.current_stream()
-        key = (dev.index if dev.index is not None else torch.cuda.current_device(), stream)
-        ws = _ws.get(key)
-        if ws is None or ws.numel() * 8 < need:
-            _ws.pop(key, None)
-            ws = _ws[key] = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        ws = _workspace(_ws, dev, stream, int(lib.hm_depth_residuals_workspace_bytes(Q, bins)))
         L.check(lib.hm_depth_residuals(L.ptr(pred_depth), L.ptr(pred_id), L.ptr(sensor), L.ptr(mask), L.ptr(lab), N, H, W,
                                        L.ptr(mq) if mq.numel() else None, int(mq.numel()), Q, float(unit), raw_lo, raw_hi,
                                        float(bin_m), bins, L.ptr(out["hist"]), L.ptr(out["counts"]), L.ptr(out["stats"]),
@@ -216,6 +230,21 @@ def dataset_summary(hist, counts, bin_m: float, thresholds_m: Sequence[float] = 
             "measured": valid / covered if covered else nan, "occluded": below / valid if valid else nan}
 
 
+def _renderer(who: str, H: int, W: int, K, vertices: torch.Tensor, faces, frame_index: Sequence[int], znear: float, N: int):
+    """``faces`` as int32 on the vertices' device, checked against them once, before any loop; and ``draw(placed)``: the
+    ``render_views`` depth and mesh_id maps of one mesh per hand, ``placed[j]`` in frame ``frame_index[j]`` of N."""
+    from ... import render
+    dev = vertices.device
+    faces = torch.as_tensor(faces).to(dev, torch.int32).reshape(-1, 3)
+    if faces.numel() and (int(faces.min()) < 0 or int(faces.max()) >= int(vertices.shape[1])):
+        raise ValueError(f"{who}: face corner outside the {int(vertices.shape[1])} vertices")
+
+    def draw(placed):
+        meshes = [{"frame": int(f), "vertices": placed[j], "faces": faces, "faces_checked": True} for j, f in enumerate(frame_index)]
+        return render.render_views(H, W, K, meshes, outputs=("depth", "mesh_id"), znear=znear, views=N, device=dev)
+    return faces, draw
+
+
 def refine_cam_t(H: int, W: int, K, vertices: torch.Tensor, faces, cam_t: torch.Tensor, frame_index: Sequence[int],
                  sensor: torch.Tensor, *, unit: float, iterations: int = 2, min_pixels: int = 200, min_fraction: float = 0.25,
                  znear: float = 0.05, mask: Optional[torch.Tensor] = None, labels=None, bin_m: float = 0.0005, bins: int = 4096,
@@ -234,27 +263,21 @@ def refine_cam_t(H: int, W: int, K, vertices: torch.Tensor, faces, cam_t: torch.
     from the crop camera the records do not keep.  Nothing inside the loop synchronises with the
     host.  Returns ``{'cam_t': (B, 3) like cam_t, 'median': (B,) float64 of the last iteration, 'valid': (B,) int64 of the last
     iteration, 'updated': (B,) bool}``; a hand that was never updated keeps its bytes."""
-    from ... import render
     if not (torch.is_tensor(vertices) and torch.is_tensor(cam_t) and vertices.is_cuda and cam_t.device == vertices.device):
         raise ValueError("refine_cam_t: vertices and cam_t must be tensors on one GPU; there is no CPU path")
     B = int(cam_t.shape[0])
     if vertices.dim() != 3 or int(vertices.shape[0]) != B or tuple(cam_t.shape) != (B, 3) or len(frame_index) != B:
         raise ValueError("refine_cam_t: expected vertices (B, V, 3), cam_t (B, 3) and B frame indices")
     dev = vertices.device
-    N = int(sensor.shape[0])
-    faces = torch.as_tensor(faces).to(dev, torch.int32).reshape(-1, 3)
-    if faces.numel() and (int(faces.min()) < 0 or int(faces.max()) >= int(vertices.shape[1])):      # once, before the loop
-        raise ValueError(f"refine_cam_t: face corner outside the {int(vertices.shape[1])} vertices")
+    faces, draw = _renderer("refine_cam_t", H, W, K, vertices, faces, frame_index, znear, int(sensor.shape[0]))
     query = torch.arange(B, dtype=torch.int32, device=dev)
-    lab = None if labels is None else _int32_on(labels, dev, B, "labels")
+    lab = None if labels is None else _int32_on("depth_residuals", labels, dev, B, "labels")
     cur = cam_t.clone()
     updated = torch.zeros(B, dtype=torch.bool, device=dev)
     median = torch.full((B,), float("nan"), dtype=torch.float64, device=dev)
     valid = torch.zeros(B, dtype=torch.int64, device=dev)
     for _ in range(int(iterations)):
-        placed = vertices + cur[:, None, :].to(vertices.dtype)
-        meshes = [{"frame": int(f), "vertices": placed[j], "faces": faces, "faces_checked": True} for j, f in enumerate(frame_index)]
-        r = render.render_views(H, W, K, meshes, outputs=("depth", "mesh_id"), znear=znear, views=N, device=dev)
+        r = draw(vertices + cur[:, None, :].to(vertices.dtype))
         s = depth_residuals(r["depth"], r["mesh_id"], sensor, query, B, unit=unit, bin_m=bin_m, bins=bins, raw_range=raw_range,
                             mask=mask, labels=lab)
         c = s["counts"]
@@ -303,27 +326,16 @@ def depth_fit(pred_depth: torch.Tensor, pred_id: torch.Tensor, sensor: torch.Ten
     Returns ``{'sums': (Q, 28) int64, 'counts': (Q, 8) int64 (FIT_COUNT_NAMES), 'solution': (Q, 8) float64 (omega, t, rms,
     solved)}`` on the device: the motion is ``p -> p + omega x (p - pivot) + t``.  Enqueued on the current stream without
     synchronising; the workspace is cached per device and stream (``release_fit_workspaces``).  There is no CPU path."""
-    if not all(torch.is_tensor(t) for t in (pred_depth, pred_id, sensor)):
-        raise ValueError("depth_fit: pred_depth, pred_id and sensor must be tensors")
-    dev = pred_id.device
-    if not (pred_id.is_cuda and pred_depth.device == dev and sensor.device == dev):
-        raise ValueError("depth_fit: pred_depth, pred_id and sensor must be on one GPU; there is no CPU path")
-    if pred_depth.dtype != torch.float32 or pred_id.dtype != torch.int32 or sensor.dtype not in (torch.uint16, torch.int16):
-        raise ValueError(f"depth_fit: expected float32, int32 and uint16, got {pred_depth.dtype}, {pred_id.dtype}, {sensor.dtype}")
-    shape = tuple(pred_id.shape)
-    if pred_id.dim() != 3 or 0 in shape or tuple(pred_depth.shape) != shape or tuple(sensor.shape) != shape:
-        raise ValueError(f"depth_fit: pred_depth {tuple(pred_depth.shape)} / pred_id {shape} / sensor {tuple(sensor.shape)}: "
-                         "expected three (N, H, W)")
-    if not (pred_depth.is_contiguous() and pred_id.is_contiguous() and sensor.is_contiguous()):
-        raise ValueError("depth_fit: pred_depth, pred_id and sensor must be contiguous")
-    if (mask is None) != (labels is None):
-        raise ValueError("depth_fit: mask and labels are given both or neither")
-    if mask is not None and not (torch.is_tensor(mask) and mask.device == dev and mask.dtype == torch.uint8
-                                 and tuple(mask.shape) == shape and mask.is_contiguous()):
-        raise ValueError(f"depth_fit: mask must be a contiguous uint8 tensor of shape {shape} on {dev}")
+    return _depth_fit(pred_depth, pred_id, sensor, mesh_query, Q, K, pivot, unit=unit, gate_m=gate_m, edge_m=edge_m,
+                      reach_m=reach_m, damping=damping, lever_m=lever_m, min_pixels=min_pixels, raw_range=raw_range, mask=mask,
+                      labels=labels)
+
+
+def _depth_fit(pred_depth, pred_id, sensor, mesh_query, Q, cameras, pivot, *, unit, gate_m, edge_m, reach_m, damping, lever_m,
+               min_pixels, raw_range, mask, labels):
+    """``depth_fit`` with ``cameras`` either its ``K`` or what ``_cameras`` made of one: (N, 4) float64 on the maps' GPU."""
     Q, min_pixels = int(Q), int(min_pixels)
-    if Q < 0:
-        raise ValueError("depth_fit: Q must not be negative")
+    dev, (N, H, W) = _check_maps("depth_fit", pred_depth, pred_id, sensor, mask, labels, Q)
     if not (np.isfinite(unit) and unit > 0):
         raise ValueError("depth_fit: unit must be finite and > 0")
     if not (0 < gate_m <= 0.25 and 0 < edge_m < np.inf and 0 < reach_m <= 1 and 0 <= damping < np.inf and 0 < lever_m < np.inf
@@ -336,27 +348,19 @@ def depth_fit(pred_depth: torch.Tensor, pred_id: torch.Tensor, sensor: torch.Ten
     if not (torch.is_tensor(pivot) and pivot.device == dev and pivot.dtype == torch.float64 and tuple(pivot.shape) == (Q, 3)
             and pivot.is_contiguous()):
         raise ValueError(f"depth_fit: pivot must be a contiguous float64 tensor of shape ({Q}, 3) on {dev}")
-    N, H, W = shape
-    cams = _cameras(K, N, dev)
-    mq = _int32_on(mesh_query, dev, None, "mesh_query")
-    lab = None
-    if labels is not None:
-        if not torch.is_tensor(labels) and any(not -2 <= int(v) <= 255 for v in np.asarray(labels).reshape(-1)):
-            raise ValueError("depth_fit: a label must be -2, -1 or 0..255")
-        lab = _int32_on(labels, dev, Q, "labels")
+    made = torch.is_tensor(cameras) and tuple(cameras.shape) == (N, 4) and cameras.dtype == torch.float64 \
+        and cameras.device == dev and cameras.is_contiguous()
+    cams = cameras if made else _cameras(cameras, N, dev)
+    mq = _int32_on("depth_fit", mesh_query, dev, None, "mesh_query")
+    lab = _labels_on("depth_fit", labels, dev, Q)
     out = {"sums": torch.empty(Q, 28, dtype=torch.int64, device=dev), "counts": torch.empty(Q, 8, dtype=torch.int64, device=dev),
            "solution": torch.empty(Q, 8, dtype=torch.float64, device=dev)}
     if Q == 0:
         return out
     lib = L.load()
-    need = int(lib.hm_depth_fit_workspace_bytes(Q))
     with torch.cuda.device(dev):
         stream = L.current_stream()
-        key = (dev.index if dev.index is not None else torch.cuda.current_device(), stream)
-        ws = _fit_ws.get(key)
-        if ws is None or ws.numel() * 8 < need:
-            _fit_ws.pop(key, None)
-            ws = _fit_ws[key] = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        ws = _workspace(_fit_ws, dev, stream, int(lib.hm_depth_fit_workspace_bytes(Q)))
         L.check(lib.hm_depth_fit(L.ptr(pred_depth), L.ptr(pred_id), L.ptr(sensor), L.ptr(mask), L.ptr(lab), N, H, W,
                                  L.ptr(mq) if mq.numel() else None, int(mq.numel()), Q, L.ptr(cams), L.ptr(pivot), float(unit),
                                  raw_lo, raw_hi, float(gate_m), float(edge_m), float(reach_m), float(damping), float(lever_m),
@@ -399,7 +403,6 @@ def fit_rigid(H: int, W: int, K, vertices: torch.Tensor, faces, cam_t: torch.Ten
     vertices: rotation (vertices + ray cam_t - ray pivot) + pivot), 'rms': (B,) float64 and 'used': (B,) int64 of the last
     iteration, 'updated': (B,) bool (a ray or a rigid step was applied), 'fitted': (B,) bool (a rigid step was), 'median' and
     'valid': the ray rounds' last (NaN and 0 without any)}``; a hand that never had a step applied keeps its bytes."""
-    from ... import render
     if not (torch.is_tensor(vertices) and torch.is_tensor(cam_t) and torch.is_tensor(pivot) and vertices.is_cuda
             and cam_t.device == vertices.device and pivot.device == vertices.device):
         raise ValueError("fit_rigid: vertices, cam_t and pivot must be tensors on one GPU; there is no CPU path")
@@ -409,9 +412,7 @@ def fit_rigid(H: int, W: int, K, vertices: torch.Tensor, faces, cam_t: torch.Ten
         raise ValueError("fit_rigid: expected vertices (B, V, 3), cam_t (B, 3), pivot (B, 3) and B frame indices")
     dev = vertices.device
     N = int(sensor.shape[0])
-    faces = torch.as_tensor(faces).to(dev, torch.int32).reshape(-1, 3)
-    if faces.numel() and (int(faces.min()) < 0 or int(faces.max()) >= int(vertices.shape[1])):      # once, before the loops
-        raise ValueError(f"fit_rigid: face corner outside the {int(vertices.shape[1])} vertices")
+    faces, draw = _renderer("fit_rigid", H, W, K, vertices, faces, frame_index, znear, N)
     cams = _cameras(K, N, dev)
     if int(ray_iterations) > 0:
         ray = refine_cam_t(H, W, K, vertices, faces, cam_t, frame_index, sensor, unit=unit, iterations=int(ray_iterations),
@@ -425,20 +426,17 @@ def fit_rigid(H: int, W: int, K, vertices: torch.Tensor, faces, cam_t: torch.Ten
     cam64 = cam_ray.to(torch.float64)
     pv = (pivot.to(torch.float64) + (cam64 - cam_t.to(torch.float64))).contiguous()
     placed = vertices.to(torch.float64) + cam64[:, None, :]
-    Kn = torch.zeros(N, 3, 3, dtype=torch.float64, device=dev)                                     # depth_fit takes K as (N, 3, 3)
-    Kn[:, 0, 0], Kn[:, 1, 1], Kn[:, 0, 2], Kn[:, 1, 2], Kn[:, 2, 2] = cams[:, 0], cams[:, 1], cams[:, 2], cams[:, 3], 1.0
     query = torch.arange(B, dtype=torch.int32, device=dev)
-    lab = None if labels is None else _int32_on(labels, dev, B, "labels")
+    lab = None if labels is None else _int32_on("depth_fit", labels, dev, B, "labels")
     R = torch.eye(3, dtype=torch.float64, device=dev)[None].repeat(B, 1, 1)
     shift = torch.zeros(B, 3, dtype=torch.float64, device=dev)
     fitted = torch.zeros(B, dtype=torch.bool, device=dev)
     rms = torch.full((B,), float("nan"), dtype=torch.float64, device=dev)
     used = torch.zeros(B, dtype=torch.int64, device=dev)
     for _ in range(int(iterations)):
-        meshes = [{"frame": int(f), "vertices": placed[j], "faces": faces, "faces_checked": True} for j, f in enumerate(frame_index)]
-        r = render.render_views(H, W, K, meshes, outputs=("depth", "mesh_id"), znear=znear, views=N, device=dev)
-        s = depth_fit(r["depth"], r["mesh_id"], sensor, query, B, Kn, pv, unit=unit, gate_m=gate_m, edge_m=edge_m, reach_m=reach_m,
-                      damping=damping, lever_m=lever_m, min_pixels=min_pixels, raw_range=raw_range, mask=mask, labels=lab)
+        r = draw(placed)
+        s = _depth_fit(r["depth"], r["mesh_id"], sensor, query, B, cams, pv, unit=unit, gate_m=gate_m, edge_m=edge_m, reach_m=reach_m,
+                       damping=damping, lever_m=lever_m, min_pixels=min_pixels, raw_range=raw_range, mask=mask, labels=lab)
         sol = s["solution"]
         w, t = sol[:, :3], sol[:, 3:6]
         ok = (sol[:, 7] > 0.5) & (torch.sqrt((w * w).sum(1)) <= float(max_rot_rad)) & (torch.sqrt((t * t).sum(1)) <= float(max_shift_m))

@@ -108,6 +108,51 @@ def test_random_maps():
     DE.release_workspaces()
 
 
+# ------------------------------------------------------------------ 7b: more than one workgroup of the scan
+def big_maps():
+    """3 x 120 x 160 pixels -- a workgroup of the scan takes 32768 -- with eleven meshes on a smooth depth field: seven in the
+    first workgroup's pixels, the disc of mesh 7 lying across pixel 32768 (row 84 of frame 1); the sensor is up to 4 mm off."""
+    N, H, W = 3, 120, 160
+    n, v, u = np.meshgrid(np.arange(N), np.arange(H), np.arange(W), indexing="ij")
+    z = 0.5 + 2e-5 * u + 2e-5 * v + 0.003 * np.sin(u / 7.0) * np.cos(v / 5.0) + 0.01 * n
+    sensor = np.rint((z + 0.004 * np.sin(u / 11.0 + v / 13.0 + n)) * 1000.0).astype(np.uint16)
+    pid = np.full((N, H, W), -1, np.int32)
+    for k in range(6):
+        pid[0, 5 + 38 * (k // 3):40 + 38 * (k // 3), 4 + 52 * (k % 3):50 + 52 * (k % 3)] = k
+    for frame, cv, cu, r, i in ((0, 100, 80, 18, 6), (1, 85, 80, 30, 7)):
+        pid[frame][(v[0] - cv) ** 2 + (u[0] - cu) ** 2 <= r * r] = i
+    pid[1, 2:30, 2:158], pid[2, 10:110, 10:150] = 8, 9
+    pid[2][(v[0] - 60) ** 2 + (u[0] - 80) ** 2 <= 20 * 20] = 10
+    pid[0, 0, :3], pid[2, -1, -3:] = 0, 9                                              # the scalar head and tail of an unaligned base are covered
+    return np.where(pid >= 0, z, 0.0).astype(np.float32), pid, sensor
+
+
+def test_more_than_one_workgroup():
+    """Vector indices past the first workgroup's, and the scalar head and tail read by workgroup 0 alone."""
+    depth, pid, sensor = big_maps()
+    total, mq = pid.size, list(range(11))
+    # by the rule alone: every query has pixels in range, and mesh 7 has some on both sides of pixel 32768
+    at = np.arange(total).reshape(pid.shape)
+    sides = [DR.residuals(depth, np.where(keep, pid, -1), sensor, mq, 11)[1] for keep in (at < 32768, at >= 32768)]
+    assert total > 32768 and sides[0][7, 5] > 0 and sides[1][7, 5] > 0 and ((sides[0] + sides[1])[:, 5] > 0).all()
+    got, (hist, counts, _) = run(depth, pid, sensor, mq, 11)
+    assert np.array_equal(counts, sides[0] + sides[1]) and len(np.unique(pid[0][pid[0] >= 0])) == 7
+    one, (hist1, counts1, _) = run(depth, pid, sensor, [0] * 11, 1)
+    assert torch.equal(one["hist"][0], got["hist"].sum(0, dtype=torch.int32)) and torch.equal(one["counts"][0], got["counts"].sum(0))
+    assert np.array_equal(hist1[0], hist.sum(0))
+    # the same from a base 4 bytes past a 16-byte boundary: three pixels of head, one of tail (total % 4 == 0)
+    flat = [torch.zeros(total + 8, dtype=t.dtype, device=DEV) for t in (dev(depth), dev(pid), dev(sensor))]   # mesh 0 around the view
+    for t, a in zip(flat, (depth, pid, sensor)):
+        t[1:1 + total] = dev(a).reshape(-1)
+    d, i, s = (t[1:1 + total].view(pid.shape) for t in flat)
+    assert i.data_ptr() % 16 == 4 and i.is_contiguous() and total % 4 == 0 and (pid.reshape(-1)[[0, 1, 2, -1]] >= 0).all()
+    for q, Q in ((mq, 11), ([0] * 11, 1)):
+        off = DE.depth_residuals(d, i, s, q, Q)
+        check(off, depth, pid, sensor, q, Q)
+        assert all(torch.equal(off[k], (got if Q == 11 else one)[k]) for k in ("hist", "counts"))
+    DE.release_workspaces()
+
+
 # ------------------------------------------------------------------ 8: residuals exactly on bin edges, both ends of the range
 @pytest.mark.parametrize("bins", [2, 4096])
 def test_bin_edges(bins):
