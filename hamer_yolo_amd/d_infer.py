@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from .infer import *  # noqa: F401,F403
-from .infer import (FRAMES_PER_STEP, _default_models, _detection_list, _imread_bgr, _list_images, _antialias_args, _precise_hamer_args, _tta_args, apply_tta_args, _record_from, _render_args, _depth_args, depth_args, refine_records, render_keypoint_args, apply_antialias_args, apply_precise_args, hamer_inference,  # noqa: F401
+from .infer import (FRAMES_PER_STEP, _default_models, _detection_list, _imread_bgr, _list_images, _antialias_args, _precise_hamer_args, _tta_args, apply_tta_args, _record_from, _render_args, _depth_args, depth_args, refine_records, _mask_fit_args, mask_fit_records, render_keypoint_args, apply_antialias_args, apply_precise_args, hamer_inference,  # noqa: F401
                     hamer_opt, hand_record, iter_folder_results, load_intrinsics, reconstruct_and_save_obj_with_wrapper)
 from .rootnet.Model_RGB import get_model  # noqa: F401
 
@@ -56,6 +56,10 @@ def _parser() -> argparse.ArgumentParser:
     _precise_hamer_args(ap)
     _antialias_args(ap)
     _render_args(ap)
+    ap.add_argument('--masks', type=str, default=None, metavar="DIR",
+                    help="label masks DIR/<name>.npy for --mask-fit (the detector still finds the hands)")
+    ap.add_argument('--mask-label', type=int, default=3, help="with --masks: the label of the hands' pixels (default 3, the reference's)")
+    _mask_fit_args(ap)
     _depth_args(ap)
     return ap
 
@@ -74,6 +78,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     keypoint_kw = render_keypoint_args(ap, args)
     depth_args(ap, args)
+    if not args.masks and (args.mask_fit != "none" or args.mask_label != 3):
+        ap.error("--mask-fit / --mask-label need --masks DIR")
+    if not 1 <= args.mask_label <= 255:
+        ap.error("--mask-label must be in 1..255")
     apply_precise_args(args)
     apply_antialias_args(args)
     apply_tta_args(args)
@@ -81,6 +89,9 @@ def main(argv=None):
     k_real = load_intrinsics(args.intrinsics)
     hamer = hamer_inference(hamer_opt)
     process_batch_manopara(args.input, args.output, k_real, hamer=hamer)
+    if args.masks and args.mask_fit == "contour":                  # before the depth step: that one starts from the fitted records
+        from .infer import _rank_world
+        mask_fit_records(args, hamer, *_rank_world(None, None))
     if args.depth_maps:
         from .infer import _rank_world
         refine_records(args, hamer, *_rank_world(None, None))

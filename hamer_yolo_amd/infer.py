@@ -1255,6 +1255,25 @@ def _mask_args(ap: argparse.ArgumentParser) -> None:
     ap.add_argument('--mask-label', type=int, default=3, help="with --masks: the label of the (right) hand's pixels (default 3, the reference's)")
     ap.add_argument('--left-mask-label', type=int, default=None, metavar="L",
                     help="with --masks: also box label L as a left hand, for masks that tell the hands apart (default: right hands only)")
+    _mask_fit_args(ap)
+
+
+def _mask_fit_args(ap: argparse.ArgumentParser) -> None:
+    ap.add_argument('--mask-fit', type=str, default="none", choices=("none", "contour"),
+                    help="with --masks: none (default) writes the records as predicted; contour fits every hand's silhouette to its "
+                         "mask's contour -- shift in the image plane, scale (depth) and rotation about the viewing axis, folded into "
+                         "cam_t and pose_global (evaluate_masks --refine-to).  With --depth-maps too, the mask fit runs first and "
+                         "the depth refinement starts from its result")
+
+
+def mask_fit_records(args, hamer, rank: int, world: int, left_label=None) -> None:
+    """The ``--mask-fit contour`` step of the drivers: the records of ``--output`` are rewritten in place, fitted to the masks."""
+    from . import evaluate_depth as ED
+    from . import evaluate_masks as EM
+    k_real = ED.load_cameras(args.intrinsics) if args.intrinsics else None
+    r = EM.refine_folder(args.input, args.output, args.masks, args.output, hamer, k_real, label=args.mask_label,
+                         left_label=left_label, rank=rank, world=world)
+    print(f"{r['fitted']} of {r['hands']} hands fitted to {args.masks}" + (f" (rank {rank})" if world > 1 else ""))
 
 
 def mask_args(ap: argparse.ArgumentParser, args) -> None:
@@ -1263,6 +1282,8 @@ def mask_args(ap: argparse.ArgumentParser, args) -> None:
     if not args.masks:
         if args.left_mask_label is not None or args.mask_label != 3:
             ap.error("--mask-label / --left-mask-label need --masks DIR")
+        if args.mask_fit != "none":
+            ap.error("--mask-fit needs --masks DIR")
         return
     for flag, on in (("--yolo-weights", args.yolo_weights is not None), ("--precise-detector", args.precise_detector),
                      ("--tta-detector", args.tta_detector)):
@@ -1388,6 +1409,10 @@ def main(argv=None):
             print(f"{stats['global_frames']} files, {stats['global_hands']} hands over {world} ranks: {stats['per_rank']}")
         import torch.distributed as dist
         dist.barrier()
+    if args.masks and args.mask_fit == "contour":                  # before the depth step: that one starts from the fitted records
+        mask_fit_records(args, hamer, rank, world, left_label=args.left_mask_label)
+        if world > 1:
+            dist.barrier()
     if args.depth_maps:
         refine_records(args, hamer, rank, world)
         if world > 1:

@@ -50,6 +50,7 @@ EXPORTS = [
     "hm_mask_boxes",
     "hm_depth_residuals_workspace_bytes", "hm_depth_residuals",
     "hm_depth_fit_workspace_bytes", "hm_depth_fit",
+    "hm_mask_fit_workspace_bytes", "hm_mask_fit",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -322,6 +323,9 @@ def load() -> C.CDLL:
     lib.hm_depth_fit_workspace_bytes.argtypes = [i]
     lib.hm_depth_fit_workspace_bytes.restype = C.c_size_t
     lib.hm_depth_fit.argtypes = [vp, vp, vp, vp, vp, i, i, i, vp, i, i, vp, vp, d, i, i, d, d, d, d, d, i, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.hm_mask_fit_workspace_bytes.argtypes = [i, i, i, i]
+    lib.hm_mask_fit_workspace_bytes.restype = C.c_size_t
+    lib.hm_mask_fit.argtypes = [vp, vp, i, i, i, vp, i, vp, i, i, i, d, d, i, vp, vp, vp, vp, C.c_size_t, vp]
     lib.hm_skeleton_overlay_workspace_bytes.argtypes = [i, i, i, i]
     lib.hm_skeleton_overlay_workspace_bytes.restype = C.c_size_t
     lib.hm_skeleton_overlay.argtypes = [vp, i, i, i, vp, i, C.POINTER(Skeleton), i, C.POINTER(C.c_uint8), i, vp, vp, C.c_size_t, vp]
@@ -341,7 +345,7 @@ def load() -> C.CDLL:
                         "hm_mesh_overlay_workspace_bytes", "hm_mesh_render_workspace_bytes",
                         "hm_skeleton_overlay_workspace_bytes", "hm_det_ap_workspace_bytes", "hm_nms_batch_workspace_bytes",
                         "hm_pck_auc_workspace_bytes", "hm_mask_score_workspace_bytes", "hm_depth_residuals_workspace_bytes",
-                        "hm_depth_fit_workspace_bytes"):
+                        "hm_depth_fit_workspace_bytes", "hm_mask_fit_workspace_bytes"):
             fn.restype = i
     if lib.hm_version() != HM_VERSION:
         raise HipLibraryError(f"{LIB_PATH} reports HM_VERSION {lib.hm_version()}, this binding is written for {HM_VERSION}: "

@@ -1038,6 +1038,63 @@ int hm_depth_fit(const float* pred_depth, const int32_t* pred_id, const uint16_t
                  int min_pixels, int64_t* sums /* device [Q][28] */, int64_t* counts /* device [Q][8] */,
                  double* solution /* device [Q][8] */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Mask fit: the 2-D similarity that brings a predicted silhouette's contour onto a label mask's: csrc/mask_fit.hip.  Per
+ * query the 4 x 4 normal equations of a contour alignment, 2 x 6 pixel counts and their damped Cholesky solution: image-plane
+ * shift, scale and rotation about the viewing axis (hamer/utils/mask_eval.py mask_fit and fit_contour).
+ *
+ * pred_id, mask, N, H, W, queries and Q are hm_mask_score's and mean the same (pred: id_lo <= pred_id < id_hi; gt: mask == label,
+ * or mask != 0 when label == -1).  centre [Q][2] i32 on the device: the integer pixel (x, y) each query's similarity is taken
+ * about.  radius in 0..64, reach_px in 1..4096, directions 1 (pred -> mask), 2 (mask -> pred) or 3 (both), damping >= 0 and
+ * lever_px > 0 (both finite), min_pixels >= 1.
+ *
+ * All per-pixel work is in integers.
+ *   Boundary map  b(s) exactly as under "Mask scores": the east, south and south-east neighbours, the last row and column
+ *                 replicated.
+ *   Match         for a boundary pixel p of map A, the boundary pixel of map B at an integer offset (dx, dy) with d2 = dx dx +
+ *                 dy dy <= radius radius that has the least d2; ties go to the least dy, then to the least dx.  None: the pixel is
+ *                 `unmatched`.
+ *   Direction 1   A = b(pred), B = b(gt); the moved point is u = p - centre and the displacement d = (dx, dy).
+ *   Direction 2   A = b(gt), B = b(pred); the moved point is the matched pred pixel, u = p + (dx, dy) - centre, and d = (-dx, -dy).
+ *   Reach         a matched pixel with ux ux + uy uy > reach_px reach_px is `out_of_reach` and adds nothing (evaluated without
+ *                 overflow for any centre: |ux| or |uy| > reach_px is out of reach).
+ * Unknowns x = (alpha, beta, tx, ty) of the motion q -> centre + (1 + alpha) (q - centre) + beta J (q - centre) + t with
+ * J (x, y) = (-y, x): scale hypot(1 + alpha, beta), angle atan2(beta, 1 + alpha) (positive: x turns towards y).
+ *   d2 > 0        a point-to-line term whose line normal is the direction to the nearest pixel: row Jr = (d.u, d.Ju, dx, dy) =
+ *                 (dx ux + dy uy, dy ux - dx uy, dx, dy) of the displacement d, residual rho = d2, weight 1 / d2.  sums[q] += the
+ *                 ten integers llrint((double)(Jr_i Jr_j) / (double)d2 * 2^20) for the pairs i <= j row by row ((0,0), (0,1) ..
+ *                 (0,3), (1,1) ..) into sums[0..9], the four integers Jr_i (= Jr_i rho / d2, exact) into sums[10..13], and d2
+ *                 (= rho rho / d2) into sums[14].  The products are exact int64 and exact doubles (below 2^38); one correctly
+ *                 rounded division per term, so the integers are the same wherever the rule is evaluated.
+ *   d2 == 0       the pixel already lies on the other contour: a point-to-point anchor with right-hand side 0.  sums[15] += ux,
+ *                 sums[16] += uy, sums[17] += ux ux + uy uy; with their number these are the entries of A^T A for
+ *                 A = [[ux, -uy, 1, 0], [uy, ux, 0, 1]].
+ * Every divided term is at most max(|u|^2, 1) <= 2^25 times 2^20, so an int64 sum cannot overflow below 2^18 used pixels per
+ * query (a 1080 x 1920 frame whose every pixel is a boundary pixel has 2^21; a hand's contour has some 2^11).
+ * counts i64 [Q][2][6], per direction: 0 boundary, 1 matched with d2 > 0, 2 anchored, 3 unmatched, 4 out of reach, 5 zero;
+ * boundary = the sum of 1..4; the entries of a direction that is switched off are 0.  sums i64 [Q][18].
+ * The solve, per query from its integers: used = the matched and the anchored of both directions, na = the anchored of both.
+ * M symmetric with M_ij = (double)sums[k] * 2^-20 for the ten pairs; then M_00 += (double)sums[17], M_11 += (double)sums[17],
+ * M_02 += (double)sums[15], M_03 += (double)sums[16], M_12 -= (double)sums[16], M_13 += (double)sums[15], M_22 += (double)na,
+ * M_33 += (double)na; then M_ii = M_ii + (damping * (double)used) * (lever_px * lever_px) for i < 2 and M_ii + damping *
+ * (double)used for the rest; g_i = (double)sums[10 + i].  Cholesky M = L L^T column by column, the forward and the backward
+ * substitution exactly as under "Depth fit" with 4 in the place of 6, every inner sum from k = 0 upwards; fp64, compiled with
+ * contraction off.  solution f64 [Q][8] = alpha, beta, tx, ty, rms = sqrt((double)sums[14] / (double)used) (0 when used == 0),
+ * 1.0 for solved, 0, 0; a query with used < min_pixels or an s of a diagonal that is not > 0 is not solved: zeros, the flag 0,
+ * and never a NaN.  A query whose frame is outside 0..N-1 is not read: its sums, counts and solution are all zero.
+ * sums, counts and solution are all written on every call (callers do not clear them).  A query's numbers depend on its own
+ * images and the scalars alone: not on Q, the order of the queries, the rest of the batch or the grid (the sums are integer
+ * atomics).  Asynchronous on `stream`: four kernels (init, pack, match, solve), no host synchronisation, no allocation; the
+ * workspace holds the two boundary maps of every query, one bit per pixel, and 32 int64 per query where the sums are added up.
+ * Q == 0 succeeds and launches nothing (queries, centre, the outputs and workspace may then be NULL).
+ * HM_ERR_ARG before any device work: a null pointer, N, H or W < 1, N H W >= 2^31, radius outside 0..64, reach_px outside
+ * 1..4096, directions outside 1..3, damping negative or not finite, lever_px not finite and > 0, min_pixels < 1, Q < 0,
+ * workspace_bytes below the query, sums, counts, solution or workspace not 8-byte aligned (pred_id, queries and centre: 4-byte). */
+size_t hm_mask_fit_workspace_bytes(int Q, int H, int W, int radius);   /* 0 for illegal sizes; positive otherwise */
+int hm_mask_fit(const int32_t* pred_id, const uint8_t* mask, int N, int H, int W, const hm_mask_query* queries /* device */, int Q,
+                const int32_t* centre /* device [Q][2]: x, y */, int radius, int reach_px, int directions, double damping,
+                double lever_px, int min_pixels, int64_t* sums /* device [Q][18] */, int64_t* counts /* device [Q][2][6] */,
+                double* solution /* device [Q][8] */, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Detector evaluation (yolo/yolov7/test.py and utils/metrics.py): csrc/det_eval.hip.  The caller owns every buffer, the
  * calls are asynchronous on `stream`, nothing synchronises or allocates, argument errors return HM_ERR_ARG before any device
  * work.  All fp32 / fp64 arithmetic is plain IEEE in the order written (no FMA contraction, no fast-math).
