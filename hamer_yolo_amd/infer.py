@@ -1213,6 +1213,7 @@ def _parser() -> argparse.ArgumentParser:
     _render_args(ap)
     _mask_args(ap)
     _depth_args(ap)
+    _visibility_args(ap)
     return ap
 
 
@@ -1274,6 +1275,24 @@ def mask_fit_records(args, hamer, rank: int, world: int, left_label=None) -> Non
     r = EM.refine_folder(args.input, args.output, args.masks, args.output, hamer, k_real, label=args.mask_label,
                          left_label=left_label, rank=rank, world=world)
     print(f"{r['fitted']} of {r['hands']} hands fitted to {args.masks}" + (f" (rank {rank})" if world > 1 else ""))
+
+
+def _visibility_args(ap: argparse.ArgumentParser) -> None:
+    ap.add_argument('--visibility', action='store_true',
+                    help="after the records are written (and after any --mask-fit / --depth-maps step), rewrite them in place with what "
+                         "the camera sees of every hand: joints_visible, vertices_visible, visible_share, in_frame, amodal_box, "
+                         "modal_box, visibility_counts (evaluate_visibility --write-to); --depth-maps and --masks are used when given")
+
+
+def visibility_records(args, hamer, rank: int, world: int, left_label=None) -> None:
+    """The ``--visibility`` step of the drivers: the records of ``--output`` are rewritten in place with the visibility keys."""
+    from . import evaluate_depth as ED
+    from . import evaluate_visibility as EV
+    k_real = ED.load_cameras(args.intrinsics) if args.intrinsics else None
+    r = EV.annotate_folder(args.output, args.output, hamer, k_real, depth_folder=args.depth_maps, unit=args.depth_scale,
+                           mask_folder=args.masks, label=args.mask_label, left_label=left_label, image_folder=args.input, rank=rank,
+                           world=world)
+    print(f"{r['annotated']} of {r['hands']} hands annotated with visibility" + (f" (rank {rank})" if world > 1 else ""))
 
 
 def mask_args(ap: argparse.ArgumentParser, args) -> None:
@@ -1355,6 +1374,9 @@ def _render_args(ap: argparse.ArgumentParser) -> None:
                     help="colours, order and default radii of the skeletons (default hamer: draw_2d_skeleton.py's)")
     ap.add_argument('--keypoint-line-radius', type=int, default=None, help="bone half-width in pixels, 0..32 (default: by style)")
     ap.add_argument('--keypoint-joint-radius', type=int, default=None, help="joint disc radius in pixels, 0..32 (default: by style)")
+    ap.add_argument('--visible-joints', action='store_true',
+                    help="with --render-keypoints: leave out the joints (and their bones) whose joints_visible code in the record "
+                         "is not 0 (records written with --visibility); a record without the key draws all joints")
     ap.add_argument('--hand-maps', type=str, default=None, metavar="DIR",
                     help="after the records are written, write per frame into DIR the label mask <name>.npy (uint8, --hand-label on "
                          "hand pixels) and <name>_maps.npz (depth in metres, index of the covering hand)")
@@ -1366,12 +1388,15 @@ def render_keypoint_args(ap: argparse.ArgumentParser, args) -> Dict:
     usage error."""
     if args.render_keypoints and not args.render:
         ap.error("--render-keypoints needs --render DIR")
+    if args.visible_joints and not args.render_keypoints:
+        ap.error("--visible-joints needs --render DIR --render-keypoints over|only")
     for name in ("keypoint_line_radius", "keypoint_joint_radius"):
         v = getattr(args, name)
         if v is not None and not 0 <= v <= 32:
             ap.error(f"--{name.replace('_', '-')} must be in 0..32")
     return {"keypoints": args.render_keypoints, "keypoint_style": args.keypoint_style,
-            "line_radius": args.keypoint_line_radius, "joint_radius": args.keypoint_joint_radius}
+            "line_radius": args.keypoint_line_radius, "joint_radius": args.keypoint_joint_radius,
+            **({"visible_joints": True} if args.visible_joints else {})}
 
 
 def main(argv=None):
@@ -1415,6 +1440,10 @@ def main(argv=None):
             dist.barrier()
     if args.depth_maps:
         refine_records(args, hamer, rank, world)
+        if world > 1:
+            dist.barrier()
+    if args.visibility:
+        visibility_records(args, hamer, rank, world, left_label=args.left_mask_label)
         if world > 1:
             dist.barrier()
     if args.obj and rank == 0:

@@ -435,7 +435,7 @@ def decode_pass(pool, paths: Sequence[str], hw: tuple):
 
 def render_folder(image_folder, npy_folder, out_folder, hamer, k_real=None, style: str = "flat", rank: int = 0, world: int = 1,
                   ext: str = ".jpg", frames_per_pass: int = FRAMES_PER_PASS, keypoints: Optional[str] = None,
-                  keypoint_style: str = "hamer", line_radius=None, joint_radius=None) -> int:
+                  keypoint_style: str = "hamer", line_radius=None, joint_radius=None, visible_joints: bool = False) -> int:
     """Draw the hands of every ``<name>.npy`` record of ``npy_folder`` onto ``image_folder``'s ``<name>.*`` frame and write
     ``out_folder/<name><ext>`` (``.jpg`` as the reference; any extension PIL writes).  Frames are grouped by the size their
     headers give and drawn in passes of ``frames_per_pass``: per pass the frames are decoded, ONE MANO forward runs for all its
@@ -446,9 +446,14 @@ def render_folder(image_folder, npy_folder, out_folder, hamer, k_real=None, styl
     world)``.  ``keypoints``: None, or 'over' / 'only' to draw the hands' 21 MANO joints as skeletons (``skeleton_frames``,
     ``keypoint_style`` and radii as there) over the mesh overlay / onto the decoded frames instead of it: the joints of the
     pass's MANO forward, mirrored and translated like the vertices, projected on the device (``project_points``), one call in
-    place.  Returns the number of images written; the overlay workspaces are released at the end."""
+    place.  ``visible_joints`` (with ``keypoints``): a joint whose code in the record's ``joints_visible``
+    (``evaluate_visibility.annotate_folder``) is not 0 is absent, and so are its bones -- through the
+    skeleton rule's confidence column (1 or 0); a hand without ``joints_visible`` draws all its joints, which is said once.
+    Returns the number of images written; the overlay workspaces are released at the end."""
     if keypoints not in (None, "over", "only"):
         raise ValueError(f"keypoints must be None, 'over' or 'only', got {keypoints!r}")
+    if visible_joints and not keypoints:
+        raise ValueError("visible_joints needs keypoints 'over' or 'only'")
     if keypoints and keypoint_style not in SKELETON_STYLES:
         raise ValueError(f"keypoint_style must be one of {sorted(SKELETON_STYLES)}, got {keypoint_style!r}")
     os.makedirs(out_folder, exist_ok=True)
@@ -482,6 +487,8 @@ def render_folder(image_folder, npy_folder, out_folder, hamer, k_real=None, styl
                     out = overlay_frames(torch.from_numpy(batch).to(dev), K, meshes, style=style)
                 if keypoints:
                     kp = project_points(joints, K)
+                    if visible_joints:
+                        kp = torch.cat([kp, torch.from_numpy(joint_confidences([h for _, h in hands])).to(dev)[..., None]], dim=2)
                     if keypoint_style == "openpose" and (line_radius is None or joint_radius is None):
                         kp = kp.cpu().numpy()                          # the OpenPose thickness is host arithmetic on the keypoints
                     skeleton_frames(out, kp, [n for n, _ in hands], style=keypoint_style, line_radius=line_radius,
@@ -491,6 +498,24 @@ def render_folder(image_folder, npy_folder, out_folder, hamer, k_real=None, styl
             return writer.close()
     finally:
         release_workspaces()
+
+
+_said_no_flags = []
+
+
+def joint_confidences(hands: Sequence[dict]) -> np.ndarray:
+    """(n, 21) float32 for the skeleton rule's confidence column: 1 where a hand record's ``joints_visible`` code is 0
+    (VISIBLE), 0 elsewhere; all 1 for a record without the key, with one printed line the first time."""
+    conf = np.ones((len(hands), 21), np.float32)
+    for j, h in enumerate(hands):
+        flags = h.get("joints_visible")
+        if flags is None:
+            if not _said_no_flags:
+                _said_no_flags.append(True)
+                print("visible_joints: a record has no joints_visible (write it with --visibility or evaluate_visibility --write-to): all its joints are drawn")
+            continue
+        conf[j] = (np.asarray(flags).reshape(21) == 0).astype(np.float32)
+    return conf
 
 
 def _record_jobs(image_folder, npy_folder, rank: int, world: int, keep_empty: bool):

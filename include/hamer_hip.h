@@ -1095,6 +1095,89 @@ int hm_mask_fit(const int32_t* pred_id, const uint8_t* mask, int N, int H, int W
                 double lever_px, int min_pixels, int64_t* sums /* device [Q][18] */, int64_t* counts /* device [Q][2][6] */,
                 double* solution /* device [Q][8] */, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Visibility: which parts of a hand the camera sees: csrc/visibility.hip.  hm_point_visibility gives one code per 3-D
+ * point (a joint, a vertex), hm_mesh_coverage pixel counts and boxes per mesh; both read the depth and mesh_id maps that
+ * hm_mesh_render wrote for the same meshes, and optionally a sensor depth map and a label mask (hamer/utils/visibility.py,
+ * DESIGN.md section 10.6).  The unit is compiled with contraction off (#pragma clang fp contract(off)); every fp64 expression
+ * is evaluated left to right as written.
+ *
+ * Common inputs.  depth [N][H][W] f32 and mesh_id [N][H][W] i32 as hm_mesh_render writes them (a pixel is COVERED when
+ * mesh_id >= 0); K_host [N][3][3] fp64 on the HOST, last row exactly (0, 0, 1); znear as hm_mesh_render's.  sensor [N][H][W] u16
+ * or NULL: raw units of `unit` metres; a reading is VALID when raw != 0 && raw_lo <= raw <= raw_hi; unit, raw_lo, raw_hi and
+ * scene_tol_m are read (and checked) only with a sensor.  mask [N][H][W] u8 or NULL, tested with a label as hm_depth_residuals
+ * does: -2 no test, -1 mask != 0, 0..255 mask == label, any other value: no pixel passes.
+ *
+ * hm_point_visibility.  points [P][3] fp64, camera frame, on the device.  groups [G] on the device: group g owns the points
+ * p0 .. p0 + np - 1, lies in view `view`, belongs to mesh row `mesh` of the render, and is tested with its own tol_m (metres)
+ * and label.  The groups' point ranges do not overlap.  A group whose range leaves 0..P-1 (or with np < 0) is treated as
+ * empty: no point of it is read or written and its entry 7 is 0.  window in 0..2: the half-width of the pixel window.
+ * Rule per point (x, y, z) of a group:
+ *   1  `z >= znear` is false (NaN included): BEHIND (1)
+ *   2  projection, exactly hm_mesh_render's: u = ((K00*x + K01*y) + K02*z) / z, v = ((K10*x + K11*y) + K12*z) / z with the K of
+ *      the group's view; `|u| < 65536 && |v| < 65536` is false: OUTSIDE (2).  X = rint_half_even(256*u), px = X >> 8 (an
+ *      arithmetic shift: the floor; a negative X is outside), py likewise from v.  (px, py) outside the image, or the group's
+ *      view outside 0..N-1 (such a group reads no map): OUTSIDE (2)
+ *   3  hand test over the window pixels (px + dx, py + dy), |dx|, |dy| <= window, that lie inside the image: a covered pixel
+ *      passes when (double)depth >= z - tol_m; an uncovered pixel passes only when it is the centre pixel (an uncovered
+ *      neighbour is neutral).  No pixel passes: SELF (3) when the centre's mesh_id == group.mesh, else OTHER (4)
+ *   4  with a sensor, over the same window: a valid reading passes when (double)raw * unit >= z - scene_tol_m.  At least one
+ *      valid reading and none passing: SCENE (5).  No valid reading leaves the point where it was
+ *   5  with a mask and label != -2: the centre pixel fails the mask test: OFF_MASK (6)
+ *   6  otherwise VISIBLE (0)
+ * codes u8 [P]: every point of every group is written, points in no group are not touched.  counts i32 [G][8]: entry c is the
+ * number of the group's points with code c for c = 0..6, entry 7 is np; all entries are written on every call.  The counts are
+ * integer sums (ballot popcounts added up in LDS, then integer atomics behind an init kernel that is part of the call), so a
+ * group's row depends on its own points and maps alone, not on G, P, the order of the groups or the grid.
+ * Launches: the init kernel, then one point kernel per 64 views (the cameras travel as kernel arguments); no workspace.
+ *
+ * hm_mesh_coverage.  The mesh table, verts, faces, K_host and znear of hm_mesh_render, with its geometry and coverage rule word
+ * for word: the same faces are skipped, samples are pixel centres, the top-left rule applies.  labels i32 [n_meshes] on the
+ * device or NULL (no mask test; also without a mask).  Pixel p of mesh m's view is COVERED BY m when some non-skipped face of m
+ * covers its centre; a pixel counts once however many faces of m cover it, and other meshes play no part.
+ * counts i64 [n_meshes][8]:
+ *   0 amodal            covered by m
+ *   1 modal             covered by m and mesh_id == m
+ *   2 behind_other      covered by m and mesh_id names another mesh (>= 0, != m)
+ *   7 uncovered_in_map  covered by m and mesh_id < 0
+ * and the modal pixels split, in this order, into
+ *   4 scene             a valid reading with (double)raw * unit < (double)depth - scene_tol_m
+ *   6 off_mask          else: a mask and labels given, labels[m] != -2, and the pixel fails the mask test
+ *   3 clear             else
+ * Entry 5, unmeasured, counts the modal pixels with a sensor given and no valid reading; it is informational and not exclusive
+ * of entries 3 and 6.  Identities: amodal == modal + behind_other + uncovered_in_map, modal == clear + scene + off_mask.
+ * boxes i32 [n_meshes][8]: x1, y1, x2, y2 (inclusive) of the amodal pixels, then of the modal pixels; -1, -1, -1, -1 when there
+ * are none.  Pixels outside the frame count nowhere.  Both arrays are written whole on every call.
+ * Work items are (mesh, 16 x 16 tile) as in the renderers: setup per 48 meshes projects the corners to the rule's fixed point and
+ * lists the tiles of each mesh's clipped box; one kernel walks the list, one lane per pixel against the faces culled into LDS,
+ * and the workgroup adds ballot popcounts and sends integer atomics (64-bit add, 32-bit min and max).  No key buffer, no
+ * per-pixel output; three memsets (work counter, counts, boxes).  The sums are integers: a mesh's row depends on its own
+ * faces and maps alone.  H, W <= 32767.
+ *
+ * Both calls: asynchronous on `stream`, no host synchronisation, no allocation.  G == 0 / n_meshes == 0 succeeds and launches
+ * nothing.  HM_ERR_ARG, with a message naming the entry point, before any device work: a null required pointer, N, H or W < 1,
+ * N H W >= 2^31, window outside 0..2, znear (and with a sensor unit or scene_tol_m) not finite and > 0, raw_lo > raw_hi, a last
+ * row of K other than (0, 0, 1), a buffer not aligned (8 bytes: points, groups, verts, i64 counts, workspace; 4 bytes: depth,
+ * mesh_id, faces, labels, boxes, i32 counts; 2 bytes: sensor), a bad mesh table, a workspace that is too small.
+ * Measured on an MI355X (tools/bench_visibility.py, profiles/visibility_bench.log; per call, host submission included, 1080 x 1920,
+ * four meshes of 780 vertices and 1500 faces per frame, every vertex and 21 more points per mesh): 16 frames hm_point_visibility
+ * 0.042 ms and hm_mesh_coverage 0.300 ms next to 0.688 ms for the hm_mesh_render call of the same scene; 64 frames 0.321 ms and
+ * 1.050 ms next to 2.349 ms; a sensor and a mask change neither: DESIGN.md section 10.6. */
+enum { HM_VIS_VISIBLE = 0, HM_VIS_BEHIND = 1, HM_VIS_OUTSIDE = 2, HM_VIS_SELF = 3, HM_VIS_OTHER = 4, HM_VIS_SCENE = 5,
+       HM_VIS_OFF_MASK = 6 };
+typedef struct hm_vis_group { double tol_m; int32_t view, mesh, p0, np, label, reserved; } hm_vis_group;
+int hm_point_visibility(const float* depth, const int32_t* mesh_id, int N, int H, int W, const double* K_host, double znear,
+                        const double* points /* device [P][3] */, int P, const hm_vis_group* groups /* device [G] */, int G,
+                        int window, const uint16_t* sensor /* or NULL */, double unit, int raw_lo, int raw_hi, double scene_tol_m,
+                        const uint8_t* mask /* or NULL */, uint8_t* codes /* device [P] */, int32_t* counts /* device [G][8] */,
+                        void* stream);
+size_t hm_mesh_coverage_workspace_bytes(int N, int H, int W, int n_verts, int n_meshes, int n_faces);   /* 0 for illegal sizes */
+int hm_mesh_coverage(int N, int H, int W, const double* K_host, const double* verts, int n_verts, const int32_t* faces,
+                     int n_faces, const hm_mesh* meshes_host, int n_meshes, double znear, const float* depth,
+                     const int32_t* mesh_id, const uint16_t* sensor /* or NULL */, double unit, int raw_lo, int raw_hi,
+                     double scene_tol_m, const uint8_t* mask /* or NULL */, const int32_t* labels /* device [n_meshes] or NULL */,
+                     int64_t* counts /* device [n_meshes][8] */, int32_t* boxes /* device [n_meshes][8] */, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* ---- Detector evaluation (yolo/yolov7/test.py and utils/metrics.py): csrc/det_eval.hip.  The caller owns every buffer, the
  * calls are asynchronous on `stream`, nothing synchronises or allocates, argument errors return HM_ERR_ARG before any device
  * work.  All fp32 / fp64 arithmetic is plain IEEE in the order written (no FMA contraction, no fast-math).
