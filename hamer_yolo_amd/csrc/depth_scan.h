@@ -109,7 +109,6 @@ __device__ __forceinline__ void for_each_query(int pixel_q, Body&& body) {
   }
 }
 
-inline bool positive_finite(double v) { return v > 0.0 && v < INFINITY; }
 // The scan grid for `total` pixels: total >> 2 is an upper bound of the whole vectors.
 inline unsigned scan_blocks(long long total) { return (total >> 2) > 0 ? (unsigned)(((total >> 2) + VECS - 1) / VECS) : 1u; }
 

@@ -6,6 +6,9 @@
 int hm_set_error(int code, const char* msg);
 int hm_check_launch(const char* what);   // hipGetLastError() -> status
 
+// "a finite number > 0", as the argument checks of the entry points word it (not-a-number fails both comparisons)
+inline bool positive_finite(double v) { return v > 0.0 && v < __builtin_inf(); }
+
 // profiling hooks (prof.hip): push returns a record index or -1 when profiling is off
 int hm_prof_push(int kind, int epilogue, int M, int N, int K, hipStream_t s);
 void hm_prof_pop(int idx, hipStream_t s);

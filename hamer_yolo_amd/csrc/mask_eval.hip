@@ -7,14 +7,8 @@
 // Three kernels on the stream, no host synchronisation, no allocation:
 //   init   writes all 8 counts of every query: zeros and pixels = H * W (0 when the query's frame is outside 0..N-1; the other
 //          two kernels then skip the query, so nothing is read out of bounds).
-//   pack   one wave per (query, strip of 32 rows, 64-pixel word of a row).  Lane l reads pixel x = 64 c + l (clamped to W - 1:
-//          the replicated last column) of one row; __ballot turns the wave's 64 answers into one word of the pred image and one
-//          of the gt image.  Lane 63 also reads pixel 64 c + 64 (clamped), the east neighbour of the word's last pixel.  With
-//          the word of the next row (clamped to H - 1: the replicated last row) the boundary map is three XORs of whole words:
-//            b = ((s ^ east(s)) | (s ^ south) | (s ^ east(south))) & valid,   east(w) = (w >> 1) | (extra << 63).
-//          The two boundary words go to the workspace ([Q][2][H][ceil(W / 64)] uint64, bits at or past W are zero); areas,
-//          intersection and boundary counts are popcounts, added with one 64-bit atomic per wave and count when not zero.
-//          The south rows of 8 rows are loaded before any is used, so a wave has 16 row loads in flight.
+//   pack   the boundary pack of mask_bits.h, shared with mask_fit.hip, writes the two boundary maps to the workspace; on the way
+//          areas, intersection and boundary counts are popcounts, added with one 64-bit atomic per wave and count when not zero.
 //   match  one wave per (query, side, 64 consecutive words of that side's boundary map).  Lane i reads word i; the words that
 //          hold a boundary pixel are then taken one at a time by the whole wave, lane j owning the row offsets dy = j - r,
 //          j + 64 - r and j + 128 - r (2 r + 1 <= 129 of them): it
@@ -22,25 +16,18 @@
 //          with shift-and-OR doubling (the table of w comes from the host in integer arithmetic), and the OR over the lanes is
 //          the other boundary dilated by the disk, restricted to this word.  matched += popcount(word & that).  Most words hold
 //          no boundary pixel and cost one load.
-#include <stdint.h>
-#include <stdio.h>
 #include "common.h"
-#include "hamer_hip_internal.h"
+#include "mask_bits.h"
 
 namespace {
+using namespace mask_bits;
 
-constexpr int MK_MAX_RADIUS = 64, MK_STRIP = 32, MK_GROUP = 8, MK_THREADS = 256, MK_WAVES = MK_THREADS / 64;
-
-struct MaskParams {
-  const int32_t* pred; const uint8_t* mask; const hm_mask_query* queries;
-  int N, H, W, Q, r, words;                              // words = ceil(W / 64)
+struct MaskParams : Params {
   unsigned long long* counts;                            // [Q][8]
-  unsigned long long* bits;                              // [Q][2][H][words]
-  uint8_t hw[MK_MAX_RADIUS + 1];                         // hw[d] = floor(sqrt(r r - d d)) for d <= r
 };
 
-__global__ __launch_bounds__(MK_THREADS) void mask_init_kernel(const MaskParams p) {
-  const long long i = (long long)blockIdx.x * MK_THREADS + threadIdx.x;
+__global__ __launch_bounds__(THREADS) void mask_init_kernel(const MaskParams p) {
+  const long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
   if (i >= (long long)p.Q * 8) return;
   const int q = (int)(i >> 3), k = (int)(i & 7);
   const int frame = p.queries[q].frame;
@@ -48,79 +35,13 @@ __global__ __launch_bounds__(MK_THREADS) void mask_init_kernel(const MaskParams 
   p.counts[i] = (k == 7 && ok) ? (unsigned long long)p.H * (unsigned long long)p.W : 0ull;
 }
 
-// one row's words: the pred and gt answers of the wave's 64 pixels, and of the pixel east of the last one (bit 63 of e*)
-struct RowWords { unsigned long long p, g, ep, eg; };
-// what a lane reads of one row: its own pixel and, in lane 63 alone, the pixel east of the word
-struct RowPixels { int id, m, ide, me; };
-
-__device__ __forceinline__ RowPixels load_row(const int32_t* __restrict__ pr, const uint8_t* __restrict__ mk, int xc, int xe, bool last_lane) {
-  RowPixels v;
-  v.id = pr[xc]; v.m = (int)mk[xc]; v.ide = -1; v.me = 0;
-  if (last_lane) { v.ide = pr[xe]; v.me = (int)mk[xe]; }
-  return v;
-}
-
-__device__ __forceinline__ RowWords row_words(const RowPixels v, bool last_lane, int lo, int hi, int label) {
-  const bool ps = v.id >= lo && v.id < hi, gs = label == -1 ? v.m != 0 : v.m == label;
-  const bool pe = last_lane && v.ide >= lo && v.ide < hi, ge = last_lane && (label == -1 ? v.me != 0 : v.me == label);
-  RowWords w;
-  w.p = __ballot(ps); w.g = __ballot(gs);
-  w.ep = __ballot(pe) ? 1ull << 63 : 0ull;
-  w.eg = __ballot(ge) ? 1ull << 63 : 0ull;
-  return w;
-}
-
-__global__ __launch_bounds__(MK_THREADS) void mask_pack_kernel(const MaskParams p) {
-  const int lane = threadIdx.x & 63;
-  const bool last_lane = lane == 63;
-  const int strips = (p.H + MK_STRIP - 1) / MK_STRIP;
-  const long long per_query = (long long)strips * p.words;
-  const long long task = (long long)blockIdx.x * MK_WAVES + (threadIdx.x >> 6);
-  if (task >= per_query * p.Q) return;                                  // a whole wave leaves: nothing below synchronises
-  const int q = (int)(task / per_query);
-  const int rem = (int)(task - (long long)q * per_query);
-  const int strip = rem / p.words, c = rem - strip * p.words;
-  const hm_mask_query qu = p.queries[q];
-  if (qu.frame < 0 || qu.frame >= p.N) return;
-  const int x = c * 64 + lane;
-  const int xc = x < p.W ? x : p.W - 1, xe = c * 64 + 64 < p.W ? c * 64 + 64 : p.W - 1;
-  const unsigned long long valid = __ballot(x < p.W);
-  const size_t plane = (size_t)p.H * (size_t)p.W;
-  const int32_t* __restrict__ pr = p.pred + (size_t)qu.frame * plane;
-  const uint8_t* __restrict__ mk = p.mask + (size_t)qu.frame * plane;
-  unsigned long long* __restrict__ bp = p.bits + ((size_t)q * 2 + 0) * (size_t)p.H * p.words;
-  unsigned long long* __restrict__ bg = p.bits + ((size_t)q * 2 + 1) * (size_t)p.H * p.words;
-  const int y0 = strip * MK_STRIP, y_end = y0 + MK_STRIP < p.H ? y0 + MK_STRIP : p.H;
+__global__ __launch_bounds__(THREADS) void mask_pack_kernel(const MaskParams p) {
   unsigned long long inter = 0, pa = 0, ga = 0, pb = 0, gb = 0;
-  RowWords cur = row_words(load_row(pr + (size_t)y0 * p.W, mk + (size_t)y0 * p.W, xc, xe, last_lane), last_lane, qu.id_lo, qu.id_hi, qu.label);
-  for (int yb = y0; yb < y_end; yb += MK_GROUP) {
-    // the south rows of MK_GROUP rows are read before any is used: the loads of a group are in flight together.  A row index is
-    // clamped to H - 1, so the last row's south neighbour is itself and no load leaves the image
-    RowPixels south[MK_GROUP];
-#pragma unroll
-    for (int k = 0; k < MK_GROUP; ++k) {
-      const int ys = yb + 1 + k < p.H ? yb + 1 + k : p.H - 1;
-      south[k] = load_row(pr + (size_t)ys * p.W, mk + (size_t)ys * p.W, xc, xe, last_lane);
-    }
-#pragma unroll
-    for (int k = 0; k < MK_GROUP; ++k) {
-      const int y = yb + k;
-      if (y >= y_end) break;
-      const RowWords nxt = row_words(south[k], last_lane, qu.id_lo, qu.id_hi, qu.label);
-      const unsigned long long pe = (cur.p >> 1) | cur.ep, pse = (nxt.p >> 1) | nxt.ep;
-      const unsigned long long ge = (cur.g >> 1) | cur.eg, gse = (nxt.g >> 1) | nxt.eg;
-      const unsigned long long bpw = ((cur.p ^ pe) | (cur.p ^ nxt.p) | (cur.p ^ pse)) & valid;
-      const unsigned long long bgw = ((cur.g ^ ge) | (cur.g ^ nxt.g) | (cur.g ^ gse)) & valid;
-      if (lane == 0) {
-        bp[(size_t)y * p.words + c] = bpw;
-        bg[(size_t)y * p.words + c] = bgw;
-      }
-      inter += __popcll(cur.p & cur.g & valid); pa += __popcll(cur.p & valid); ga += __popcll(cur.g & valid);
-      pb += __popcll(bpw); gb += __popcll(bgw);
-      cur = nxt;
-    }
-  }
-  if (lane == 0) {
+  const int q = pack_strips(p, [&](const RowWords& cur, unsigned long long bpw, unsigned long long bgw, unsigned long long valid) {
+    inter += __popcll(cur.p & cur.g & valid); pa += __popcll(cur.p & valid); ga += __popcll(cur.g & valid);
+    pb += __popcll(bpw); gb += __popcll(bgw);
+  });
+  if (q >= 0 && (threadIdx.x & 63) == 0) {
     unsigned long long* cnt = p.counts + (size_t)q * 8;
     if (inter) atomicAdd(cnt + 0, inter);
     if (pa) atomicAdd(cnt + 1, pa);
@@ -152,11 +73,11 @@ __device__ __forceinline__ unsigned long long dilate_word(unsigned long long bel
   return uh | dl;
 }
 
-__global__ __launch_bounds__(MK_THREADS) void mask_match_kernel(const MaskParams p) {
+__global__ __launch_bounds__(THREADS) void mask_match_kernel(const MaskParams p) {
   const int lane = threadIdx.x & 63;
   const long long items = (long long)p.H * p.words;
   const long long chunks = (items + 63) / 64;
-  const long long task = (long long)blockIdx.x * MK_WAVES + (threadIdx.x >> 6);
+  const long long task = (long long)blockIdx.x * WAVES + (threadIdx.x >> 6);
   if (task >= chunks * 2 * p.Q) return;
   const int q = (int)(task / (chunks * 2));
   const long long rem = task - (long long)q * chunks * 2;
@@ -203,52 +124,37 @@ __global__ __launch_bounds__(MK_THREADS) void mask_match_kernel(const MaskParams
   if (lane == 0 && matched) atomicAdd(p.counts + (size_t)q * 8 + 5 + side, matched);
 }
 
-long long mask_words(int W) { return ((long long)W + 63) / 64; }
-
 }  // namespace
 
 extern "C" size_t hm_mask_score_workspace_bytes(int Q, int H, int W, int radius) {
-  if (Q < 0 || H < 1 || W < 1 || radius < 0 || radius > MK_MAX_RADIUS) return 0;
-  const size_t per_query = (size_t)2 * (size_t)H * (size_t)mask_words(W) * sizeof(unsigned long long);
-  return (size_t)(Q < 1 ? 1 : Q) * per_query;                            // never 0 for legal sizes: Q == 0 asks for one query's
+  if (Q < 0 || H < 1 || W < 1 || radius < 0 || radius > MAX_RADIUS) return 0;
+  return map_words(Q < 1 ? 1 : Q, H, W) * sizeof(unsigned long long);    // never 0 for legal sizes: Q == 0 asks for one query's
 }
 
 extern "C" int hm_mask_score(const int32_t* pred_id, const uint8_t* mask, int N, int H, int W, const hm_mask_query* queries, int Q,
                              int radius, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream_) {
-  if (N < 1 || H < 1 || W < 1) return hm_set_error(HM_ERR_ARG, "hm_mask_score: N, H and W must be positive");
-  if ((long long)N * H * W >= (1ll << 31)) return hm_set_error(HM_ERR_ARG, "hm_mask_score: N * H * W must be below 2^31");
-  if (radius < 0 || radius > MK_MAX_RADIUS) return hm_set_error(HM_ERR_ARG, "hm_mask_score: radius must be in 0..64");
-  if (Q < 0) return hm_set_error(HM_ERR_ARG, "hm_mask_score: Q must not be negative");
-  if (!pred_id || !mask) return hm_set_error(HM_ERR_ARG, "hm_mask_score: null pred_id or mask");
-  if (Q == 0) return HM_OK;                                              // nothing to score: no launch, nothing else is read
-  if (!queries || !counts || !workspace) return hm_set_error(HM_ERR_ARG, "hm_mask_score: null queries, counts or workspace");
-  if (workspace_bytes < hm_mask_score_workspace_bytes(Q, H, W, radius))
-    return hm_set_error(HM_ERR_ARG, "hm_mask_score: workspace too small (hm_mask_score_workspace_bytes)");
-  if (((uintptr_t)counts & 7) || ((uintptr_t)workspace & 7) || ((uintptr_t)pred_id & 3) || ((uintptr_t)queries & 3))
-    return hm_set_error(HM_ERR_ARG, "hm_mask_score: counts and workspace must be 8-byte aligned, pred_id and queries 4-byte");
   MaskParams p;
   p.pred = pred_id; p.mask = mask; p.queries = queries;
-  p.N = N; p.H = H; p.W = W; p.Q = Q; p.r = radius; p.words = (int)mask_words(W);
+  p.N = N; p.H = H; p.W = W; p.Q = Q; p.r = radius;
   p.counts = (unsigned long long*)counts; p.bits = (unsigned long long*)workspace;
-  for (int d = 0; d <= MK_MAX_RADIUS; ++d) {
-    int w = 0;
-    if (d <= radius) while ((w + 1) * (w + 1) + d * d <= radius * radius) ++w;
-    p.hw[d] = (uint8_t)w;
-  }
-  const long long strips = (H + MK_STRIP - 1) / MK_STRIP;
-  const long long pack_blocks = ((long long)Q * strips * p.words + MK_WAVES - 1) / MK_WAVES;
+  const char* buffers = (!queries || !counts || !workspace) ? "null queries, counts or workspace"
+      : workspace_bytes < hm_mask_score_workspace_bytes(Q, H, W, radius) ? "workspace too small (hm_mask_score_workspace_bytes)"
+      : (((uintptr_t)counts & 7) || ((uintptr_t)workspace & 7) || ((uintptr_t)pred_id & 3) || ((uintptr_t)queries & 3))
+          ? "counts and workspace must be 8-byte aligned, pred_id and queries 4-byte" : nullptr;
+  int rc = host_checks("hm_mask_score", p, nullptr, buffers);
+  if (rc != HM_OK || Q == 0) return rc;                                  // no query, nothing to score: no launch
   const long long chunks = ((long long)H * p.words + 63) / 64;
-  const long long match_blocks = ((long long)Q * 2 * chunks + MK_WAVES - 1) / MK_WAVES;
-  if (pack_blocks > 0x7fffffffll || match_blocks > 0x7fffffffll)
+  const long long match_blocks = ((long long)Q * 2 * chunks + WAVES - 1) / WAVES;
+  if (pack_blocks(p) > 0x7fffffffll || match_blocks > 0x7fffffffll)
     return hm_set_error(HM_ERR_ARG, "hm_mask_score: Q * H * W too large for one call");
   hipStream_t s = (hipStream_t)stream_;
   HmProfScope prof(HM_K_OTHER, 2, Q, H, W, s);
-  hipLaunchKernelGGL(mask_init_kernel, dim3((unsigned)(((long long)Q * 8 + MK_THREADS - 1) / MK_THREADS)), dim3(MK_THREADS), 0, s, p);
-  int rc = hm_check_launch("hm_mask_score (init)");
+  hipLaunchKernelGGL(mask_init_kernel, dim3((unsigned)(((long long)Q * 8 + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, p);
+  rc = hm_check_launch("hm_mask_score (init)");
   if (rc != HM_OK) return rc;
-  hipLaunchKernelGGL(mask_pack_kernel, dim3((unsigned)pack_blocks), dim3(MK_THREADS), 0, s, p);
+  hipLaunchKernelGGL(mask_pack_kernel, dim3((unsigned)pack_blocks(p)), dim3(THREADS), 0, s, p);
   rc = hm_check_launch("hm_mask_score (pack)");
   if (rc != HM_OK) return rc;
-  hipLaunchKernelGGL(mask_match_kernel, dim3((unsigned)match_blocks), dim3(MK_THREADS), 0, s, p);
+  hipLaunchKernelGGL(mask_match_kernel, dim3((unsigned)match_blocks), dim3(THREADS), 0, s, p);
   return hm_check_launch("hm_mask_score (match)");
 }

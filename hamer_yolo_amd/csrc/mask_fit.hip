@@ -9,13 +9,11 @@
 // below) and every expression is written in the rule's order.
 //
 // Four kernels on the stream, no host synchronisation, no allocation.  The workspace holds the boundary maps, [Q][2][H]
-// [ceil(W / 64)] uint64 with one bit per pixel (the layout of mask_eval.hip; bits at or past W are zero), followed by one row of
-// 32 int64 per query where the sums are added up: 18 sums, 2 x 6 counts, 2 unused.
+// [ceil(W / 64)] uint64 with one bit per pixel (mask_bits.h, shared with mask_eval.hip; bits at or past W are zero), followed by
+// one row of 32 int64 per query where the sums are added up: 18 sums, 2 x 6 counts, 2 unused.
 //   init   zeroes the rows of sums and counts.  The boundary maps need no clearing: pack writes every word of every query whose
 //          frame is inside the batch, and the maps of the other queries are never read.
-//   pack   one wave per (query, strip of 32 rows, 64-pixel word of a row), as in mask_eval.hip: lane l reads pixel x = 64 c + l
-//          (clamped to W - 1), __ballot makes the words, lane 63 also reads the pixel east of the word, and with the south row
-//          the boundary map is three XORs of whole words.
+//   pack   the boundary pack of mask_bits.h and nothing else.
 //   match  one workgroup per (query, direction, tile of 32 rows x one 64-pixel word) of the direction's OWN boundary map.  A tile
 //          without a boundary pixel -- nearly all of them -- costs one load per row.  Otherwise the 32 + 2 r rows x 3 words of the
 //          OTHER map that the tile's discs can reach go to LDS, the tile's set bits are compacted into a queue in LDS (a row's
@@ -29,105 +27,40 @@
 //   solve  one thread per query: copies its row to sums and counts, builds M, factorises and solves in the header's order.
 #include <limits.h>
 #include <math.h>
-#include <stdint.h>
 #include "common.h"
-#include "hamer_hip_internal.h"
+#include "mask_bits.h"
 
 #pragma clang fp contract(off)
 
 namespace {
+using namespace mask_bits;
 
-constexpr int MF_MAX_RADIUS = 64, MF_MAX_REACH = 4096, MF_STRIP = 32, MF_GROUP = 8, MF_THREADS = 256, MF_WAVES = MF_THREADS / 64;
+constexpr int MF_MAX_REACH = 4096;
 constexpr int MF_TILE = 32;                               // rows of a match tile
-constexpr int MF_ROWS = MF_TILE + 2 * MF_MAX_RADIUS;      // rows of the other map a tile can reach
+constexpr int MF_ROWS = MF_TILE + 2 * MAX_RADIUS;         // rows of the other map a tile can reach
 constexpr int MF_SUMS = 18, MF_COUNTS = 12, MF_CELLS = 32;
 constexpr int MF_LOCAL = MF_SUMS + 5;                     // what a workgroup gathers: the sums and its direction's five counts
 constexpr double MF_SCALE = 1048576.0, MF_INV_SCALE = 1.0 / 1048576.0;        // 2^20 and 2^-20: exact
 enum { MF_NONE = 0, MF_LINE = 1, MF_ANCHOR = 2, MF_UNMATCHED = 3, MF_OUT = 4 };
 
-struct MaskFitParams {
-  const int32_t* pred; const uint8_t* mask; const hm_mask_query* queries; const int32_t* centre;
-  int N, H, W, Q, r, words, reach, directions, min_pixels, tiles;     // words = ceil(W / 64), tiles = ceil(H / MF_TILE)
+struct MaskFitParams : Params {
+  const int32_t* centre;
+  int reach, directions, min_pixels, tiles;               // tiles = ceil(H / MF_TILE)
   double damping, lever2;
-  unsigned long long* bits;                               // [Q][2][H][words]
   unsigned long long* acc;                                // [Q][32]
   long long* sums;                                        // [Q][18]
   long long* counts;                                      // [Q][2][6]
   double* solution;                                       // [Q][8]
-  uint8_t hw[MF_MAX_RADIUS + 1];                          // hw[d] = floor(sqrt(r r - d d)) for d <= r
 };
 
-__global__ __launch_bounds__(MF_THREADS) void mfit_init_kernel(const MaskFitParams p) {
-  const long long i = (long long)blockIdx.x * MF_THREADS + threadIdx.x;
+__global__ __launch_bounds__(THREADS) void mfit_init_kernel(const MaskFitParams p) {
+  const long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
   if (i < (long long)p.Q * MF_CELLS) p.acc[i] = 0ull;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ pack
-struct RowWords { unsigned long long p, g, ep, eg; };     // a row's pred and gt words and the pixel east of each (bit 63)
-struct RowPixels { int id, m, ide, me; };                 // what a lane reads of a row; lane 63 alone the pixel east of the word
-
-__device__ __forceinline__ RowPixels load_row(const int32_t* __restrict__ pr, const uint8_t* __restrict__ mk, int xc, int xe, bool last_lane) {
-  RowPixels v;
-  v.id = pr[xc]; v.m = (int)mk[xc]; v.ide = -1; v.me = 0;
-  if (last_lane) { v.ide = pr[xe]; v.me = (int)mk[xe]; }
-  return v;
-}
-
-__device__ __forceinline__ RowWords row_words(const RowPixels v, bool last_lane, int lo, int hi, int label) {
-  const bool ps = v.id >= lo && v.id < hi, gs = label == -1 ? v.m != 0 : v.m == label;
-  const bool pe = last_lane && v.ide >= lo && v.ide < hi, ge = last_lane && (label == -1 ? v.me != 0 : v.me == label);
-  RowWords w;
-  w.p = __ballot(ps); w.g = __ballot(gs);
-  w.ep = __ballot(pe) ? 1ull << 63 : 0ull;
-  w.eg = __ballot(ge) ? 1ull << 63 : 0ull;
-  return w;
-}
-
-__global__ __launch_bounds__(MF_THREADS) void mfit_pack_kernel(const MaskFitParams p) {
-  const int lane = threadIdx.x & 63;
-  const bool last_lane = lane == 63;
-  const int strips = (p.H + MF_STRIP - 1) / MF_STRIP;
-  const long long per_query = (long long)strips * p.words;
-  const long long task = (long long)blockIdx.x * MF_WAVES + (threadIdx.x >> 6);
-  if (task >= per_query * p.Q) return;                                  // a whole wave leaves: nothing below synchronises
-  const int q = (int)(task / per_query);
-  const int rem = (int)(task - (long long)q * per_query);
-  const int strip = rem / p.words, c = rem - strip * p.words;
-  const hm_mask_query qu = p.queries[q];
-  if (qu.frame < 0 || qu.frame >= p.N) return;
-  const int x = c * 64 + lane;
-  const int xc = x < p.W ? x : p.W - 1, xe = c * 64 + 64 < p.W ? c * 64 + 64 : p.W - 1;
-  const unsigned long long valid = __ballot(x < p.W);
-  const size_t plane = (size_t)p.H * (size_t)p.W;
-  const int32_t* __restrict__ pr = p.pred + (size_t)qu.frame * plane;
-  const uint8_t* __restrict__ mk = p.mask + (size_t)qu.frame * plane;
-  unsigned long long* __restrict__ bp = p.bits + ((size_t)q * 2 + 0) * (size_t)p.H * p.words;
-  unsigned long long* __restrict__ bg = p.bits + ((size_t)q * 2 + 1) * (size_t)p.H * p.words;
-  const int y0 = strip * MF_STRIP, y_end = y0 + MF_STRIP < p.H ? y0 + MF_STRIP : p.H;
-  RowWords cur = row_words(load_row(pr + (size_t)y0 * p.W, mk + (size_t)y0 * p.W, xc, xe, last_lane), last_lane, qu.id_lo, qu.id_hi, qu.label);
-  for (int yb = y0; yb < y_end; yb += MF_GROUP) {
-    // the south rows of MF_GROUP rows are read before any is used; a row index is clamped to H - 1, so the last row's south
-    // neighbour is itself and no load leaves the image
-    RowPixels south[MF_GROUP];
-#pragma unroll
-    for (int k = 0; k < MF_GROUP; ++k) {
-      const int ys = yb + 1 + k < p.H ? yb + 1 + k : p.H - 1;
-      south[k] = load_row(pr + (size_t)ys * p.W, mk + (size_t)ys * p.W, xc, xe, last_lane);
-    }
-#pragma unroll
-    for (int k = 0; k < MF_GROUP; ++k) {
-      const int y = yb + k;
-      if (y >= y_end) break;
-      const RowWords nxt = row_words(south[k], last_lane, qu.id_lo, qu.id_hi, qu.label);
-      const unsigned long long pe = (cur.p >> 1) | cur.ep, pse = (nxt.p >> 1) | nxt.ep;
-      const unsigned long long ge = (cur.g >> 1) | cur.eg, gse = (nxt.g >> 1) | nxt.eg;
-      if (lane == 0) {
-        bp[(size_t)y * p.words + c] = ((cur.p ^ pe) | (cur.p ^ nxt.p) | (cur.p ^ pse)) & valid;
-        bg[(size_t)y * p.words + c] = ((cur.g ^ ge) | (cur.g ^ nxt.g) | (cur.g ^ gse)) & valid;
-      }
-      cur = nxt;
-    }
-  }
+__global__ __launch_bounds__(THREADS) void mfit_pack_kernel(const MaskFitParams p) {
+  pack_strips(p, [](const RowWords&, unsigned long long, unsigned long long, unsigned long long) {});
 }
 
 // ----------------------------------------------------------------------------------------------------------------- match
@@ -137,7 +70,7 @@ struct MatchLds {
   unsigned long long acc[MF_LOCAL + 1];
   int base[MF_TILE + 1];                                  // set bits in the rows before a row
   unsigned short queue[MF_TILE * 64];                     // row << 6 | bit of every boundary pixel of the tile, row-major
-  uint8_t hw[MF_MAX_RADIUS + 1];
+  uint8_t hw[MAX_RADIUS + 1];
 };
 
 __device__ __forceinline__ long long wave_sum(long long v) {
@@ -165,7 +98,7 @@ __device__ __forceinline__ bool nearest_in_row(unsigned long long lo, unsigned l
   return true;
 }
 
-__global__ __launch_bounds__(MF_THREADS) void mfit_match_kernel(const MaskFitParams p) {
+__global__ __launch_bounds__(THREADS) void mfit_match_kernel(const MaskFitParams p) {
   __shared__ MatchLds s;
   const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
   long long b = (long long)blockIdx.x;
@@ -181,7 +114,7 @@ __global__ __launch_bounds__(MF_THREADS) void mfit_match_kernel(const MaskFitPar
   const int y0 = tile * MF_TILE, r = p.r;
   if (t < MF_TILE) s.mine[t] = y0 + t < p.H ? mine[(size_t)(y0 + t) * p.words + c] : 0ull;
   if (t <= MF_LOCAL) s.acc[t] = 0ull;
-  if (t <= MF_MAX_RADIUS) s.hw[t] = p.hw[t];
+  if (t <= MAX_RADIUS) s.hw[t] = p.hw[t];
   __syncthreads();
   unsigned long long any = 0ull;
 #pragma unroll
@@ -189,7 +122,7 @@ __global__ __launch_bounds__(MF_THREADS) void mfit_match_kernel(const MaskFitPar
   if (any == 0ull) return;                                              // the same for every thread: no boundary pixel in the tile
 
   const int rows = MF_TILE + 2 * r;
-  for (int i = t; i < rows * 3; i += MF_THREADS) {
+  for (int i = t; i < rows * 3; i += THREADS) {
     const int rr = i / 3, k = i - rr * 3;
     const int yy = y0 - r + rr, cc = c - 1 + k;
     s.other[rr][k] = (yy >= 0 && yy < p.H && cc >= 0 && cc < p.words) ? other[(size_t)yy * p.words + cc] : 0ull;
@@ -201,8 +134,8 @@ __global__ __launch_bounds__(MF_THREADS) void mfit_match_kernel(const MaskFitPar
   }
   __syncthreads();
 #pragma unroll
-  for (int i = 0; i < MF_TILE / MF_WAVES; ++i) {
-    const int row = i * MF_WAVES + wave;
+  for (int i = 0; i < MF_TILE / WAVES; ++i) {
+    const int row = i * WAVES + wave;
     const unsigned long long a = s.mine[row];
     if ((a >> lane) & 1ull) s.queue[s.base[row] + __popcll(a & ((1ull << lane) - 1ull))] = (unsigned short)((row << 6) | lane);
   }
@@ -211,7 +144,7 @@ __global__ __launch_bounds__(MF_THREADS) void mfit_match_kernel(const MaskFitPar
   const long long cx = (long long)p.centre[(size_t)q * 2], cy = (long long)p.centre[(size_t)q * 2 + 1];
   const long long reach = (long long)p.reach, reach2 = reach * reach;
 
-  for (int e0 = wave * 64; e0 < total; e0 += MF_THREADS) {              // wave-uniform: the whole wave shuffles below
+  for (int e0 = wave * 64; e0 < total; e0 += THREADS) {              // wave-uniform: the whole wave shuffles below
     const bool active = e0 + lane < total;
     int where = MF_NONE, best = INT_MAX, bdx = 0, bdy = 0, row = 0, bit = 0;
     if (active) {
@@ -363,65 +296,51 @@ __global__ __launch_bounds__(64) void mfit_solve_kernel(const MaskFitParams p) {
   out[6] = 0.0; out[7] = 0.0;
 }
 
-long long fit_words(int W) { return ((long long)W + 63) / 64; }
-
 }  // namespace
 
 extern "C" size_t hm_mask_fit_workspace_bytes(int Q, int H, int W, int radius) {
-  if (Q < 0 || H < 1 || W < 1 || radius < 0 || radius > MF_MAX_RADIUS) return 0;
-  const size_t per_query = ((size_t)2 * (size_t)H * (size_t)fit_words(W) + MF_CELLS) * sizeof(unsigned long long);
-  return (size_t)(Q < 1 ? 1 : Q) * per_query;                            // never 0 for legal sizes: Q == 0 asks for one query's
+  if (Q < 0 || H < 1 || W < 1 || radius < 0 || radius > MAX_RADIUS) return 0;
+  const size_t n = (size_t)(Q < 1 ? 1 : Q);                              // never 0 for legal sizes: Q == 0 asks for one query's
+  return (map_words((int)n, H, W) + n * MF_CELLS) * sizeof(unsigned long long);
 }
 
 extern "C" int hm_mask_fit(const int32_t* pred_id, const uint8_t* mask, int N, int H, int W, const hm_mask_query* queries, int Q,
                            const int32_t* centre, int radius, int reach_px, int directions, double damping, double lever_px,
                            int min_pixels, int64_t* sums, int64_t* counts, double* solution, void* workspace,
                            size_t workspace_bytes, void* stream_) {
-  if (N < 1 || H < 1 || W < 1) return hm_set_error(HM_ERR_ARG, "hm_mask_fit: N, H and W must be positive");
-  if ((long long)N * H * W >= (1ll << 31)) return hm_set_error(HM_ERR_ARG, "hm_mask_fit: N * H * W must be below 2^31");
-  if (radius < 0 || radius > MF_MAX_RADIUS) return hm_set_error(HM_ERR_ARG, "hm_mask_fit: radius must be in 0..64");
-  if (reach_px < 1 || reach_px > MF_MAX_REACH) return hm_set_error(HM_ERR_ARG, "hm_mask_fit: reach_px must be in 1..4096");
-  if (directions < 1 || directions > 3) return hm_set_error(HM_ERR_ARG, "hm_mask_fit: directions must be 1, 2 or 3");
-  if (!(damping >= 0.0 && damping < INFINITY)) return hm_set_error(HM_ERR_ARG, "hm_mask_fit: damping must be a finite number >= 0");
-  if (!(lever_px > 0.0 && lever_px < INFINITY)) return hm_set_error(HM_ERR_ARG, "hm_mask_fit: lever_px must be a finite number > 0");
-  if (min_pixels < 1) return hm_set_error(HM_ERR_ARG, "hm_mask_fit: min_pixels must be at least 1");
-  if (Q < 0) return hm_set_error(HM_ERR_ARG, "hm_mask_fit: Q must not be negative");
-  if (!pred_id || !mask) return hm_set_error(HM_ERR_ARG, "hm_mask_fit: null pred_id or mask");
-  if (Q == 0) return HM_OK;                                              // nothing to fit: no launch, nothing else is read
-  if (!queries || !centre || !sums || !counts || !solution || !workspace)
-    return hm_set_error(HM_ERR_ARG, "hm_mask_fit: null queries, centre, sums, counts, solution or workspace");
-  if (workspace_bytes < hm_mask_fit_workspace_bytes(Q, H, W, radius))
-    return hm_set_error(HM_ERR_ARG, "hm_mask_fit: workspace too small (hm_mask_fit_workspace_bytes)");
-  if (((uintptr_t)sums & 7) || ((uintptr_t)counts & 7) || ((uintptr_t)solution & 7) || ((uintptr_t)workspace & 7) ||
-      ((uintptr_t)pred_id & 3) || ((uintptr_t)queries & 3) || ((uintptr_t)centre & 3))
-    return hm_set_error(HM_ERR_ARG, "hm_mask_fit: sums, counts, solution and workspace must be 8-byte aligned, pred_id, queries and centre 4-byte");
   MaskFitParams p;
   p.pred = pred_id; p.mask = mask; p.queries = queries; p.centre = centre;
-  p.N = N; p.H = H; p.W = W; p.Q = Q; p.r = radius; p.words = (int)fit_words(W); p.reach = reach_px; p.directions = directions;
-  p.min_pixels = min_pixels; p.tiles = (H + MF_TILE - 1) / MF_TILE;
-  p.damping = damping; p.lever2 = lever_px * lever_px;
+  p.N = N; p.H = H; p.W = W; p.Q = Q; p.r = radius; p.reach = reach_px; p.directions = directions;
+  p.min_pixels = min_pixels; p.damping = damping; p.lever2 = lever_px * lever_px;
   p.bits = (unsigned long long*)workspace;
-  p.acc = p.bits + (size_t)Q * 2 * (size_t)H * (size_t)p.words;
   p.sums = (long long*)sums; p.counts = (long long*)counts; p.solution = solution;
-  for (int d = 0; d <= MF_MAX_RADIUS; ++d) {
-    int w = 0;
-    if (d <= radius) while ((w + 1) * (w + 1) + d * d <= radius * radius) ++w;
-    p.hw[d] = (uint8_t)w;
-  }
-  const long long strips = (H + MF_STRIP - 1) / MF_STRIP;
-  const long long pack_blocks = ((long long)Q * strips * p.words + MF_WAVES - 1) / MF_WAVES;
+  const char* scalars = (reach_px < 1 || reach_px > MF_MAX_REACH) ? "reach_px must be in 1..4096"
+      : (directions < 1 || directions > 3)        ? "directions must be 1, 2 or 3"
+      : !(damping >= 0.0 && damping < INFINITY)   ? "damping must be a finite number >= 0"
+      : !positive_finite(lever_px)                ? "lever_px must be a finite number > 0"
+      : min_pixels < 1                            ? "min_pixels must be at least 1" : nullptr;
+  const char* buffers = (!queries || !centre || !sums || !counts || !solution || !workspace)
+          ? "null queries, centre, sums, counts, solution or workspace"
+      : workspace_bytes < hm_mask_fit_workspace_bytes(Q, H, W, radius) ? "workspace too small (hm_mask_fit_workspace_bytes)"
+      : (((uintptr_t)sums & 7) || ((uintptr_t)counts & 7) || ((uintptr_t)solution & 7) || ((uintptr_t)workspace & 7) ||
+         ((uintptr_t)pred_id & 3) || ((uintptr_t)queries & 3) || ((uintptr_t)centre & 3))
+          ? "sums, counts, solution and workspace must be 8-byte aligned, pred_id, queries and centre 4-byte" : nullptr;
+  int rc = host_checks("hm_mask_fit", p, scalars, buffers);
+  if (rc != HM_OK || Q == 0) return rc;                                  // no query, nothing to fit: no launch
+  p.tiles = (H + MF_TILE - 1) / MF_TILE;
+  p.acc = p.bits + map_words(Q, H, W);
   const long long match_blocks = (long long)Q * 2 * p.tiles * p.words;
-  if (pack_blocks > 0x7fffffffll || match_blocks > 0x7fffffffll)
+  if (pack_blocks(p) > 0x7fffffffll || match_blocks > 0x7fffffffll)
     return hm_set_error(HM_ERR_ARG, "hm_mask_fit: Q * H * W too large for one call");
   hipStream_t s = (hipStream_t)stream_;
   HmProfScope prof(HM_K_OTHER, 10, Q, H, W, s);
-  hipLaunchKernelGGL(mfit_init_kernel, dim3((unsigned)(((long long)Q * MF_CELLS + MF_THREADS - 1) / MF_THREADS)), dim3(MF_THREADS), 0, s, p);
-  int rc = hm_check_launch("hm_mask_fit (init)");
+  hipLaunchKernelGGL(mfit_init_kernel, dim3((unsigned)(((long long)Q * MF_CELLS + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, p);
+  rc = hm_check_launch("hm_mask_fit (init)");
   if (rc != HM_OK) return rc;
-  hipLaunchKernelGGL(mfit_pack_kernel, dim3((unsigned)pack_blocks), dim3(MF_THREADS), 0, s, p);
+  hipLaunchKernelGGL(mfit_pack_kernel, dim3((unsigned)pack_blocks(p)), dim3(THREADS), 0, s, p);
   rc = hm_check_launch("hm_mask_fit (pack)");
   if (rc != HM_OK) return rc;
-  hipLaunchKernelGGL(mfit_match_kernel, dim3((unsigned)match_blocks), dim3(MF_THREADS), 0, s, p);
+  hipLaunchKernelGGL(mfit_match_kernel, dim3((unsigned)match_blocks), dim3(THREADS), 0, s, p);
   rc = hm_check_launch("hm_mask_fit (match)");
   if (rc != HM_OK) return rc;
   hipLaunchKernelGGL(mfit_solve_kernel, dim3((unsigned)((Q + 63) / 64)), dim3(64), 0, s, p);

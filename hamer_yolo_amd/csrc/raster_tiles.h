@@ -4,7 +4,8 @@
 // winning 64-bit key to the view's key buffer; a last pass takes the keys and leaves the buffer as it found it.
 // Nothing in this header does floating-point arithmetic that could be contracted (rint_u8 only rounds and compares).  Every
 // fp32 / fp64 expression of a drawing rule -- projection, depth, shading, blend -- stays in its own file under that file's
-// `#pragma clang fp contract(off)`, which is what keeps the bytes equal to the numpy rules.
+// `#pragma clang fp contract(off)`, which is what keeps the bytes equal to the numpy rules (zbuffer_faces.h, which builds on
+// this header, holds the one projection two files share and says why).
 // The skeleton kernels use TILE, align256, the item packing and the tile-overlap predicate only: their per-tile flag claim
 // and their one-wave cull are different algorithms.
 #pragma once

@@ -2,12 +2,11 @@
 // mesh, both against the depth and label maps hm_mesh_render writes, and optionally a sensor depth map and a label mask.
 // The rules are stated in include/hamer_hip.h ("Visibility"); tests/visibility_rule.py restates them in numpy.
 //  * hm_point_visibility - an init kernel writes every group's count row (zeros and np); the point kernel runs one lane per
-//                point over the (group, 256-point chunk) items, found by a scan of the group table: the fp64 projection of
-//                hm_mesh_render restated from the written rule, the window tests, one code byte per point; the counts are
-//                ballot popcounts added up in LDS, then one integer atomic per occupied code and chunk.  The cameras travel
-//                as kernel arguments, 64 views per launch.
-//  * hm_mesh_coverage - the renderer's setup without depth (per face the fixed-point corners, the validity tests, the winding
-//                swap, the ownership bits, the clipped pixel box; the mesh's box cut into 16 x 16 tiles on a work list), then
+//                point over the (group, 256-point chunk) items, found by a scan of the group table: the renderer's projection
+//                (zbuffer_faces.h), the window tests, one code byte per point; the counts are ballot popcounts added up in
+//                LDS, then one integer atomic per occupied code and chunk.  The cameras travel as kernel arguments, 64 views
+//                per launch.
+//  * hm_mesh_coverage - the renderer's face setup and sample test (zbuffer_faces.h), of which only the geometry is kept, then
 //                one pass over the work list: per (mesh, tile) the faces are culled into LDS, one lane per pixel decides "any
 //                face of the mesh covers my centre", classifies the pixel against the maps, and the workgroup sends ballot
 //                popcounts (64-bit adds) and the boxes' corners (32-bit min / max).  No key buffer, no per-pixel output.
@@ -15,15 +14,15 @@
 #include <math.h>
 #include "common.h"
 #include "raster_tiles.h"
+#include "zbuffer_faces.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 using namespace raster_tiles;
+using namespace zbuffer_faces;
 
 constexpr int VIEWS_PER_LAUNCH = 64;               // 64 cameras of six doubles: the argument block stays under 4 KiB
-constexpr int MESHES_PER_LAUNCH = 48;              // as the renderer's setup
-constexpr int F_SMALL = 1, F_OWN0 = 2, F_OWN1 = 4, F_OWN2 = 8;
 enum { VIS_VISIBLE = 0, VIS_BEHIND, VIS_OUTSIDE, VIS_SELF, VIS_OTHER, VIS_SCENE, VIS_OFF_MASK };
 
 struct VisCameras {
@@ -63,11 +62,8 @@ __device__ __forceinline__ int point_code(const hm_vis_group& g, const double* _
   const double x = pt[0], y = pt[1], z = pt[2];
   if (!(z >= znear)) return VIS_BEHIND;
   if (g.view < 0 || g.view >= m.N) return VIS_OUTSIDE;
-  const double* k = cam.k[g.view - cam.first];
-  const double u = ((k[0] * x + k[1] * y) + k[2] * z) / z;
-  const double v = ((k[3] * x + k[4] * y) + k[5] * z) / z;
-  if (!(fabs(u) < 65536.0) || !(fabs(v) < 65536.0)) return VIS_OUTSIDE;
-  const int X = (int)rint(256.0 * u), Y = (int)rint(256.0 * v);      // |.| <= 2^24
+  int X, Y;
+  if (!project_fixed(cam.k[g.view - cam.first], x, y, z, X, Y)) return VIS_OUTSIDE;
   const int px = X >> 8, py = Y >> 8;                                  // arithmetic shifts: floor
   if (px < 0 || px >= m.W || py < 0 || py >= m.H) return VIS_OUTSIDE;
   const size_t base = (size_t)g.view * m.H * m.W;
@@ -140,18 +136,8 @@ __global__ __launch_bounds__(256) void vis_points_kernel(VisCameras cam, VisMaps
 }
 
 // ------------------------------------------------------------------------------------------------------------------ coverage
-struct CMesh {
-  hm_mesh m;
-  double k[6];
-};
-struct CMeshBlock {
-  CMesh m[MESHES_PER_LAUNCH];
-  int count, first;
-};
-struct CFace {                                     // corners in the order the rule leaves them, 24.8 fixed point
-  int x0, y0, x1, y1, x2, y2;
-  int flags, pad;
-};
+using CFace = FaceGeom;                            // a face record is the geometry alone (tag unused: 0)
+static_assert(sizeof(CFace) == 32, "the workspace layout counts on this");
 
 // The tile core's workspace without its key buffer and tile flags: counter, mesh records, work list, face records, face boxes.
 TileLayout layout(int H, int W, int n_meshes, int n_faces) {
@@ -167,68 +153,16 @@ TileLayout layout(int H, int W, int n_meshes, int n_faces) {
   return L;
 }
 
-__device__ __forceinline__ bool owns(int ax, int ay, int bx, int by) {
-  const int dy = by - ay, dx = bx - ax;
-  return dy < 0 || (dy == 0 && dx > 0);
-}
-
 // One workgroup per mesh of the block.
-__global__ __launch_bounds__(256) void coverage_setup_kernel(CMeshBlock mb, const double* __restrict__ verts,
+__global__ __launch_bounds__(256) void coverage_setup_kernel(MeshBlock mb, const double* __restrict__ verts,
                                                              const int* __restrict__ faces, int H, int W, double znear,
                                                              char* __restrict__ ws, TileLayout L) {
-  const int mi = blockIdx.x, tid = threadIdx.x;
+  const int mi = blockIdx.x;
   const hm_mesh m = mb.m[mi].m;
-  const int mesh = mb.first + mi;
-  const double k00 = mb.m[mi].k[0], k01 = mb.m[mi].k[1], k02 = mb.m[mi].k[2];
-  const double k10 = mb.m[mi].k[3], k11 = mb.m[mi].k[4], k12 = mb.m[mi].k[5];
-  const double* vb = verts + (size_t)m.v0 * 3;
-  CFace* recs = (CFace*)(ws + L.recs);
-  int4* boxes = (int4*)(ws + L.boxes);
-  int lx0 = INT_MAX, ly0 = INT_MAX, lx1 = INT_MIN, ly1 = INT_MIN;
-  for (int j = tid; j < m.nf; j += 256) {
-    const size_t fid = (size_t)m.f0 + j;
-    const int c[3] = {faces[fid * 3], faces[fid * 3 + 1], faces[fid * 3 + 2]};
-    bool ok = true;
-    int X[3] = {0, 0, 0}, Y[3] = {0, 0, 0};
-    for (int q = 0; q < 3; ++q) {
-      if (c[q] < 0 || c[q] >= m.nv) { ok = false; continue; }          // never read outside the mesh's vertices
-      const double x = vb[(size_t)c[q] * 3], y = vb[(size_t)c[q] * 3 + 1], z = vb[(size_t)c[q] * 3 + 2];
-      const double u = ((k00 * x + k01 * y) + k02 * z) / z;
-      const double v = ((k10 * x + k11 * y) + k12 * z) / z;
-      if (!(z >= znear) || !(fabs(u) < 65536.0) || !(fabs(v) < 65536.0)) { ok = false; continue; }
-      X[q] = (int)rint(256.0 * u); Y[q] = (int)rint(256.0 * v);       // |.| <= 2^24
-    }
-    int4 box = make_int4(1, 1, 0, 0);                                   // empty
-    CFace r = {};
-    if (ok) {
-      long long area = edge64(X[0], Y[0], X[1], Y[1], X[2], Y[2]);
-      if (area < 0) {
-        int t = X[1]; X[1] = X[2]; X[2] = t;
-        t = Y[1]; Y[1] = Y[2]; Y[2] = t;
-        area = -area;
-      }
-      if (area != 0) {
-        const int fx0 = min(X[0], min(X[1], X[2])), fx1 = max(X[0], max(X[1], X[2]));
-        const int fy0 = min(Y[0], min(Y[1], Y[2])), fy1 = max(Y[0], max(Y[1], Y[2]));
-        r.x0 = X[0]; r.y0 = Y[0]; r.x1 = X[1]; r.y1 = Y[1]; r.x2 = X[2]; r.y2 = Y[2];
-        r.flags = ((fx1 - fx0) < 32768 && (fy1 - fy0) < 32768 ? F_SMALL : 0) | (owns(X[1], Y[1], X[2], Y[2]) ? F_OWN0 : 0) |
-                  (owns(X[2], Y[2], X[0], Y[0]) ? F_OWN1 : 0) | (owns(X[0], Y[0], X[1], Y[1]) ? F_OWN2 : 0);
-        // pixels whose centre 256 p + 128 lies inside the corners' box (arithmetic shifts: floor), clipped to the view
-        box = make_int4(max((fx0 + 127) >> 8, 0), max((fy0 + 127) >> 8, 0), min((fx1 - 128) >> 8, W - 1), min((fy1 - 128) >> 8, H - 1));
-        if (box.x <= box.z && box.y <= box.w) {
-          lx0 = min(lx0, box.x); ly0 = min(ly0, box.y); lx1 = max(lx1, box.z); ly1 = max(ly1, box.w);
-        } else {
-          box = make_int4(1, 1, 0, 0);
-        }
-      }
-    }
-    recs[fid] = r;
-    boxes[fid] = box;
-  }
-  emit_mesh_tiles(lx0, ly0, lx1, ly1, mesh, MeshRec{m.frame, m.f0, m.nf, 0}, ws, L);
+  const int4 box = setup_faces(mb.m[mi], verts, faces, H, W, znear, (CFace*)(ws + L.recs), (int4*)(ws + L.boxes),
+                               [](CFace& r, const FaceGeom& g, const FaceRest&) { r = g; });
+  emit_mesh_tiles(box.x, box.y, box.z, box.w, mb.first + mi, MeshRec{m.frame, m.f0, m.nf, 0}, ws, L);
 }
-
-__device__ __forceinline__ bool covered(long long e, bool own) { return e > 0 || (e == 0 && own); }
 
 // The box of a wave's set lanes inside its four tile rows (lane = 16 * row + column): left, top, right, bottom, tile-relative.
 __device__ __forceinline__ int4 ballot_box(unsigned long long b, int wave) {
@@ -270,19 +204,8 @@ __global__ __launch_bounds__(256) void coverage_kernel(VisMaps mp, CoverageOut o
       const int n = cull_to_lds(hit, [&](int slot) { s_face[slot] = recs[(size_t)m.f0 + j]; });
       if (in_view && !cov) {
         for (int q = 0; q < n && !cov; ++q) {
-          const CFace& f = s_face[q];
-          const int fx0 = min(f.x0, min(f.x1, f.x2)), fx1 = max(f.x0, max(f.x1, f.x2));
-          const int fy0 = min(f.y0, min(f.y1, f.y2)), fy1 = max(f.y0, max(f.y1, f.y2));
-          if (sx < fx0 || sx > fx1 || sy < fy0 || sy > fy1) continue;    // inside the box every difference is < the span
-          if (f.flags & F_SMALL) {                                       // |e| < 2^31: two products below 2^30
-            const int a = edge32(f.x1, f.y1, f.x2, f.y2, sx, sy), b = edge32(f.x2, f.y2, f.x0, f.y0, sx, sy),
-                      c = edge32(f.x0, f.y0, f.x1, f.y1, sx, sy);
-            cov = covered(a, f.flags & F_OWN0) && covered(b, f.flags & F_OWN1) && covered(c, f.flags & F_OWN2);
-          } else {
-            const long long a = edge64(f.x1, f.y1, f.x2, f.y2, sx, sy), b = edge64(f.x2, f.y2, f.x0, f.y0, sx, sy),
-                            c = edge64(f.x0, f.y0, f.x1, f.y1, sx, sy);
-            cov = covered(a, f.flags & F_OWN0) && covered(b, f.flags & F_OWN1) && covered(c, f.flags & F_OWN2);
-          }
+          if (outside_box(s_face[q], sx, sy)) continue;
+          cov = edges_inside(s_face[q], sx, sy);
         }
       }
       __syncthreads();                                                 // the list is rewritten by the next chunk
@@ -337,23 +260,18 @@ __global__ __launch_bounds__(256) void coverage_kernel(VisMaps mp, CoverageOut o
   }
 }
 
-bool finite_pos(double v) { return v > 0.0 && v < INFINITY; }
-
 int check_maps(const char* entry, int N, int H, int W, const double* K, double znear, const float* depth, const int32_t* mesh_id,
                const uint16_t* sensor, double unit, int raw_lo, int raw_hi, double scene_tol_m, const uint8_t* mask) {
   if (!K || !depth || !mesh_id) return tile_error(entry, "null pointer");
   if (N < 1 || H < 1 || W < 1 || (long long)N * H * W >= (1ll << 31)) return tile_error(entry, "need N, H, W >= 1 and N H W < 2^31");
-  if (!finite_pos(znear)) return tile_error(entry, "znear must be a finite number > 0");
+  if (!positive_finite(znear)) return tile_error(entry, "znear must be a finite number > 0");
   if (((uintptr_t)depth | (uintptr_t)mesh_id) & 3) return tile_error(entry, "depth and mesh_id must be 4-byte aligned");
   if ((uintptr_t)sensor & 1) return tile_error(entry, "sensor must be 2-byte aligned");
   if (sensor) {
-    if (!finite_pos(unit) || !finite_pos(scene_tol_m)) return tile_error(entry, "unit and scene_tol_m must be finite numbers > 0");
+    if (!positive_finite(unit) || !positive_finite(scene_tol_m)) return tile_error(entry, "unit and scene_tol_m must be finite numbers > 0");
     if (raw_lo > raw_hi) return tile_error(entry, "raw_lo > raw_hi");
   }
-  for (int n = 0; n < N; ++n)
-    if (!(K[n * 9 + 6] == 0.0 && K[n * 9 + 7] == 0.0 && K[n * 9 + 8] == 1.0))
-      return tile_error(entry, "the last row of every K must be exactly (0, 0, 1)");
-  return HM_OK;
+  return check_cameras(entry, K, N);
 }
 
 VisMaps maps_of(int N, int H, int W, const float* depth, const int32_t* mesh_id, const uint16_t* sensor, double unit, int raw_lo,
@@ -430,13 +348,8 @@ extern "C" int hm_mesh_coverage(int N, int H, int W, const double* K_host, const
       hipMemsetAsync(boxes, 0xFF, (size_t)n_meshes * 8 * sizeof(int32_t), s) != hipSuccess)
     return hm_set_error(HM_ERR_HIP, "hm_mesh_coverage: hipMemsetAsync");
   for (int first = 0; first < n_meshes; first += MESHES_PER_LAUNCH) {
-    CMeshBlock mb;
-    mb.first = first;
-    mb.count = n_meshes - first < MESHES_PER_LAUNCH ? n_meshes - first : MESHES_PER_LAUNCH;
-    for (int i = 0; i < mb.count; ++i) {
-      mb.m[i].m = meshes_host[first + i];
-      for (int c = 0; c < 6; ++c) mb.m[i].k[c] = K_host[(size_t)mb.m[i].m.frame * 9 + c];
-    }
+    MeshBlock mb;
+    fill_mesh_block(mb, meshes_host, n_meshes, K_host, first);
     hipLaunchKernelGGL(coverage_setup_kernel, dim3(mb.count), dim3(256), 0, s, mb, verts, faces, H, W, znear, ws, L);
   }
   CoverageOut o;

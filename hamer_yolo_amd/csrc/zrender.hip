@@ -2,15 +2,14 @@
 // renderer.render(...)`): per view an RGBA image, a per-pixel depth map and a per-pixel mesh label, and optionally the
 // colour composed onto BGR frames.  The rule is stated in include/hamer_hip.h (hm_mesh_render) and DESIGN.md section 8.1;
 // tests/zrender_rule.py restates it in numpy.  It has the shape of render.hip, and the common part is raster_tiles.h: one
-// workspace whose key buffer stays 0xFF between calls, mesh records as kernel arguments, no host synchronisation.
+// workspace whose key buffer stays 0xFF between calls, mesh records as kernel arguments, no host synchronisation.  Which
+// pixel centres a face covers is zbuffer_faces.h, shared with visibility.hip.
 //  * normals - one thread per vertex walks its mesh's faces, staged in LDS 1024 at a time, and sums the fp64 face cross
 //              products of the faces that name it in ascending row order: no float atomics, one order.
-//  * setup   - one workgroup per mesh: per face the fp64 projection to 24.8 fixed point, the validity tests, the winding
-//              swap, 1/z per corner, the top-left ownership bits, the pixel box clipped to the view; the mesh's box, cut into
-//              16 x 16 tiles, appended to a work list through one atomic counter.
+//  * setup   - one workgroup per mesh: the shared face setup, of which this file keeps everything (1/z per corner, the area,
+//              the vertex rows); the mesh's box, cut into 16 x 16 tiles, appended to a work list through one atomic counter.
 //  * raster  - a grid-strided loop over the work list: per (mesh, tile) the faces are culled into LDS (ballot + prefix),
-//              one lane per pixel evaluates the edge functions at the pixel centre (int32 when the face's box spans less
-//              than 2^15 sub-pixel units, int64 otherwise), computes the fp64 perspective-correct depth of the covered
+//              one lane per pixel runs the shared sample test, computes the fp64 perspective-correct depth of the covered
 //              (pixel, face) pairs only, and sends the smallest (fp32 depth bits, face id) key to the view's key buffer with
 //              one unsigned 64-bit atomicMin.
 //  * resolve - one pass over the views, four pixels per lane where the row length and the pointers allow 16-byte
@@ -20,54 +19,37 @@
 #include <math.h>
 #include "common.h"
 #include "raster_tiles.h"
+#include "zbuffer_faces.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 using namespace raster_tiles;
+using namespace zbuffer_faces;
 
-constexpr int MESHES_PER_LAUNCH = 48;              // kernel argument block stays under 4 KiB
 constexpr int NORMAL_CHUNK = 1024;                 // faces staged in LDS per step of the normals kernel
-constexpr int F_SMALL = 1, F_OWN0 = 2, F_OWN1 = 4, F_OWN2 = 8;
 
-struct ZMesh {
-  hm_mesh m;
-  double k[6];                                     // K00 K01 K02 K10 K11 K12 of the mesh's view
-};
-struct ZMeshBlock {
-  ZMesh m[MESHES_PER_LAUNCH];
-  int count, first;
-};
-
-// Per face, written by setup, indexed by the global face id.  Corners are in the order the rule leaves them (1 and 2
-// swapped when the signed area was negative), in 24.8 fixed point.
+// Per face, written by setup, indexed by the global face id.
 struct ZFace {
-  int x0, y0, x1, y1, x2, y2;
-  int flags, mesh;                                 // mesh: row of the mesh table
+  FaceGeom g;                                      // g.tag: row of the mesh table
   double area2;                                    // twice the area (> 0), exact
   double r0, r1, r2;                               // 1 / z per corner
   int v0, v1, v2, pad;                             // global vertex rows of the corners
 };
 struct ZTileFace {                                 // what raster keeps in LDS
-  int x0, y0, x1, y1, x2, y2;
-  int flags, j;                                    // j: the face's index inside its mesh
+  FaceGeom g;                                      // g.tag: the face's index inside its mesh
   double area2, r0, r1, r2;
 };
+static_assert(sizeof(ZFace) == 80 && sizeof(ZTileFace) == 64, "the workspace layout counts on these");
 
 using ZLayout = TileLayout;                        // tail: one fp64 normal (three doubles) per vertex
 ZLayout layout(int N, int H, int W, int n_verts, int n_meshes, int n_faces) {
   return tile_layout(N, H, W, n_meshes, n_faces, sizeof(ZFace), (size_t)n_verts * 3 * sizeof(double));
 }
 
-// Edge a -> b owns the samples on its line: a top edge or a left edge of a triangle of positive area.
-__device__ __forceinline__ bool owns(int ax, int ay, int bx, int by) {
-  const int dy = by - ay, dx = bx - ax;
-  return dy < 0 || (dy == 0 && dx > 0);
-}
-
 // Grid (ceil(max nv / 256), meshes of the block): one thread per vertex.
-__global__ __launch_bounds__(256) void zrender_normals_kernel(ZMeshBlock mb, const double* __restrict__ verts,
-                                                              const int* __restrict__ faces, char* __restrict__ ws, ZLayout L) {
+__global__ __launch_bounds__(256) void zrender_normals_kernel(MeshBlock mb, const double* __restrict__ verts, const int* __restrict__ faces,
+                                                              char* __restrict__ ws, ZLayout L) {
   __shared__ int s_f[NORMAL_CHUNK * 3];
   const hm_mesh m = mb.m[blockIdx.y].m;
   if ((int)(blockIdx.x * 256) >= m.nv) return;                         // the whole workgroup leaves together
@@ -106,71 +88,19 @@ __global__ __launch_bounds__(256) void zrender_normals_kernel(ZMeshBlock mb, con
 }
 
 // One workgroup per mesh of the block.
-__global__ __launch_bounds__(256) void zrender_setup_kernel(ZMeshBlock mb, const double* __restrict__ verts,
+__global__ __launch_bounds__(256) void zrender_setup_kernel(MeshBlock mb, const double* __restrict__ verts,
                                                             const int* __restrict__ faces, int H, int W, double znear,
                                                             char* __restrict__ ws, ZLayout L) {
-  const int mi = blockIdx.x, tid = threadIdx.x;
+  const int mi = blockIdx.x, mesh = mb.first + mi;
   const hm_mesh m = mb.m[mi].m;
-  const int mesh = mb.first + mi;
-  const double k00 = mb.m[mi].k[0], k01 = mb.m[mi].k[1], k02 = mb.m[mi].k[2];
-  const double k10 = mb.m[mi].k[3], k11 = mb.m[mi].k[4], k12 = mb.m[mi].k[5];
-  const double* vb = verts + (size_t)m.v0 * 3;
-  ZFace* recs = (ZFace*)(ws + L.recs);
-  int4* boxes = (int4*)(ws + L.boxes);
-  int lx0 = INT_MAX, ly0 = INT_MAX, lx1 = INT_MIN, ly1 = INT_MIN;
-  for (int j = tid; j < m.nf; j += 256) {
-    const size_t fid = (size_t)m.f0 + j;
-    int c[3] = {faces[fid * 3], faces[fid * 3 + 1], faces[fid * 3 + 2]};
-    bool ok = true;
-    int X[3] = {0, 0, 0}, Y[3] = {0, 0, 0};
-    double R[3] = {0, 0, 0};
-    for (int q = 0; q < 3; ++q) {
-      if (c[q] < 0 || c[q] >= m.nv) { ok = false; continue; }         // never read outside the mesh's vertices
-      const double x = vb[(size_t)c[q] * 3], y = vb[(size_t)c[q] * 3 + 1], z = vb[(size_t)c[q] * 3 + 2];
-      const double u = ((k00 * x + k01 * y) + k02 * z) / z;
-      const double v = ((k10 * x + k11 * y) + k12 * z) / z;
-      if (!(z >= znear) || !(fabs(u) < 65536.0) || !(fabs(v) < 65536.0)) { ok = false; continue; }
-      X[q] = (int)rint(256.0 * u); Y[q] = (int)rint(256.0 * v);      // |.| <= 2^24
-      R[q] = 1.0 / z;
-    }
-    int4 box = make_int4(1, 1, 0, 0);                                  // empty
-    ZFace r = {};
-    if (ok) {
-      long long area = edge64(X[0], Y[0], X[1], Y[1], X[2], Y[2]);
-      if (area < 0) {
-        int t = X[1]; X[1] = X[2]; X[2] = t;
-        t = Y[1]; Y[1] = Y[2]; Y[2] = t;
-        t = c[1]; c[1] = c[2]; c[2] = t;
-        const double d = R[1]; R[1] = R[2]; R[2] = d;
-        area = -area;
-      }
-      if (area != 0) {
-        const int fx0 = min(X[0], min(X[1], X[2])), fx1 = max(X[0], max(X[1], X[2]));
-        const int fy0 = min(Y[0], min(Y[1], Y[2])), fy1 = max(Y[0], max(Y[1], Y[2]));
-        r.x0 = X[0]; r.y0 = Y[0]; r.x1 = X[1]; r.y1 = Y[1]; r.x2 = X[2]; r.y2 = Y[2];
-        // E_i is the edge function of the edge opposite corner i: 1 -> 2, 2 -> 0, 0 -> 1
-        r.flags = ((fx1 - fx0) < 32768 && (fy1 - fy0) < 32768 ? F_SMALL : 0) | (owns(X[1], Y[1], X[2], Y[2]) ? F_OWN0 : 0) |
-                  (owns(X[2], Y[2], X[0], Y[0]) ? F_OWN1 : 0) | (owns(X[0], Y[0], X[1], Y[1]) ? F_OWN2 : 0);
-        r.mesh = mesh;
-        r.area2 = (double)area;
-        r.r0 = R[0]; r.r1 = R[1]; r.r2 = R[2];
-        r.v0 = m.v0 + c[0]; r.v1 = m.v0 + c[1]; r.v2 = m.v0 + c[2];
-        // pixels whose centre 256 p + 128 lies inside the corners' box (arithmetic shifts: floor), clipped to the view
-        box = make_int4(max((fx0 + 127) >> 8, 0), max((fy0 + 127) >> 8, 0), min((fx1 - 128) >> 8, W - 1), min((fy1 - 128) >> 8, H - 1));
-        if (box.x <= box.z && box.y <= box.w) {
-          lx0 = min(lx0, box.x); ly0 = min(ly0, box.y); lx1 = max(lx1, box.z); ly1 = max(ly1, box.w);
-        } else {
-          box = make_int4(1, 1, 0, 0);
-        }
-      }
-    }
-    recs[fid] = r;
-    boxes[fid] = box;
-  }
-  emit_mesh_tiles(lx0, ly0, lx1, ly1, mesh, MeshRec{m.frame, m.f0, m.nf, 0}, ws, L);
+  const int4 box = setup_faces(mb.m[mi], verts, faces, H, W, znear, (ZFace*)(ws + L.recs), (int4*)(ws + L.boxes),
+                               [&](ZFace& r, const FaceGeom& g, const FaceRest& t) {
+    r.g = g; r.g.tag = mesh; r.area2 = t.area2;
+    r.r0 = t.r0; r.r1 = t.r1; r.r2 = t.r2;
+    r.v0 = m.v0 + t.c0; r.v1 = m.v0 + t.c1; r.v2 = m.v0 + t.c2;
+  });
+  emit_mesh_tiles(box.x, box.y, box.z, box.w, mesh, MeshRec{m.frame, m.f0, m.nf, 0}, ws, L);
 }
-
-__device__ __forceinline__ bool covered(long long e, bool own) { return e > 0 || (e == 0 && own); }
 
 // fp32 depth of a covered sample from its edge values: the rule's expression, in its order.
 __device__ __forceinline__ float sample_depth(double e0, double e1, double e2, double area2, double r0, double r1, double r2) {
@@ -202,31 +132,18 @@ __global__ __launch_bounds__(256) void zrender_raster_kernel(int H, int W, char*
       const bool hit = j < m.nf && box_meets_tile(boxes[(size_t)m.f0 + j], x0, y0);
       const int n = cull_to_lds(hit, [&](int slot) {
         const ZFace r = recs[(size_t)m.f0 + j];
-        const ZTileFace t = {r.x0, r.y0, r.x1, r.y1, r.x2, r.y2, r.flags, j, r.area2, r.r0, r.r1, r.r2};
+        const FaceGeom& g = r.g;                                       // member by member: the record leaves as four 16-byte stores
+        const ZTileFace t = {{g.x0, g.y0, g.x1, g.y1, g.x2, g.y2, g.flags, j}, r.area2, r.r0, r.r1, r.r2};
         s_face[slot] = t;
       });
       if (px < W && py < H) {
         for (int q = 0; q < n; ++q) {
           const ZTileFace& f = s_face[q];
-          const int fx0 = min(f.x0, min(f.x1, f.x2)), fx1 = max(f.x0, max(f.x1, f.x2));
-          const int fy0 = min(f.y0, min(f.y1, f.y2)), fy1 = max(f.y0, max(f.y1, f.y2));
-          if (sx < fx0 || sx > fx1 || sy < fy0 || sy > fy1) continue;    // inside the box every difference is < the span
           double e0, e1, e2;
-          bool in;
-          if (f.flags & F_SMALL) {                                       // |e| < 2^31: two products below 2^30
-            const int a = edge32(f.x1, f.y1, f.x2, f.y2, sx, sy), b = edge32(f.x2, f.y2, f.x0, f.y0, sx, sy),
-                      c = edge32(f.x0, f.y0, f.x1, f.y1, sx, sy);
-            in = covered(a, f.flags & F_OWN0) && covered(b, f.flags & F_OWN1) && covered(c, f.flags & F_OWN2);
-            e0 = (double)a; e1 = (double)b; e2 = (double)c;
-          } else {
-            const long long a = edge64(f.x1, f.y1, f.x2, f.y2, sx, sy), b = edge64(f.x2, f.y2, f.x0, f.y0, sx, sy),
-                            c = edge64(f.x0, f.y0, f.x1, f.y1, sx, sy);
-            in = covered(a, f.flags & F_OWN0) && covered(b, f.flags & F_OWN1) && covered(c, f.flags & F_OWN2);
-            e0 = (double)a; e1 = (double)b; e2 = (double)c;
-          }
-          if (!in) continue;
+          if (outside_box(f.g, sx, sy)) continue;
+          if (!edges_inside(f.g, sx, sy, e0, e1, e2)) continue;
           const float d = sample_depth(e0, e1, e2, f.area2, f.r0, f.r1, f.r2);
-          const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(m.f0 + f.j);
+          const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(m.f0 + f.g.tag);
           if (key < best) best = key;
         }
       }
@@ -254,8 +171,9 @@ __device__ __forceinline__ ZPixel shade(unsigned long long key, int px, int py, 
   const ZFace f = ((const ZFace*)(ws + L.recs))[(unsigned)key];
   const double* nrm = (const double*)(ws + L.tail);
   const int sx = 256 * px + 128, sy = 256 * py + 128;
-  const double e0 = (double)edge64(f.x1, f.y1, f.x2, f.y2, sx, sy), e1 = (double)edge64(f.x2, f.y2, f.x0, f.y0, sx, sy),
-               e2 = (double)edge64(f.x0, f.y0, f.x1, f.y1, sx, sy);
+  const FaceGeom& g = f.g;
+  const double e0 = (double)edge64(g.x1, g.y1, g.x2, g.y2, sx, sy), e1 = (double)edge64(g.x2, g.y2, g.x0, g.y0, sx, sy),
+               e2 = (double)edge64(g.x0, g.y0, g.x1, g.y1, sx, sy);
   const double l0 = e0 / f.area2, l1 = e1 / f.area2, l2 = e2 / f.area2;
   const double a0 = l0 * f.r0, a1 = l1 * f.r1, a2 = l2 * f.r2;
   const double* n0 = nrm + (size_t)f.v0 * 3;
@@ -270,7 +188,7 @@ __device__ __forceinline__ ZPixel shade(unsigned long long key, int px, int py, 
   ZPixel p;
   p.rgba = rint_u8(255.0 * o.base[0] * I) | (rint_u8(255.0 * o.base[1] * I) << 8) | (rint_u8(255.0 * o.base[2] * I) << 16) | 0xFF000000u;
   p.depth = __uint_as_float((unsigned)(key >> 32));
-  p.mesh = f.mesh;
+  p.mesh = f.g.tag;
   return p;
 }
 
@@ -357,16 +275,15 @@ int check_args(int N, int H, int W, const double* K, const double* verts, int n_
   if (n_meshes < 0 || n_verts < 0 || n_faces < 0) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: negative count");
   if (n_meshes > 0 && !meshes) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: null mesh table");
   if ((n_verts > 0 && !verts) || (n_faces > 0 && !faces)) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: null vertices or faces");
-  if (!(znear > 0.0) || !(znear < INFINITY)) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: znear must be a finite number > 0");
-  for (int n = 0; n < N; ++n)
-    if (!(K[n * 9 + 6] == 0.0 && K[n * 9 + 7] == 0.0 && K[n * 9 + 8] == 1.0))
-      return hm_set_error(HM_ERR_ARG, "hm_mesh_render: the last row of every K must be exactly (0, 0, 1)");
+  if (!positive_finite(znear)) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: znear must be a finite number > 0");
+  int rc = check_cameras("hm_mesh_render", K, N);
+  if (rc != HM_OK) return rc;
   if (base_rgb)
     for (int c = 0; c < 3; ++c)
       if (!(base_rgb[c] >= 0.0 && base_rgb[c] <= 1.0)) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: base_rgb outside [0, 1]");
   if (!out && !rgba && !depth && !mesh_id) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: no output requested");
   if ((frames == nullptr) != (out == nullptr)) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: frames and out are given both or neither");
-  int rc = check_out_apart("hm_mesh_render", frames, out, (size_t)N * H * W * 3);
+  rc = check_out_apart("hm_mesh_render", frames, out, (size_t)N * H * W * 3);
   if (rc == HM_OK) rc = check_mesh_table("hm_mesh_render", "view", meshes, n_meshes, N, n_verts, n_faces, true);
   if (rc != HM_OK) return rc;
   if (ws_bytes < layout(N, H, W, n_verts, n_meshes, n_faces).total) return hm_set_error(HM_ERR_ARG, "hm_mesh_render: workspace too small");
@@ -396,15 +313,8 @@ extern "C" int hm_mesh_render(int N, int H, int W, const double* K_host, const d
   if (hipMemsetAsync(ws + L.counter, 0, L.meshes - L.counter, s) != hipSuccess)     // counter and tile flags
     return hm_set_error(HM_ERR_HIP, "hm_mesh_render: hipMemsetAsync");
   for (int first = 0; first < n_meshes; first += MESHES_PER_LAUNCH) {
-    ZMeshBlock mb;
-    mb.first = first;
-    mb.count = n_meshes - first < MESHES_PER_LAUNCH ? n_meshes - first : MESHES_PER_LAUNCH;
-    int max_nv = 0;
-    for (int i = 0; i < mb.count; ++i) {
-      mb.m[i].m = meshes_host[first + i];
-      for (int c = 0; c < 6; ++c) mb.m[i].k[c] = K_host[(size_t)mb.m[i].m.frame * 9 + c];
-      max_nv = mb.m[i].m.nv > max_nv ? mb.m[i].m.nv : max_nv;
-    }
+    MeshBlock mb;
+    const int max_nv = fill_mesh_block(mb, meshes_host, n_meshes, K_host, first);
     if (max_nv > 0)
       hipLaunchKernelGGL(zrender_normals_kernel, dim3((max_nv + 255) / 256, mb.count), dim3(256), 0, s, mb, verts, faces, ws, L);
     hipLaunchKernelGGL(zrender_setup_kernel, dim3(mb.count), dim3(256), 0, s, mb, verts, faces, H, W, znear, ws, L);

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from ... import lib as L
+from .depth_eval import _workspace
 
 MAX_RADIUS = 64
 COUNT_NAMES = ("inter", "pred_area", "gt_area", "pred_boundary", "gt_boundary", "pred_matched", "gt_matched", "pixels")
@@ -53,28 +54,33 @@ def _query_table(queries, N: int) -> np.ndarray:
     return np.ascontiguousarray(q.astype(np.int32))
 
 
+def _check_pair(who: str, pred_id, mask):
+    """The checks both entry points make of the two maps; returns their device and (N, H, W)."""
+    if not (torch.is_tensor(pred_id) and torch.is_tensor(mask)):
+        raise ValueError(f"{who}: pred_id and mask must be tensors")
+    if not (pred_id.is_cuda and mask.is_cuda and pred_id.device == mask.device):
+        raise ValueError(f"{who}: pred_id and mask must be on one GPU; there is no CPU path")
+    if pred_id.dtype != torch.int32 or mask.dtype != torch.uint8:
+        raise ValueError(f"{who}: pred_id must be int32 and mask uint8, got {pred_id.dtype} and {mask.dtype}")
+    if pred_id.dim() != 3 or tuple(pred_id.shape) != tuple(mask.shape) or 0 in pred_id.shape:
+        raise ValueError(f"{who}: pred_id {tuple(pred_id.shape)} / mask {tuple(mask.shape)}: expected two (N, H, W)")
+    if not (pred_id.is_contiguous() and mask.is_contiguous()):
+        raise ValueError(f"{who}: pred_id and mask must be contiguous")
+    return pred_id.device, tuple(int(v) for v in pred_id.shape)
+
+
 def mask_counts(pred_id: torch.Tensor, mask: torch.Tensor, queries: Sequence, radius: Optional[int] = None,
                 bound_th: float = 0.008, counts: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One hm_mask_score call.  ``pred_id`` (N, H, W) int32 and ``mask`` (N, H, W) uint8, contiguous tensors on one GPU;
     ``queries``: a sequence of (frame, id_lo, id_hi, label); ``radius``: the tolerance in pixels, 0..64 (None:
     ``bound_radius(H, W, bound_th)``).  Returns (Q, 8) int64 on the device (``COUNT_NAMES``), or fills ``counts``.  Enqueued
     on the current stream without synchronising; the workspace is cached per device and stream (``release_workspaces``)."""
-    if not (torch.is_tensor(pred_id) and torch.is_tensor(mask)):
-        raise ValueError("mask_counts: pred_id and mask must be tensors")
-    if not (pred_id.is_cuda and mask.is_cuda and pred_id.device == mask.device):
-        raise ValueError("mask_counts: pred_id and mask must be on one GPU; there is no CPU path")
-    if pred_id.dtype != torch.int32 or mask.dtype != torch.uint8:
-        raise ValueError(f"mask_counts: pred_id must be int32 and mask uint8, got {pred_id.dtype} and {mask.dtype}")
-    if pred_id.dim() != 3 or tuple(pred_id.shape) != tuple(mask.shape) or 0 in pred_id.shape:
-        raise ValueError(f"mask_counts: pred_id {tuple(pred_id.shape)} / mask {tuple(mask.shape)}: expected two (N, H, W)")
-    if not (pred_id.is_contiguous() and mask.is_contiguous()):
-        raise ValueError("mask_counts: pred_id and mask must be contiguous")
-    N, H, W = (int(v) for v in pred_id.shape)
+    dev, (N, H, W) = _check_pair("mask_counts", pred_id, mask)
     r = bound_radius(H, W, bound_th) if radius is None else int(radius)
     if not 0 <= r <= MAX_RADIUS:
         raise ValueError(f"mask_counts: radius {r} outside 0..{MAX_RADIUS}")
     table = _query_table(queries, N)
-    Q, dev = int(table.shape[0]), pred_id.device
+    Q = int(table.shape[0])
     if counts is None:
         counts = torch.empty(Q, 8, dtype=torch.int64, device=dev)
     elif not (torch.is_tensor(counts) and counts.device == dev and counts.dtype == torch.int64 and tuple(counts.shape) == (Q, 8)
@@ -83,14 +89,9 @@ def mask_counts(pred_id: torch.Tensor, mask: torch.Tensor, queries: Sequence, ra
     if Q == 0:
         return counts
     lib = L.load()
-    need = int(lib.hm_mask_score_workspace_bytes(Q, H, W, r))
     with torch.cuda.device(dev):
         stream = L.current_stream()
-        key = (dev.index if dev.index is not None else torch.cuda.current_device(), stream)
-        ws = _ws.get(key)
-        if ws is None or ws.numel() * 8 < need:
-            _ws.pop(key, None)
-            ws = _ws[key] = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        ws = _workspace(_ws, dev, stream, int(lib.hm_mask_score_workspace_bytes(Q, H, W, r)))
         qd = torch.from_numpy(table).to(dev)
         L.check(lib.hm_mask_score(L.ptr(pred_id), L.ptr(mask), N, H, W, L.ptr(qd), Q, r, L.ptr(counts), L.ptr(ws), ws.numel() * 8,
                                   stream), "hm_mask_score")
@@ -241,23 +242,12 @@ def mask_fit(pred_id: torch.Tensor, mask: torch.Tensor, queries, centre, *, radi
     the motion is ``q -> centre + (1 + alpha) (q - centre) + beta J (q - centre) + t`` with ``J (x, y) = (-y, x)``.  Enqueued on
     the current stream without synchronising; the workspace is cached per device and stream (``release_fit_workspaces``).
     There is no CPU path."""
-    if not (torch.is_tensor(pred_id) and torch.is_tensor(mask)):
-        raise ValueError("mask_fit: pred_id and mask must be tensors")
-    if not (pred_id.is_cuda and mask.is_cuda and pred_id.device == mask.device):
-        raise ValueError("mask_fit: pred_id and mask must be on one GPU; there is no CPU path")
-    if pred_id.dtype != torch.int32 or mask.dtype != torch.uint8:
-        raise ValueError(f"mask_fit: pred_id must be int32 and mask uint8, got {pred_id.dtype} and {mask.dtype}")
-    if pred_id.dim() != 3 or tuple(pred_id.shape) != tuple(mask.shape) or 0 in pred_id.shape:
-        raise ValueError(f"mask_fit: pred_id {tuple(pred_id.shape)} / mask {tuple(mask.shape)}: expected two (N, H, W)")
-    if not (pred_id.is_contiguous() and mask.is_contiguous()):
-        raise ValueError("mask_fit: pred_id and mask must be contiguous")
-    N, H, W = (int(v) for v in pred_id.shape)
+    dev, (N, H, W) = _check_pair("mask_fit", pred_id, mask)
     r, reach, directions, min_pixels = int(radius), int(reach_px), int(directions), int(min_pixels)
     if not (0 <= r <= MAX_RADIUS and 1 <= reach <= MAX_REACH and directions in (1, 2, 3) and 0 <= damping < np.inf
             and 0 < lever_px < np.inf and min_pixels >= 1):
         raise ValueError(f"mask_fit: expected radius in 0..{MAX_RADIUS}, reach_px in 1..{MAX_REACH}, directions 1, 2 or 3, "
                          "damping >= 0, lever_px > 0 and min_pixels >= 1")
-    dev = pred_id.device
     qd = _device_table("mask_fit", queries if torch.is_tensor(queries) else _query_table(queries, N), dev, 4, "query")
     cd = _device_table("mask_fit", centre, dev, 2, "centre")
     Q = int(qd.shape[0])
@@ -268,14 +258,9 @@ def mask_fit(pred_id: torch.Tensor, mask: torch.Tensor, queries, centre, *, radi
     if Q == 0:
         return out
     lib = L.load()
-    need = int(lib.hm_mask_fit_workspace_bytes(Q, H, W, r))
     with torch.cuda.device(dev):
         stream = L.current_stream()
-        key = (dev.index if dev.index is not None else torch.cuda.current_device(), stream)
-        ws = _fit_ws.get(key)
-        if ws is None or ws.numel() * 8 < need:
-            _fit_ws.pop(key, None)
-            ws = _fit_ws[key] = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        ws = _workspace(_fit_ws, dev, stream, int(lib.hm_mask_fit_workspace_bytes(Q, H, W, r)))
         L.check(lib.hm_mask_fit(L.ptr(pred_id), L.ptr(mask), N, H, W, L.ptr(qd), Q, L.ptr(cd), r, reach, directions, float(damping),
                                 float(lever_px), min_pixels, L.ptr(out["sums"]), L.ptr(out["counts"]), L.ptr(out["solution"]),
                                 L.ptr(ws), ws.numel() * 8, stream), "hm_mask_fit")

@@ -224,6 +224,32 @@ def test_buffers_and_leftover_state():
     assert ME._fit_ws == {}
 
 
+@pytest.mark.parametrize("H,W", [(3, 64), (37, 53), (70, 131)])
+def test_both_entry_points_write_the_same_boundary_maps(H, W):
+    """hm_mask_score and hm_mask_fit leave the same words at the head of their workspaces, each pre-filled with 0xA5: the
+    boundary maps of the rule, 64 pixels per word, zero bits at or past W."""
+    import test_gpu_mask_eval as GE
+    gt = ER.blobs(H, W, 6)
+    pid = np.where(ER.blobs(H, W, 5), 0, -1).astype(np.int32)[None]
+    mask = np.where(gt, 3, 0).astype(np.uint8)[None]
+    mask[0][ER.blobs(H, W, 7, n=1) & ~gt] = 5                                          # label -1 is more than label 3
+    q = np.array([(0, 0, 1, 3), (0, 0, 1, -1)], np.int32)
+    d_pid, d_mask = dev(pid), dev(mask)
+    _, ws_score = GE.abi(d_pid, d_mask, q, KW["radius"])
+    _, ws_fit = abi(d_pid, d_mask, dev(q), dev(np.array([(W // 2, H // 2)] * 2, np.int32)))
+    words = (W + 63) // 64
+    n = len(q) * 2 * H * words
+    got_score, got_fit = (w.cpu().numpy()[:n * 8].view(np.uint64).reshape(len(q), 2, H, words) for w in (ws_score, ws_fit))
+    want = np.zeros((len(q), 2, H, words * 64), bool)
+    for k, qu in enumerate(q):
+        for side, image in enumerate(ER.query_images(pid, mask, qu)):
+            want[k, side, :, :W] = ER.bmap(image)
+    want = np.packbits(want, axis=-1, bitorder="little").view(np.uint64)
+    assert want[0].any() and not np.array_equal(want[0, 1], want[1, 1])
+    assert np.array_equal(got_score, got_fit)
+    assert np.array_equal(got_score, want), np.argwhere(got_score != want)[:8].tolist()
+
+
 def test_argument_errors_with_real_buffers():
     """Every error the header lists, now over real device buffers: HM_ERR_ARG, and the outputs keep their bytes."""
     H, W = 37, 53

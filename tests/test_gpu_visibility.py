@@ -202,6 +202,44 @@ def test_fifty_one_face_meshes():
     V.release_workspaces(); render.release_workspaces()
 
 
+def test_large_face_and_shared_edge():
+    """Both integer widths of the shared sample test, in the renderer and in the coverage kernel: a triangle whose corner box
+    spans more than 2^15 sub-pixel units (the int64 edge functions) behind a square of two small triangles (int32) whose
+    common edge runs exactly through pixel centres, and the same two triangles as two meshes of a second view: every pixel on
+    the diagonal belongs to exactly one of them."""
+    H, W = 24, 40
+    K = camera(H, W)
+    big = np.array([at_pixel(K, -150.0, -10.0, 0.5), at_pixel(K, 200.0, 5.0, 0.5), at_pixel(K, 20.0, 300.0, 0.5)])
+    square = np.array([at_pixel(K, u, v, 0.4) for u, v in ((4.5, 4.5), (20.5, 4.5), (20.5, 20.5), (4.5, 20.5))])
+    meshes = [{"frame": 0, "vertices": big, "faces": np.array([[0, 1, 2]], np.int32)},
+              {"frame": 0, "vertices": square, "faces": np.array([[0, 1, 2], [0, 2, 3]], np.int32)},
+              {"frame": 1, "vertices": square, "faces": np.array([[0, 1, 2]], np.int32)},
+              {"frame": 1, "vertices": square, "faces": np.array([[2, 0, 3]], np.int32)}]
+    spans = []
+    for m in meshes:
+        corners, _, _, _, valid = ZR.face_table(m["vertices"], m["faces"], K, 0.05)
+        assert valid.all()
+        spans += [int((c.max(0) - c.min(0)).max()) for c in corners]
+    assert spans[0] >= 32768 and max(spans[1:]) < 32768               # whatever the code under test does, both widths are asked for
+    oracle, f0 = [], 0
+    for m in meshes:
+        oracle.append(dict(m, face_id0=f0))
+        f0 += len(m["faces"])
+    want = ZR.render(2, H, W, K, oracle)
+    depth, mesh_id, depth_h, mid_h = maps_of(2, H, W, K, meshes)
+    assert np.array_equal(mid_h, want["mesh_id"]) and np.array_equal(depth_h.view(np.uint32), want["depth"].view(np.uint32))
+    assert [int((mid_h[0] == m).sum()) for m in (0, 1)] == [704, 256] and (mid_h[0] >= 0).all()
+    assert [int((mid_h[1] == m).sum()) for m in (-1, 2, 3)] == [704, 136, 120]
+    counts, boxes = V.mesh_coverage(H, W, K, gpu_meshes(meshes), depth, mesh_id)
+    counts, boxes = counts.cpu().numpy(), boxes.cpu().numpy()
+    want_counts, want_boxes = VR.mesh_coverage(H, W, K, meshes, want["depth"], want["mesh_id"])
+    assert np.array_equal(counts, want_counts) and np.array_equal(boxes, want_boxes)
+    check_against_the_renderer(counts, boxes, mid_h, meshes)
+    assert counts[:, 0].tolist() == [960, 256, 136, 120]
+    assert boxes[:, 4:].tolist() == [[0, 0, 39, 23], [4, 4, 19, 19], [4, 4, 19, 19], [4, 5, 18, 19]]
+    V.release_workspaces(); render.release_workspaces()
+
+
 # ------------------------------------------------------------------ c: batch invariance, buffers
 def test_batch_invariance_in_bytes():
     H, W = 40, 70

@@ -12,7 +12,7 @@ out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-s
 cur = None
 rows = {}
 for line in out.splitlines():
-    m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|VGPRs Spill|SGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]):\s+(\S+)", line)
+    m = re.search(r"remark:\s+(Function Name|VGPRs|AGPRs|VGPRs Spill|TotalSGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]):\s+(\S+)", line)
     if not m:
         continue
     k, v = m.groups()
@@ -24,4 +24,5 @@ for line in out.splitlines():
 for name, r in rows.items():
     if flt in name:
         short = name.replace("(anonymous namespace)::", "")
-        print(f"{short[:110]:110s} vgpr {r.get('VGPRs','?'):>4} agpr {r.get('AGPRs','?'):>3} spill {r.get('VGPRs Spill','?'):>3} scratch {r.get('ScratchSize','?'):>4} occ {r.get('Occupancy','?')}")
+        print(f"{short[:110]:110s} vgpr {r.get('VGPRs','?'):>4} agpr {r.get('AGPRs','?'):>3} sgpr {r.get('TotalSGPRs','?'):>3} spill {r.get('VGPRs Spill','?'):>3} "
+              f"scratch {r.get('ScratchSize','?'):>4} lds {r.get('LDS Size','?'):>6} occ {r.get('Occupancy','?')}")
