@@ -1214,6 +1214,7 @@ def _parser() -> argparse.ArgumentParser:
     _mask_args(ap)
     _depth_args(ap)
     _visibility_args(ap)
+    _penetration_args(ap)
     return ap
 
 
@@ -1293,6 +1294,27 @@ def visibility_records(args, hamer, rank: int, world: int, left_label=None) -> N
                            mask_folder=args.masks, label=args.mask_label, left_label=left_label, image_folder=args.input, rank=rank,
                            world=world)
     print(f"{r['annotated']} of {r['hands']} hands annotated with visibility" + (f" (rank {rank})" if world > 1 else ""))
+
+
+def _penetration_args(ap: argparse.ArgumentParser) -> None:
+    ap.add_argument('--penetration', action='store_true',
+                    help="after the records are written (and after any --mask-fit / --depth-maps step), rewrite the two-hand records in "
+                         "place with how far the hands pass through each other: penetration_depth_m, penetration_mean_m, "
+                         "penetration_vertices, contact_vertices, vertices_signed_distance, vertices_contact (evaluate_penetration --write-to)")
+    ap.add_argument('--resolve-penetration', action='store_true',
+                    help="as --penetration, after translating the two hands of every two-hand record apart: cam_t is moved, and "
+                         "cam_t_unresolved, penetration_shift_m and penetration_resolved are added (evaluate_penetration --resolve-to)")
+
+
+def penetration_records(args, hamer, rank: int, world: int) -> None:
+    """The ``--penetration`` / ``--resolve-penetration`` step of the drivers: the records of ``--output`` are rewritten in place."""
+    from . import evaluate_penetration as EP
+    if args.resolve_penetration:
+        r = EP.resolve_folder(args.output, args.output, hamer, rank=rank, world=world)
+        print(f"{r['moved']} of {r['annotated']} two-hand records moved apart, {r['unresolved']} still interpenetrate" + (f" (rank {rank})" if world > 1 else ""))
+    else:
+        r = EP.annotate_folder(args.output, args.output, hamer, rank=rank, world=world)
+        print(f"{r['annotated']} two-hand records annotated with penetration, {r['penetrating']} interpenetrate" + (f" (rank {rank})" if world > 1 else ""))
 
 
 def mask_args(ap: argparse.ArgumentParser, args) -> None:
@@ -1440,6 +1462,10 @@ def main(argv=None):
             dist.barrier()
     if args.depth_maps:
         refine_records(args, hamer, rank, world)
+        if world > 1:
+            dist.barrier()
+    if args.penetration or args.resolve_penetration:               # after the refinements: they move the hands
+        penetration_records(args, hamer, rank, world)
         if world > 1:
             dist.barrier()
     if args.visibility:

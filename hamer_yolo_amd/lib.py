@@ -52,6 +52,7 @@ EXPORTS = [
     "hm_depth_fit_workspace_bytes", "hm_depth_fit",
     "hm_mask_fit_workspace_bytes", "hm_mask_fit",
     "hm_point_visibility", "hm_mesh_coverage_workspace_bytes", "hm_mesh_coverage",
+    "hm_mesh_penetration_workspace_bytes", "hm_mesh_penetration",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -131,6 +132,11 @@ class BoxQuery(C.Structure):
 class VisGroup(C.Structure):
     """hm_vis_group: the points p0 .. p0 + np - 1 of one hm_point_visibility call, in view ``view``, of mesh row ``mesh``."""
     _fields_ = [("tol_m", C.c_double)] + [(n, C.c_int32) for n in ("view", "mesh", "p0", "np", "label", "reserved")]
+
+
+class PenQuery(C.Structure):
+    """hm_pen_query: the vertices of mesh row ``a`` against the surface of mesh row ``b``."""
+    _fields_ = [("a", C.c_int32), ("b", C.c_int32)]
 
 
 class VitBlock(C.Structure):
@@ -337,6 +343,10 @@ def load() -> C.CDLL:
     lib.hm_mesh_coverage_workspace_bytes.restype = C.c_size_t
     lib.hm_mesh_coverage.argtypes = [i, i, i, C.POINTER(d), vp, i, vp, i, C.POINTER(Mesh), i, d, vp, vp, vp, d, i, i, d, vp, vp, vp, vp,
                                      vp, C.c_size_t, vp]
+    lib.hm_mesh_penetration_workspace_bytes.argtypes = [i, i, i]
+    lib.hm_mesh_penetration_workspace_bytes.restype = C.c_size_t
+    lib.hm_mesh_penetration.argtypes = [vp, i, vp, i, C.POINTER(Mesh), i, C.POINTER(PenQuery), i, d, vp, vp, vp, C.c_longlong, vp, vp,
+                                        C.c_size_t, vp]
     lib.hm_skeleton_overlay_workspace_bytes.argtypes = [i, i, i, i]
     lib.hm_skeleton_overlay_workspace_bytes.restype = C.c_size_t
     lib.hm_skeleton_overlay.argtypes = [vp, i, i, i, vp, i, C.POINTER(Skeleton), i, C.POINTER(C.c_uint8), i, vp, vp, C.c_size_t, vp]
@@ -356,7 +366,8 @@ def load() -> C.CDLL:
                         "hm_mesh_overlay_workspace_bytes", "hm_mesh_render_workspace_bytes",
                         "hm_skeleton_overlay_workspace_bytes", "hm_det_ap_workspace_bytes", "hm_nms_batch_workspace_bytes",
                         "hm_pck_auc_workspace_bytes", "hm_mask_score_workspace_bytes", "hm_depth_residuals_workspace_bytes",
-                        "hm_depth_fit_workspace_bytes", "hm_mask_fit_workspace_bytes", "hm_mesh_coverage_workspace_bytes"):
+                        "hm_depth_fit_workspace_bytes", "hm_mask_fit_workspace_bytes", "hm_mesh_coverage_workspace_bytes",
+                        "hm_mesh_penetration_workspace_bytes"):
             fn.restype = i
     if lib.hm_version() != HM_VERSION:
         raise HipLibraryError(f"{LIB_PATH} reports HM_VERSION {lib.hm_version()}, this binding is written for {HM_VERSION}: "

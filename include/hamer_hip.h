@@ -1178,6 +1178,84 @@ int hm_mesh_coverage(int N, int H, int W, const double* K_host, const double* ve
                      int64_t* counts /* device [n_meshes][8] */, int32_t* boxes /* device [n_meshes][8] */, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---- Penetration: do two hand meshes pass through each other: csrc/penetration.hip (hamer/utils/penetration.py, DESIGN.md
+ * section 10.7; tests/penetration_rule.py restates the rule in numpy).  A QUERY is an ordered pair (a, b) of rows of the mesh
+ * table: every vertex of a gets its signed distance to the surface of b.  verts, faces and the hm_mesh rows are those of
+ * hm_mesh_render (frame is not read but must be >= 0; two meshes share neither vertex rows nor face rows); a query may name
+ * any two rows, also of different frames.  b should be a closed surface (hamer/utils/penetration.py close_boundaries closes the
+ * MANO wrist).  The rule uses integers and fp64 only; the unit is compiled with contraction off and every rounded fp64
+ * expression is evaluated left to right as written, so the outputs equal the numpy rule bit for bit.
+ *
+ * Fixed point.  X = rint_half_even(x * 65536) per coordinate (a quantum of 2^-16 m, about 15 um).  A vertex is VALID when
+ * |x|, |y|, |z| < 16384 (not-a-number and infinities fail), so |X| <= 2^30.  A face is VALID when its three corners lie in
+ * 0..nv-1 and name valid vertices; other faces are never read further.  A mesh's BOX is the integer bounding box of its valid
+ * vertices (empty without one).  T = ceil(contact_tol_m * 65536), 0 <= contact_tol_m <= 1, so T <= 2^16.
+ * Status of a query, in this order:
+ *   HM_PEN_TOO_LARGE (2)  a side (hi - lo) of a's or b's box is >= 2^17 (2 m): every vertex of a gets INVALID, NaN, -1, every
+ *                         count and sum is 0, nothing else is computed
+ *   HM_PEN_DISJOINT (1)   a's box and b's box inflated by T on every side do not overlap (also when either is empty): every
+ *                         valid vertex of a is FAR, `invalid` is counted, every other count and sum is 0; no face is read
+ *   HM_PEN_OK (0)         otherwise.  A valid vertex of a outside b's inflated box is FAR without any face test; the others are
+ *                         TESTED
+ * Exactness.  A tested vertex P lies in b's inflated box and every corner V of a valid face in b's box, so per axis
+ * |P - V| < 2^17 + 2^16 < 2^18 and |V - V'| < 2^17.  The edge functions are two products below 2^35; the six dot products of the
+ * distance are three products below 2^35, sums below 2^37; the components of n = (V1 - V0) x (V2 - V0) are two products below 2^34,
+ * so |n_k| < 2^35: all are integers below 2^53, which fp64 products and sums give exactly.  n . (V0 - P) is three products below
+ * 2^35 * 2^18 = 2^53, a sum below 2^55 (< 2^57): it is taken in int64.  Nothing else in the rule needs to be exact.
+ * Face order.  A = (X1-X0)*(Y2-Y0) - (Y1-Y0)*(X2-X0) is twice the face's projected area; when A < 0 corners 1 and 2 are swapped
+ * and A := -A, and everything below uses this order (so n_z = A >= 0).
+ * Inside test.  P is inside b when the ray from P in +z crosses an odd number of b's valid faces.  A face with A != 0 is crossed
+ * when (a) (X, Y) of P lies in its projection by hm_mesh_render's coverage rule: E_i the edge function of the edge opposite
+ * corner i (1->2, 2->0, 0->1) at (X, Y), every E_i > 0, or == 0 on an edge that owns its boundary (dy < 0, or dy == 0 and
+ * dx > 0), and (b) s = n . (V0 - P) > 0: the face's plane at (X, Y) is strictly above P.  With the half-open ownership a ray
+ * through a shared edge or vertex crosses each sheet of the surface once; a vertex exactly on the surface gets what the rule
+ * gives.
+ * Distance.  For a tested vertex, over b's valid faces with n != 0 (a face of area 0 in space is skipped), delta = closest
+ * point of the face minus P, in quanta, by the region method with a = V0, b = V1, c = V2, ab = b-a, ac = c-a, bc = c-b, ap = P-a,
+ * bp = P-b, cp = P-c (integers), dot(u, w) = (ux*wx + uy*wy) + uz*wz, d1 = dot(ab,ap), d2 = dot(ac,ap), d3 = dot(ab,bp),
+ * d4 = dot(ac,bp), d5 = dot(ab,cp), d6 = dot(ac,cp), the first case that holds:
+ *   1  d1 <= 0 && d2 <= 0: delta = -ap                          2  d3 >= 0 && d4 <= d3: delta = -bp
+ *   3  vc = d1*d4 - d3*d2; vc <= 0 && d1 >= 0 && d3 <= 0: v = d1 / (d1 - d3), delta_k = v*ab_k - ap_k
+ *   4  d6 >= 0 && d5 <= d6: delta = -cp
+ *   5  vb = d5*d2 - d1*d6; vb <= 0 && d2 >= 0 && d6 <= 0: w = d2 / (d2 - d6), delta_k = w*ac_k - ap_k
+ *   6  va = d3*d6 - d5*d4; va <= 0 && d4-d3 >= 0 && d5-d6 >= 0: w = (d4-d3) / ((d4-d3) + (d5-d6)), delta_k = w*bc_k - bp_k
+ *   7  nn = (nx*nx + ny*ny) + nz*nz, s = (nx*-apx + ny*-apy) + nz*-apz, t = s / nn, delta_k = n_k*t
+ * (d1 - d3 = |ab|^2, d2 - d6 = |ac|^2, (d4-d3) + (d5-d6) = |bc|^2 and nn are >= 1 for a face with n != 0: no division by 0.)
+ * D2 = (dx*dx + dy*dy) + dz*dz; the nearest face is the one of smallest D2, ties to the lower face row; d = sqrt(D2) * 2^-16 in
+ * metres.  A face of the product region 7 that the rounded va, vb, vc misjudge lies within rounding of an edge, where both
+ * formulas agree to rounding.
+ * Per vertex of a (row = the sum of the a-meshes' nv over the earlier queries, plus the vertex's index): code u8 -- HM_PEN_FAR
+ * 0 (not tested, or outside with d > contact_tol_m), HM_PEN_NEAR 1 (outside, d <= contact_tol_m), HM_PEN_INSIDE 2,
+ * HM_PEN_INVALID 3 (not a valid vertex); signed_distance f32: (float)d for NEAR, (float)-d for INSIDE, +inf for FAR, NaN for
+ * INVALID; nearest_face i32: the face's index inside mesh b for NEAR and INSIDE, else -1.
+ * Per query sums i64 [10]: 0 tested, 1 near, 2 inside, 3 invalid, 4 status, 5 the bits of the largest d over the inside
+ * vertices as an fp64 (0 without one; non-negative doubles order like their bit patterns), 6 the sum of llrint(d * 2^32) over
+ * the inside vertices, 7..9 the sums of llrint(delta_k * 65536) (= (c - p)_k in metres * 2^32), k = x, y, z, over the inside
+ * vertices: the push that takes a out of b.  All integer sums (ballot popcounts, wave sums, one 64-bit atomic per term behind
+ * a memset that is part of the call): a query's outputs depend on its two meshes and contact_tol_m alone, not on the batch, its
+ * place in it, or scheduling.
+ * meshes_host and queries_host are read on the HOST before return.  n_rows: the capacity of code, signed_distance and
+ * nearest_face in rows, >= the sum of the a-meshes' nv.  Launches: one memset, setup per 128 meshes, the query table per 192
+ * queries, one kernel over (query, 64 vertices of a) items: four waves share b's faces, staged 512 at a time in LDS.
+ * Asynchronous on `stream`, no host synchronisation, no allocation; n_queries == 0 succeeds and launches nothing.  HM_ERR_ARG,
+ * with a message naming the entry point, before any device work: a negative count, contact_tol_m outside 0..1, a null required
+ * pointer, a buffer not aligned (16 bytes: workspace; 8: verts, sums; 4: faces, signed_distance, nearest_face), a bad mesh
+ * table, a query naming a mesh outside it, 2^31 or more rows or work items, n_rows or the workspace too small.
+ * Measured on an MI355X (tools/bench_penetration.py, profiles/penetration_bench.log; per call through the Python wrapper, host
+ * submission included, queries of 778 vertices against 1552 faces; in brackets the device time of the call's memset and launches):
+ * overlapping 16 queries 0.318 ms (0.309), 64 queries 0.548 ms (0.525), 256 queries 1.610 ms (1.311); disjoint (the early out) 0.143 ms
+ * (0.025), 0.428 ms (0.027), 1.545 ms (0.049): the wrapper's per-mesh packing, not the kernel; hm_mesh_score on the same point
+ * counts 0.163 / 0.167 / 0.182 ms: DESIGN.md section 10.7. */
+enum { HM_PEN_FAR = 0, HM_PEN_NEAR = 1, HM_PEN_INSIDE = 2, HM_PEN_INVALID = 3 };
+enum { HM_PEN_OK = 0, HM_PEN_DISJOINT = 1, HM_PEN_TOO_LARGE = 2 };
+typedef struct hm_pen_query { int32_t a, b; } hm_pen_query;            /* rows of the mesh table */
+size_t hm_mesh_penetration_workspace_bytes(int n_verts, int n_meshes, int n_queries);   /* 0 for illegal sizes */
+int hm_mesh_penetration(const double* verts, int n_verts, const int32_t* faces, int n_faces, const hm_mesh* meshes_host,
+                        int n_meshes, const hm_pen_query* queries_host, int n_queries, double contact_tol_m,
+                        uint8_t* code /* device [n_rows] */, float* signed_distance /* device [n_rows] */,
+                        int32_t* nearest_face /* device [n_rows] */, long long n_rows, int64_t* sums /* device [n_queries][10] */,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Detector evaluation (yolo/yolov7/test.py and utils/metrics.py): csrc/det_eval.hip.  The caller owns every buffer, the
  * calls are asynchronous on `stream`, nothing synchronises or allocates, argument errors return HM_ERR_ARG before any device
  * work.  All fp32 / fp64 arithmetic is plain IEEE in the order written (no FMA contraction, no fast-math).
