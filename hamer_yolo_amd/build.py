@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhamer_hip.so")
-SOURCES = ["status.hip", "gemm.hip", "norm.hip", "attention.hip", "patch.hip", "decoder.hip", "mano.hip", "tome.hip", "forward.hip", "prof.hip", "yolo.hip", "conv_f32.hip", "render.hip", "sar.hip", "sar_f32.hip", "gemm_f32.hip", "attention_f32.hip", "convnext.hip", "zrender.hip", "crop_aa.hip", "pose_eval.hip", "skeleton.hip", "det_eval.hip", "nms_batch.hip", "tta.hip", "mesh_eval.hip", "mask_eval.hip", "mask_boxes.hip", "depth_eval.hip", "depth_fit.hip", "mask_fit.hip", "visibility.hip", "penetration.hip"]
+SOURCES = ["status.hip", "gemm.hip", "norm.hip", "attention.hip", "patch.hip", "decoder.hip", "mano.hip", "tome.hip", "forward.hip", "prof.hip", "yolo.hip", "conv_f32.hip", "render.hip", "sar.hip", "sar_f32.hip", "gemm_f32.hip", "attention_f32.hip", "convnext.hip", "zrender.hip", "crop_aa.hip", "pose_eval.hip", "skeleton.hip", "det_eval.hip", "nms_batch.hip", "tta.hip", "mesh_eval.hip", "mask_eval.hip", "mask_boxes.hip", "depth_eval.hip", "depth_fit.hip", "mask_fit.hip", "visibility.hip", "penetration.hip", "motion.hip"]
 
 
 def _stale() -> bool:

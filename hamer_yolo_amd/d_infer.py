@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from .infer import *  # noqa: F401,F403
-from .infer import (FRAMES_PER_STEP, _default_models, _detection_list, _imread_bgr, _list_images, _antialias_args, _precise_hamer_args, _tta_args, apply_tta_args, _record_from, _render_args, _depth_args, depth_args, refine_records, _mask_fit_args, mask_fit_records, _visibility_args, visibility_records, _penetration_args, penetration_records, render_keypoint_args, apply_antialias_args, apply_precise_args, hamer_inference,  # noqa: F401
+from .infer import (FRAMES_PER_STEP, _default_models, _detection_list, _imread_bgr, _list_images, _antialias_args, _precise_hamer_args, _tta_args, apply_tta_args, _record_from, _render_args, _depth_args, depth_args, refine_records, _mask_fit_args, mask_fit_records, _visibility_args, visibility_records, _penetration_args, penetration_records, _smooth_args, smooth_args, smooth_records, render_keypoint_args, apply_antialias_args, apply_precise_args, hamer_inference,  # noqa: F401
                     hamer_opt, hand_record, iter_folder_results, load_intrinsics, reconstruct_and_save_obj_with_wrapper)
 from .rootnet.Model_RGB import get_model  # noqa: F401
 
@@ -63,6 +63,7 @@ def _parser() -> argparse.ArgumentParser:
     _depth_args(ap)
     _visibility_args(ap)
     _penetration_args(ap)
+    _smooth_args(ap)
     return ap
 
 
@@ -80,6 +81,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     keypoint_kw = render_keypoint_args(ap, args)
     depth_args(ap, args)
+    smooth_args(ap, args)
     if not args.masks and (args.mask_fit != "none" or args.mask_label != 3):
         ap.error("--mask-fit / --mask-label need --masks DIR")
     if not 1 <= args.mask_label <= 255:
@@ -100,6 +102,9 @@ def main(argv=None):
     if args.penetration or args.resolve_penetration:               # after the refinements: they move the hands
         from .infer import _rank_world
         penetration_records(args, hamer, *_rank_world(None, None))
+    if args.smooth_tracks:                                         # after every step that moves a hand, before every step that reads one
+        from .infer import _rank_world
+        smooth_records(args, hamer, *_rank_world(None, None))
     if args.visibility:
         from .infer import _rank_world
         visibility_records(args, hamer, *_rank_world(None, None))

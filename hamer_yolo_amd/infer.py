@@ -1215,6 +1215,7 @@ def _parser() -> argparse.ArgumentParser:
     _depth_args(ap)
     _visibility_args(ap)
     _penetration_args(ap)
+    _smooth_args(ap)
     return ap
 
 
@@ -1315,6 +1316,36 @@ def penetration_records(args, hamer, rank: int, world: int) -> None:
     else:
         r = EP.annotate_folder(args.output, args.output, hamer, rank=rank, world=world)
         print(f"{r['annotated']} two-hand records annotated with penetration, {r['penetrating']} interpenetrate" + (f" (rank {rank})" if world > 1 else ""))
+
+
+def _smooth_args(ap: argparse.ArgumentParser) -> None:
+    ap.add_argument('--smooth-tracks', action='store_true',
+                    help="after the records are written (and after any --mask-fit / --depth-maps / --penetration step), treat the "
+                         "folder as one video and rewrite the records in place smoothed over time, missing hands filled: new "
+                         "pose_global, pose_hand, theta, betas, cam_t, the old ones as *_unsmoothed, track_status, track_pairs, "
+                         "track_moved_deg, track_filled (evaluate_motion --smooth-to); before --visibility, --obj, --render, --hand-maps")
+    ap.add_argument('--smooth-radius', type=int, default=None, metavar="R", help="with --smooth-tracks: frames each way, 0..32 (default 4)")
+    ap.add_argument('--smooth-sigma', type=float, default=None, metavar="S", help="with --smooth-tracks: the Gaussian window's sigma in frames (default 2)")
+    ap.add_argument('--smooth-fill', type=int, default=None, metavar="K",
+                    help="with --smooth-tracks: fill a missing hand only from neighbours at most K frames away (default 2; 0: never)")
+
+
+def smooth_args(ap: argparse.ArgumentParser, args) -> None:
+    """Usage errors of the smoothing options: the sub-flags need ``--smooth-tracks``; the defaults are filled in."""
+    from .evaluate_motion import smooth_options
+    args.smooth_radius, args.smooth_sigma, args.smooth_fill = smooth_options(
+        ap, args.smooth_tracks, "--smooth-tracks", {"radius": "--smooth-radius", "sigma": "--smooth-sigma", "max_fill": "--smooth-fill"},
+        args.smooth_radius, args.smooth_sigma, args.smooth_fill)
+
+
+def smooth_records(args, hamer, rank: int, world: int) -> None:
+    """The ``--smooth-tracks`` step of the drivers: the records of ``--output`` are rewritten in place, smoothed over time.  The
+    filter needs the whole sequence, so rank 0 alone runs it, over the whole folder; the callers put it between two barriers."""
+    if rank != 0:
+        return
+    from . import evaluate_motion as EMO
+    r = EMO.smooth_folder(args.output, args.output, hamer, args.smooth_radius, args.smooth_sigma, args.smooth_fill)
+    print(f"{r['smoothed']} hands smoothed over {r['records']} records, {r['filled']} filled, {r['kept']} kept, {r['degenerate']} degenerate")
 
 
 def mask_args(ap: argparse.ArgumentParser, args) -> None:
@@ -1428,6 +1459,7 @@ def main(argv=None):
     keypoint_kw = render_keypoint_args(ap, args)
     mask_args(ap, args)
     depth_args(ap, args)
+    smooth_args(ap, args)
     per_frame_k = bool(args.masks and args.intrinsics and os.path.isdir(args.intrinsics))      # (a folder of <name>.txt: records only)
     k_real = load_intrinsics(args.intrinsics) if args.intrinsics and not per_frame_k else None
     if args.ckpt:
@@ -1466,6 +1498,10 @@ def main(argv=None):
             dist.barrier()
     if args.penetration or args.resolve_penetration:               # after the refinements: they move the hands
         penetration_records(args, hamer, rank, world)
+        if world > 1:
+            dist.barrier()
+    if args.smooth_tracks:                                         # after every step that moves a hand, before every step that reads one
+        smooth_records(args, hamer, rank, world)                   # (the barrier of the step before stands in front)
         if world > 1:
             dist.barrier()
     if args.visibility:

@@ -53,6 +53,7 @@ EXPORTS = [
     "hm_mask_fit_workspace_bytes", "hm_mask_fit",
     "hm_point_visibility", "hm_mesh_coverage_workspace_bytes", "hm_mesh_coverage",
     "hm_mesh_penetration_workspace_bytes", "hm_mesh_penetration",
+    "hm_track_smooth", "hm_track_jitter",
 ]
 KIND_NAMES = ["gemm", "layernorm", "attention", "im2col", "linear_f32", "cross_attn", "mano", "crop", "conv", "other"]
 
@@ -347,6 +348,8 @@ def load() -> C.CDLL:
     lib.hm_mesh_penetration_workspace_bytes.restype = C.c_size_t
     lib.hm_mesh_penetration.argtypes = [vp, i, vp, i, C.POINTER(Mesh), i, C.POINTER(PenQuery), i, d, vp, vp, vp, C.c_longlong, vp, vp,
                                         C.c_size_t, vp]
+    lib.hm_track_smooth.argtypes = [vp, vp, vp, i, i, i, i, C.POINTER(d), i, vp, vp, vp, vp, vp, vp, vp]
+    lib.hm_track_jitter.argtypes = [vp, vp, i, i, i, vp, vp]
     lib.hm_skeleton_overlay_workspace_bytes.argtypes = [i, i, i, i]
     lib.hm_skeleton_overlay_workspace_bytes.restype = C.c_size_t
     lib.hm_skeleton_overlay.argtypes = [vp, i, i, i, vp, i, C.POINTER(Skeleton), i, C.POINTER(C.c_uint8), i, vp, vp, C.c_size_t, vp]

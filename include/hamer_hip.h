@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32) and the additive fp32 HaMeR entry points (hm_gemm_f32, hm_vit_attention_f32; hm_hamer_forward, hm_patch_im2col and hm_cross_attention take HM_DTYPE_F32) and the additive ConvNeXt SAR entry points (hm_dwconv7_ln, hm_ln_patchify2, hm_stem4_im2col, hm_sar_saigb_ch) and the additive attention test hook (hm_attention_grid, HM_OPT_ATT_GRID) and the additive hand-metric entry point (hm_pose_eval) and the additive depth-fit entry points (hm_depth_fit_workspace_bytes, hm_depth_fit: the existing tests pin 402); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
+#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32) and the additive fp32 HaMeR entry points (hm_gemm_f32, hm_vit_attention_f32; hm_hamer_forward, hm_patch_im2col and hm_cross_attention take HM_DTYPE_F32) and the additive ConvNeXt SAR entry points (hm_dwconv7_ln, hm_ln_patchify2, hm_stem4_im2col, hm_sar_saigb_ch) and the additive attention test hook (hm_attention_grid, HM_OPT_ATT_GRID) and the additive hand-metric entry point (hm_pose_eval) and the additive depth-fit entry points (hm_depth_fit_workspace_bytes, hm_depth_fit: the existing tests pin 402) and the additive motion entry points (hm_track_smooth, hm_track_jitter: checked by export name); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
 
 enum { HM_DTYPE_BF16 = 0, HM_DTYPE_F16 = 1,
        HM_DTYPE_F32 = 2 /* same value as HM_OUT_F32.  The fp32 YOLOv7 route (its section below) and the precise HaMeR route
@@ -1255,6 +1255,59 @@ int hm_mesh_penetration(const double* verts, int n_verts, const int32_t* faces, 
                         uint8_t* code /* device [n_rows] */, float* signed_distance /* device [n_rows] */,
                         int32_t* nearest_face /* device [n_rows] */, long long n_rows, int64_t* sums /* device [n_queries][10] */,
                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Motion: csrc/motion.hip.  The first entry points that look across frames.  A sequence is N
+ * frames by S tracks (the drivers: S = 2, right and left); nothing associates hands, a track is one column.  Everything is fp64
+ * without contraction in the order written; tests/motion_rule.py restates it in numpy and the kernels equal it byte for byte.
+ *
+ * hm_track_smooth: a zero-phase filter of rotations as rotations.
+ *   rot [N][S][J][9] f64 (3 x 3, row-major), lin [N][S][C] f64, present [N][S] u8 (non-zero: present);
+ *   weights_host [R + 1] f64, 0 <= R <= HM_MOTION_MAX_RADIUS, read on the HOST before return and passed to the kernel as
+ *   arguments (the callers make them as w[0] = 1, w[k] = exp(-0.5 (k / sigma)^2): the kernel calls no exp and no trigonometry).
+ * The symmetric-pair window of frame t of a track, for every element A of the rotations and channels alike:
+ *   acc = w[0] * A[t], W = w[0] when t is present, else acc = 0, W = 0;
+ *   for k = 1 .. R, only when t - k >= 0, t + k < N and both are present (a PAIR):
+ *     acc = acc + w[k] * (A[t-k] + A[t+k]);  W = W + 2.0 * w[k].
+ * Offsets count only as pairs, so a track of constant velocity (a fixed axis and rate; channels linear in t) comes back
+ * unchanged for any presence pattern and at both ends, and a missing frame is interpolated by the same sum.
+ * pairs [N][S] i32: the pairs used; nearest_pair: the smallest k used, 0 without one.  Without a pair the outputs are the
+ * input's bytes (present: HM_TRACK_KEPT) or NaN (absent: HM_TRACK_ABSENT).  With one:
+ *   linear channels: acc / W.
+ *   rotations: M = acc / W element by element.  With the cofactor matrix
+ *     c00 = m11 m22 - m12 m21   c01 = m12 m20 - m10 m22   c02 = m10 m21 - m11 m20
+ *     c10 = m02 m21 - m01 m22   c11 = m00 m22 - m02 m20   c12 = m01 m20 - m00 m21
+ *     c20 = m01 m12 - m02 m11   c21 = m02 m10 - m00 m12   c22 = m00 m11 - m01 m10
+ *   and det = (m00 c00 + m01 c01) + m02 c02, the rotation is degenerate unless det M >= 1/64 (a NaN is degenerate); else
+ *   X = M and exactly 12 times X <- (X + cof(X) / det X) * 0.5, element by element: Newton's iteration for the polar factor,
+ *   the rotation nearest M (on the CPU every window with det >= 1/64 had converged to fp64 after 9 steps).
+ * status [N][S] i32: HM_TRACK_SMOOTHED (present) or HM_TRACK_FILLED (absent) when there is a pair and none of the J rotations is
+ * degenerate; HM_TRACK_DEGENERATE when one is: every output of the hand, channels included, is then the input's bytes
+ * (present) or NaN (absent), so a hand never mixes filtered and raw joints.  pairs and nearest_pair are what was counted either way.
+ * moved [N][S][J] f64: for HM_TRACK_SMOOTHED ((((0 + d0 d0) + d1 d1) + ...) + d8 d8), d = output - input over the 9 elements
+ * in row-major order -- the squared Frobenius distance, 8 sin^2(angle / 2) between rotations -- and NaN for every other status.
+ * rot_out and lin_out never alias rot and lin.  Launch: one kernel; a workgroup is (32 frames, track), its 256 threads 32
+ * frames x 8 units (a rotation, or 9 channels), the units in passes of 8 with the tile and a halo of R frames on each side in
+ * LDS (at most 54 KiB); one flag per frame in LDS carries the degenerate decision across the passes.  A (frame, track)'s bytes
+ * depend on its own window only: not on N, S or the tile.  N == 0 or S == 0 succeeds without a launch.  HM_ERR_ARG before any
+ * device work: a negative count, R outside 0..32, a weight outside 0..1 or NaN, a null pointer where its count is positive,
+ * a misaligned array, in-place outputs, 2^31 or more frames x tracks.
+ *
+ * hm_track_jitter: the acceleration of point tracks.  points [N][S][P][3] f64, 1 <= P <= HM_MOTION_MAX_POINTS; accel [N][S] f64:
+ * where t - 1, t and t + 1 lie in the sequence and are present, the mean over the P points of |x[t-1] - 2 x[t] + x[t+1]|, NaN
+ * elsewhere.  Per point d = (x[t-1] - 2.0 * x[t]) + x[t+1] per coordinate, n = sqrt((dx dx + dy dy) + dz dz); a wave per
+ * (frame, track): lane l adds the n of points l, l + 64, ... in this order to 0.0, the lanes meet as v[l] = v[l] + v[l + o]
+ * for o = 32, 16, 8, 4, 2, 1, and accel = v[0] / (double)P.  The same conventions and errors; P > 1024 is HM_ERR_ARG.
+ * Measured on an MI355X (tools/bench_motion.py, profiles/motion_bench.log; S = 2, J = 16, C = 13, per call through the Python
+ * wrapper, in brackets the device time of the launch): hm_track_smooth, R = 4, N = 64 / 1024 / 16384: 0.049 (0.034) / 0.051
+ * (0.034) / 0.127 (0.096) ms; R = 32: 0.075 (0.065) / 0.084 (0.072) / 0.206 (0.182) ms; hm_track_jitter, N = 16384, P = 21 / 778:
+ * 0.023 (0.015) / 0.154 (0.147) ms: DESIGN.md section 10.8. */
+#define HM_MOTION_MAX_RADIUS 32
+#define HM_MOTION_MAX_POINTS 1024
+enum { HM_TRACK_KEPT = 0, HM_TRACK_SMOOTHED = 1, HM_TRACK_FILLED = 2, HM_TRACK_ABSENT = 3, HM_TRACK_DEGENERATE = 4 };
+int hm_track_smooth(const double* rot, const double* lin, const uint8_t* present, int N, int S, int J, int C,
+                    const double* weights_host, int R, double* rot_out, double* lin_out, int32_t* status, int32_t* pairs,
+                    int32_t* nearest_pair, double* moved, void* stream);
+int hm_track_jitter(const double* points, const uint8_t* present, int N, int S, int P, double* accel, void* stream);
 
 /* ---- Detector evaluation (yolo/yolov7/test.py and utils/metrics.py): csrc/det_eval.hip.  The caller owns every buffer, the
  * calls are asynchronous on `stream`, nothing synchronises or allocates, argument errors return HM_ERR_ARG before any device
