@@ -3570,8 +3570,8 @@ extern "C" int hm_gemm(const hm_gemm_args* a, void* stream_) {
   return hm_set_error(HM_ERR_ARG, "hm_gemm: dtype must be HM_DTYPE_BF16 or HM_DTYPE_F16");
 }
 
-extern "C" int hm_gemm_fp8(const hm_gemm_fp8_args* a, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
+// Argument checks of hm_gemm_fp8 and the kernel arguments it launches with.
+static int fp8_prepare(const hm_gemm_fp8_args* a, KArgs& k) {
   if (!a) return hm_set_error(HM_ERR_ARG, "hm_gemm_fp8: null args");
   const hm_gemm_fp8_args& g = *a;
   if (g.M <= 0 || g.N <= 0 || g.K <= 0 || g.M % 16 != 0 || g.N % 64 != 0 || g.K % 128 != 0)
@@ -3585,27 +3585,47 @@ extern "C" int hm_gemm_fp8(const hm_gemm_fp8_args* a, void* stream_) {
   if (g.epilogue == HM_EPI_RESID_F32 && (!g.resid || g.ldr < g.N || g.ldr % 4 != 0))
     return hm_set_error(HM_ERR_ARG, "hm_gemm_fp8: residual epilogue needs resid and ldr >= N, ldr % 4 == 0");
   if (g.epilogue == HM_EPI_GELU_MX8 && !g.out_scales) return hm_set_error(HM_ERR_ARG, "hm_gemm_fp8: HM_EPI_GELU_MX8 needs out_scales");
-  KArgs k{};
+  if (g.epilogue != HM_EPI_STORE && g.epilogue != HM_EPI_RESID_F32 && g.epilogue != HM_EPI_GELU_MX8)
+    return hm_set_error(HM_ERR_ARG, "hm_gemm_fp8: epilogue must be STORE, RESID_F32 or GELU_MX8");
+  if (g.epilogue == HM_EPI_STORE && g.out_dtype != HM_DTYPE_BF16)
+    return hm_set_error(HM_ERR_ARG, "hm_gemm_fp8: HM_EPI_STORE writes bf16 (out_dtype HM_DTYPE_BF16)");
+  k = KArgs{};
   k.X = g.X8; k.W = g.W8; k.C = g.C; k.bias = g.bias; k.resid = g.resid;
   k.M = g.M; k.N = g.N; k.K = g.K; k.ldx = g.ldx; k.ldw = g.ldw; k.ldc = g.ldc; k.ldr = g.ldr; k.resid_mod = 0;
   k.group_m = g_group_m; k.ksplit = 1;
   k.xs = (const unsigned char*)g.x_scales; k.wscale = g.w_scale; k.out_scales = (unsigned char*)g.out_scales;
+  return HM_OK;
+}
+
+// Whether the persistent kernel takes a checked problem.  RESID_F32: the persistent form is bit-identical, measured NOT faster
+// (all workgroups reach their 512 KB-per-tile epilogues in lockstep; the one-tile kernel's workgroups drift apart and spread
+// that traffic): opt-in, hm_set_option(HM_OPT_FP8P_RESID, 1)
+static bool fp8_takes_persistent(const KArgs& k, int epilogue) {
+  switch (epilogue) {
+    case HM_EPI_STORE: return fp8p_ok(k) && (k.ldc & 7) == 0;
+    case HM_EPI_RESID_F32: return hm_option(HM_OPT_FP8P_RESID) != 0 && fp8p_ok(k) && k.resid_mod == 0 && (k.ldr & 3) == 0 && (k.ldc & 3) == 0;
+    case HM_EPI_GELU_MX8: return fp8p_ok(k) && (k.ldc & 15) == 0;
+    default: return false;
+  }
+}
+
+extern "C" int hm_gemm_fp8_persistent(const hm_gemm_fp8_args* a) {
+  KArgs k{};
+  if (fp8_prepare(a, k) != HM_OK) return -1;
+  return fp8_takes_persistent(k, a->epilogue) ? 1 : 0;
+}
+
+extern "C" int hm_gemm_fp8(const hm_gemm_fp8_args* a, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  KArgs k{};
+  if (const int rc = fp8_prepare(a, k)) return rc;
+  const hm_gemm_fp8_args& g = *a;
   HmProfScope prof(HM_K_GEMM, 16 + g.epilogue, g.M, g.N, g.K, stream);
+  const bool persistent = fp8_takes_persistent(k, g.epilogue);
   switch (g.epilogue) {
-    case HM_EPI_STORE:
-      if (g.out_dtype != HM_DTYPE_BF16) return hm_set_error(HM_ERR_ARG, "hm_gemm_fp8: HM_EPI_STORE writes bf16 (out_dtype HM_DTYPE_BF16)");
-      if (fp8p_ok(k) && (g.ldc & 7) == 0) return launch_fp8p<HM_EPI_STORE>(k, stream);
-      return launch_fp8<HM_EPI_STORE>(k, stream);
-    case HM_EPI_RESID_F32:
-      // persistent form: bit-identical, measured NOT faster (all workgroups reach their 512 KB-per-tile epilogues in
-      // lockstep; the one-tile kernel's workgroups drift apart and spread that traffic): opt-in, hm_set_option(HM_OPT_FP8P_RESID, 1)
-      if (hm_option(HM_OPT_FP8P_RESID) != 0 && fp8p_ok(k) && k.resid_mod == 0 && (k.ldr & 3) == 0 && (k.ldc & 3) == 0)
-        return launch_fp8p<HM_EPI_RESID_F32>(k, stream);
-      return launch_fp8<HM_EPI_RESID_F32>(k, stream);
-    case HM_EPI_GELU_MX8:
-      if (fp8p_ok(k) && (g.ldc & 15) == 0) return launch_fp8p<HM_EPI_GELU_MX8>(k, stream);
-      return launch_fp8<HM_EPI_GELU_MX8>(k, stream);
-    default: return hm_set_error(HM_ERR_ARG, "hm_gemm_fp8: epilogue must be STORE, RESID_F32 or GELU_MX8");
+    case HM_EPI_STORE: return persistent ? launch_fp8p<HM_EPI_STORE>(k, stream) : launch_fp8<HM_EPI_STORE>(k, stream);
+    case HM_EPI_RESID_F32: return persistent ? launch_fp8p<HM_EPI_RESID_F32>(k, stream) : launch_fp8<HM_EPI_RESID_F32>(k, stream);
+    default: return persistent ? launch_fp8p<HM_EPI_GELU_MX8>(k, stream) : launch_fp8<HM_EPI_GELU_MX8>(k, stream);
   }
 }
 

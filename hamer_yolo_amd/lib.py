@@ -38,7 +38,7 @@ EXPORTS = [
     "hm_gemm_f32", "hm_vit_attention_f32",
     "hm_dwconv7_ln", "hm_ln_patchify2", "hm_stem4_im2col", "hm_sar_saigb_ch",
     "hm_mesh_render_workspace_bytes", "hm_mesh_render",
-    "hm_attention_grid",
+    "hm_attention_grid", "hm_gemm_fp8_persistent",
     "hm_crop_aa_box_from_bbox", "hm_crop_batch_aa",
     "hm_pose_eval",
     "hm_skeleton_overlay_workspace_bytes", "hm_skeleton_overlay",
@@ -255,6 +255,7 @@ def load() -> C.CDLL:
     lib.hm_hamer_forward.argtypes = [C.POINTER(HamerWeights), vp, i, C.POINTER(HamerOutputs), vp, C.c_size_t, vp]
     lib.hm_ln_finalize.argtypes = [vp, vp, i, i, C.c_float, vp]
     lib.hm_gemm_fp8.argtypes = [C.POINTER(GemmFp8Args), vp]
+    lib.hm_gemm_fp8_persistent.argtypes = [C.POINTER(GemmFp8Args)]
     lib.hm_layernorm_mx8.argtypes = [vp, vp, vp, vp, vp, i, i, C.c_float, vp]
     lib.hm_vit_attention_mx8.argtypes = [vp, vp, vp, i, i, i, i, C.c_float, vp]
     lib.hm_nchw3_to_nhwc8.argtypes = [vp, vp, i, i, i, i, vp]

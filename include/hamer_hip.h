@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32) and the additive fp32 HaMeR entry points (hm_gemm_f32, hm_vit_attention_f32; hm_hamer_forward, hm_patch_im2col and hm_cross_attention take HM_DTYPE_F32) and the additive ConvNeXt SAR entry points (hm_dwconv7_ln, hm_ln_patchify2, hm_stem4_im2col, hm_sar_saigb_ch) and the additive attention test hook (hm_attention_grid, HM_OPT_ATT_GRID) and the additive hand-metric entry point (hm_pose_eval) and the additive depth-fit entry points (hm_depth_fit_workspace_bytes, hm_depth_fit: the existing tests pin 402) and the additive motion entry points (hm_track_smooth, hm_track_jitter: checked by export name); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
+#define HM_VERSION 402   /* 402 also carries the additive SAR mesh-head entry points (hm_sar_saigb, hm_sar_graph_mix, hm_sar_linear, hm_sar_softargmax, hm_sar_postprocess) and the additive mesh overlay entry points (hm_mesh_overlay, hm_mesh_overlay_workspace_bytes: lib.load() checks them by export name, and the fp32 route's tests pin 402) and the additive fp32 RootNet / SAR entry points (hm_conv2d_f32_relu, hm_nchw3_to_nhwc8_f32, hm_gap_linear_f32, hm_sar_saigb_f32, hm_sar_graph_mix_f32, hm_sar_linear_f32) and the additive fp32 HaMeR entry points (hm_gemm_f32, hm_vit_attention_f32; hm_hamer_forward, hm_patch_im2col and hm_cross_attention take HM_DTYPE_F32) and the additive ConvNeXt SAR entry points (hm_dwconv7_ln, hm_ln_patchify2, hm_stem4_im2col, hm_sar_saigb_ch) and the additive attention test hook (hm_attention_grid, HM_OPT_ATT_GRID) and the additive hand-metric entry point (hm_pose_eval) and the additive depth-fit entry points (hm_depth_fit_workspace_bytes, hm_depth_fit: the existing tests pin 402) and the additive motion entry points (hm_track_smooth, hm_track_jitter: checked by export name) and the additive fp8 route query (hm_gemm_fp8_persistent: checked by export name); 402: HM_DTYPE_F32 (the fp32 YOLOv7 route: conv, maxpool, upsample, letterbox, hm_yolo_run); 401: hm_conv2d_stem_pair, HM_OP_CONV_PAIR, HM_OPT_CONV_STEM_PAIR; 400 = round 4: hm_option_count, hm_gemm_px_grid (302 = round 3: hm_set_option, hm_hamer_weights.tome_r) -- lib.load() checks it */
 
 enum { HM_DTYPE_BF16 = 0, HM_DTYPE_F16 = 1,
        HM_DTYPE_F32 = 2 /* same value as HM_OUT_F32.  The fp32 YOLOv7 route (its section below) and the precise HaMeR route
@@ -137,6 +137,11 @@ typedef struct hm_gemm_fp8_args {
   int out_dtype;      /* HM_EPI_STORE: HM_DTYPE_BF16 or HM_DTYPE_F16 */
 } hm_gemm_fp8_args;
 int hm_gemm_fp8(const hm_gemm_fp8_args* args, void* stream);
+/* Host-side query, no device work: 1 when hm_gemm_fp8 runs `args` on the persistent kernel (whole 256 x 256 tiles, at least 8,
+ * K >= 256, a bias, the leading dimensions it needs, under the current HM_OPT_FP8_ONE_TILE / HM_OPT_FP8P_RESID), 0 when on the
+ * one-tile kernel, -1 when hm_gemm_fp8 would refuse them (hm_last_error_string says why).  hm_gemm_fp8 dispatches on the same
+ * function, so a test that asserts the route cannot disagree with the launch. */
+int hm_gemm_fp8_persistent(const hm_gemm_fp8_args* args);
 /* nn.LayerNorm with MXFP8 output (the X operand of hm_gemm_fp8): out8 [M][D] e4m3, out_scales [D/32][M] E8M0.  D % 32 == 0. */
 int hm_layernorm_mx8(const float* x, const float* gamma, const float* beta, void* out8, void* out_scales, int M, int D,
                      float eps, void* stream);

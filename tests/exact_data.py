@@ -22,6 +22,11 @@ own: a dyadic MANO model with signed-permutation rotations, for which mano_rule 
 in any order; three-valued logits whose fp32 sigmoid is exactly 1/2, 1 or 0 for the decode; integer features over a
 power-of-two HW for the pooled linear layer; values every output type holds for the two layout kernels.
 
+The fp8 GEMMs run all three epilogues on the exact integers (fp8_epilogue_case): hashed integer bias and residual for the fp32 and
+bf16 outputs, and for GELU -> MXFP8 a bias that keeps every |v| >= 16, where the GELU is exactly max(v, 0), with block maxima on
+both sides of 448 2^k.  The attention kernels (section "attention") get code-book data whose softmax is exactly few-hot: P is 1
+on the m in {1, 2, 4} keys of a hashed group and 0 elsewhere, so the output is one rounding of sum / m.
+
 Plain helper module (imported like sar_rule.py); torch and numpy on the CPU only, nothing here touches the compiled library.
 """
 import numpy as np
@@ -90,15 +95,15 @@ def conv_case(n, Ci, Co, k, H, W):
     return x, w, b
 
 
-def fp8_case(M, N, K):
+def fp8_case(M, N, K, ws_range=1):
     """MXFP8 operands whose every product and sum is exact: xi (M,K) in -4..4 and wi (N,K) in -3..3 (integers that e4m3
-    holds exactly), E8M0 block scales xs (K/32, M) of 2^-1..2^2 and per-row weight scales ws (N,) of 2^-1..2^1.
-    Returns x8, xs, w8, ws (the bytes and scales the kernel takes) and xi, wi (the same values as fp32)."""
+    holds exactly), E8M0 block scales xs (K/32, M) of 2^-1..2^2 and per-row weight scales ws (N,) of 2^-1..2^1 (ws_range = 2:
+    2^-2..2^2).  Returns x8, xs, w8, ws (the bytes and scales the kernel takes) and xi, wi (the same values as fp32)."""
     sd = _shape_seed(M, N, K)
     xi = ints("exact.fp8.x", (M, K), -4, 4, sd)
     wi = ints("exact.fp8.w", (N, K), -3, 3, sd)
     xs = (127 + ints("exact.fp8.xs", (K // 32, M), -1, 2, sd)).to(torch.uint8)
-    ws = torch.ldexp(torch.ones(N), ints("exact.fp8.ws", (N,), -1, 1, sd).to(torch.int32))
+    ws = torch.ldexp(torch.ones(N), ints("exact.fp8.ws", (N,), -ws_range, ws_range, sd).to(torch.int32))
     x8 = xi.to(torch.float8_e4m3fn)
     w8 = wi.to(torch.float8_e4m3fn)
     assert torch.equal(x8.float(), xi) and torch.equal(w8.float(), wi)            # e4m3-exact
@@ -113,6 +118,69 @@ def fp8_reference(xi, xs, wi, ws):
     sx = torch.ldexp(torch.ones((), dtype=torch.float64), xs.to(torch.int32) - 127)        # (K/32, M)
     xd = xi.double() * sx.t().repeat_interleave(32, dim=1)
     return xd @ (wi.double() * ws.double()[:, None]).t()
+
+
+FP8_BIAS_RANGE, FP8_RESID_RANGE = 32, 510
+FP8_GELU_EXACT = 16.0                     # |v| >= 16: exp2(-0.5 log2e v^2) <= 2^-184 is zero, both GELUs give max(v, 0) exactly
+FP8_ZERO_BLOCKS = 5                       # about one 32-column block in five has a negative bias throughout and comes out all zero
+# In the seeds of bias, resid and the GELU bias, as LN_SALT; and the exponent range of ws in these cases.  With ws in 2^-1..2^1
+# the fault "row scales rotated" stays under 40 % of the GELU -> MXFP8 bytes at most shapes whatever the salt; with 2^-2..2^2 this
+# is the first salt under which every listed shape meets every fault fraction of tests/test_exact_data_host.py.
+FP8_SALT = 17
+FP8_EPILOGUE_WS_RANGE = 2
+
+
+def fp8_epilogue_case(M, N, K):
+    """fp8_case plus what the three epilogues of hm_gemm_fp8 need to be exact, as a dict:
+    x8, xs, w8, ws, xi, wi   the operands of fp8_case(M, N, K, FP8_EPILOGUE_WS_RANGE);
+    acc (M, N) fp64           the scaled product, ws applied;
+    bias (N,), resid (M, N)   hashed integers in +-FP8_BIAS_RANGE and +-FP8_RESID_RANGE: STORE expects acc + bias rounded once
+                              to bf16, RESID_F32 expects acc + bias + resid, every sum exact in fp32 (asserted);
+    gelu_bias (N,)            sign_n (448 2^kb - off): kb hashed per 32-column block in k0 .. k0 + 2 with
+                              k0 = ceil(log2((A + 16 + 2 sigma) / 448)), off = round(1.6 sigma), A and sigma the maximum and
+                              the standard deviation of |acc|; sign_n hashed per column and negative over whole blocks for
+                              about a fifth of them.  v = acc + gelu_bias has |v| >= 16 everywhere (asserted), where the GELU is
+                              exactly max(v, 0), and the block maxima straddle 448 2^kb, so the scale bytes depend on the row
+                              and on the block; an all-negative block is all zero with the scale byte 0;
+    positive (N,) bool        the columns whose bias is positive."""
+    x8, xs, w8, ws, xi, wi = fp8_case(M, N, K, FP8_EPILOGUE_WS_RANGE)
+    sd = _shape_seed(M, N, K, FP8_SALT)
+    acc = fp8_reference(xi, xs, wi, ws)
+    bias = ints("exact.fp8.bias", (N,), -FP8_BIAS_RANGE, FP8_BIAS_RANGE, sd)
+    resid = ints("exact.fp8.resid", (M, N), -FP8_RESID_RANGE, FP8_RESID_RANGE, sd)
+    sx = torch.ldexp(torch.ones(()), xs.to(torch.int32) - 127)
+    unit = float(sx.min()) * float(ws.min())
+    bound = exact_bound(xi, wi, K, bias, resid, scale=float(sx.max()) * float(ws.max()), unit=unit)
+    assert bound < EXACT_LIMIT, (M, N, K, bound)
+    for t in (acc + bias.double(), acc + bias.double() + resid.double()):
+        assert torch.equal(t.float().double(), t)
+    a = acc.abs()
+    A, sigma = float(a.max()), float(a.std())
+    k0 = int(np.ceil(np.log2((A + FP8_GELU_EXACT + 2 * sigma) / 448.0)))
+    off = float(round(1.6 * sigma))
+    nblk = N // 32
+    kb = (k0 + ints("exact.fp8.gelu.kb", (nblk,), 0, 2, sd)).to(torch.int32).repeat_interleave(32)
+    sign = 2 * ints("exact.fp8.gelu.sign", (N,), 0, 1, sd) - 1
+    dead = (ints("exact.fp8.gelu.dead", (nblk,), 0, FP8_ZERO_BLOCKS - 1, sd) == 0).repeat_interleave(32)
+    sign = torch.where(dead, -torch.ones(N), sign)
+    gb = sign * (torch.ldexp(torch.full((N,), 448.0), kb) - off)
+    v = acc + gb.double()
+    assert float(v.abs().min()) >= FP8_GELU_EXACT, (M, N, K, float(v.abs().min()))
+    assert torch.equal(v.float().double(), v) and float(v.abs().max()) / unit < EXACT_LIMIT
+    return {"x8": x8, "xs": xs, "w8": w8, "ws": ws, "xi": xi, "wi": wi, "acc": acc, "bias": bias, "resid": resid,
+            "gelu_bias": gb, "positive": sign > 0}
+
+
+def fp8_gelu_expect(v):
+    """(bytes (M, N), scales (N/32, M)) of GELU -> MXFP8 on v with |v| >= FP8_GELU_EXACT: the oracle quantiser on max(v, 0)."""
+    from oracle import fp8_ref as Q
+    v = v.float()
+    return Q.mx8_quantize(torch.where(v > 0, v, torch.zeros_like(v)))
+
+
+def fp8_unsigned_zero(b):
+    """e4m3 bytes with -0 (0x80) written as +0: the kernels' GELU gives +0 where torch's gives -0."""
+    return torch.where(b == 0x80, torch.zeros_like(b), b)
 
 
 # ------------------------------------------------------------------------------------------------ LayerNorm
@@ -290,6 +358,13 @@ GEMM_F32_RAGGED = [(1, 1280 - 32, 768), (1, 3840 - 32, 1280)]
 GEMM_F32_STRIDED = [(192, 1280, 1280), (77, 100, 96)]
 # hm_gemm_fp8
 GEMM_FP8 = [(272, 320, 384)]
+# hm_gemm_fp8 with its three epilogues: the one-tile kernel (HM_OPT_FP8_ONE_TILE where a shape would go persistent) ...
+GEMM_FP8_ONE_TILE = [(16, 64, 128), (240, 192, 256), (272, 320, 384), (528, 576, 128), (256, 256, 5120), (768, 768, 1280)]
+# ... and the persistent one: (M, N, K, HM_OPT_FP8P_GRID settings).  (768, 768, 384) on 8 workgroups: 9 tiles of three K-steps,
+# one workgroup takes two with the ring parity flipped between them; (1024, 1280, 384): 20 tiles, XCD runs of 3 and 2
+GEMM_FP8_PERSISTENT = [(512, 1024, 256, (0,)), (768, 768, 384, (8,)), (1024, 1280, 384, (8,)), (1280, 1024, 1280, (8, 16))]
+GEMM_FP8_WIDE = [(272, 320, 384), (768, 768, 384)]                        # run with wide leading dimensions
+GEMM_FP8_NO_BIAS = [(512, 1024, 256), (272, 320, 384)]
 # hm_conv2d_nhwc, (n, Ci, Co, k, stride, H, W)
 CONV_BASIC = [(2, 16, 32, 3, 1, 9, 11)]
 CONV_EVERY_TILE = [(2, 16, 32, 3, 1, 9, 11), (2, 32, 264, 3, 2, 21, 19), (2, 64, 72, 1, 1, 33, 35), (2, 8, 256, 3, 1, 30, 34)]
@@ -1181,3 +1256,166 @@ def assert_exact(got, ref, what=""):
     """assert torch.equal(got, ref), with a message that locates the fault."""
     msg = mismatch_report(got, ref, str(what))
     assert msg is None, msg
+
+
+# ------------------------------------------------------------------------------------------------ attention
+# Code-book data whose softmax is exactly few-hot.  Per (crop, head) the keys are cut by a hashed permutation into groups of
+# 1, 2 or 4; group g has a hashed sign code u_g in {-1, +1}^80, every key of the group is 8 u_g and every query is 8 u_g of the
+# group of ONE key it is dealt by a second hashed permutation (so every key index is some query's chosen key).  q.k is 5120 on
+# the query's own group and 64 (u_g . u_h) elsewhere; with the log2-domain scale 2^-3 the top scores are all exactly 640, the
+# exponent of the chosen keys is exactly 0 and every other key lies at least ATT_GAP log2 units below, where an fp32 exponential
+# is exactly zero (2^-149 is the smallest fp32 subnormal).  P is then 1 on the m keys of the group, the row sum m, 1 / m exact,
+# and the accumulator the integer-valued sum of the group's V rows: the output is one rounding of an exactly known number.
+ATT_T, ATT_HD, ATT_HDP = 192, 80, 96
+ATT_LOG2E = np.float32(1.44269504088896340736)        # the constant launch_att multiplies the scale by, as fp32
+ATT_C = 2.0 ** -3                                     # the log2-domain scale every exact case runs at
+ATT_SCALE_DENSE = float(np.float32(ATT_C / 1.44269504088896340736))      # * ATT_LOG2E in fp32 is exactly 2^-3 (asserted in the tests)
+ATT_SCALE_F32 = ATT_C                                 # attention_f32_kernel scales q first and uses expf
+ATT_GAP = 160.0
+# Goes into every seed, as LN_SALT does: the first salt under which every listed case meets the builder's assertions (gap,
+# coverage of every key and query tile, scale-byte variety) and the fault fractions of tests/test_exact_data_host.py.
+ATT_SALT = 0
+ATT_DENSE = [(3, 4, (1,)), (3, 4, (1, 2, 4)), (2, 16, (1,)), (2, 16, (1, 2, 4))]      # (B, heads, group sizes): dense and MX8
+ATT_F32 = [(1, 2, (1,)), (1, 2, (1, 2, 4)), (3, 4, (1,)), (3, 4, (1, 2, 4))]
+ATT_PRODUCTION = (3, 4, (1,))                         # the dominant-key case run at scale 80^-0.5
+ATT_TOME_B, ATT_TOME_HEADS = 3, 4
+ATT_TOME_EDGES = [1, 15, 16, 17, 191, 192]
+ATT_TOME_DECIDES = 192                                # tokens of the case in which the sizes decide (a multiple of 3)
+ATT_SIZE_MAX = 8                                      # hashed sizes 1..8: log2 <= 3
+
+
+def att_tome_tokens():
+    """Every token count the attention of a block sees under the merging schedule of synth.HamerConfig() (r = (8, -1), the
+    schedule HamerEngine(token_merge=True) runs), plus the edges."""
+    from hamer_yolo_amd.engine import parse_tome_r
+    t, seen = ATT_T, set(ATT_TOME_EDGES)
+    for r in parse_tome_r(synth.HamerConfig().vit.depth, (8, -1)):
+        seen.add(t)
+        t -= min(r, t // 2)
+    return sorted(seen)
+
+
+def _hashed_perm(tag, shape, seed):
+    """A hashed permutation of range(shape[-1]) for every leading index."""
+    n = 1
+    for s in shape:
+        n *= int(s)
+    h = synth._hash_u32(torch.arange(n, dtype=torch.int64), synth.name_seed(tag, seed)).reshape(*shape)
+    return torch.argsort(h, dim=-1, stable=True)
+
+
+def attention_case(B, heads, tokens, group_sizes, sizes=None):
+    """q, k, v of the few-hot attention described above for B crops of `tokens` tokens.
+    sizes: None; "hashed" (token sizes 1..ATT_SIZE_MAX, which shift a logit by at most 3 and leave P unchanged on dominant-key
+    data); "decides" (group_sizes must be (3,): three identical keys with sizes 1, 1 and 2 in a hashed order, so the weights
+    are 1/4, 1/4, 1/2 -- the partition is then shared by a crop's heads, as the sizes are).
+    Returns a dict: qkv (B*tokens, 3*heads*80) fp32 (every value exact in bf16 and fp16), size (B*tokens,) fp32 or None,
+    weights (B, heads, tokens, tokens) fp64 (the exact P / row sum), expect (B*tokens, heads*80) fp64 (weights @ V, exact),
+    gap (the smallest distance in log2 units at scale 2^-3 between a chosen and any other logit, sizes included),
+    chosen (B, heads, tokens) the key each query was dealt."""
+    T, HD = int(tokens), ATT_HD
+    assert 1 <= T <= ATT_T and all(m in (1, 2, 3, 4) for m in group_sizes)
+    decides = sizes == "decides"
+    assert not decides or (tuple(group_sizes) == (3,) and T % 3 == 0)
+    assert decides or all(m in (1, 2, 4) for m in group_sizes)
+    sd = _shape_seed(B, heads, T, len(group_sizes), sum(group_sizes), ATT_SALT)
+    ph = 1 if decides else heads
+    # partition: positions of a hashed permutation cut into runs whose lengths are hashed draws from group_sizes
+    perm = _hashed_perm("exact.att.perm", (B, ph, T), sd)                                     # position -> key
+    gs = torch.tensor(group_sizes, dtype=torch.int64)
+    draw = gs[ints("exact.att.draw", (B, ph, T), 0, len(group_sizes) - 1, sd).long()]
+    ends = draw.cumsum(-1)
+    pos = torch.arange(T, dtype=torch.int64).expand(B, ph, T).contiguous()
+    gpos = torch.searchsorted(ends, pos, right=True)                                          # group of a position
+    # a clipped last run whose length is no legal group size (3 of a drawn 4) becomes single keys
+    start = torch.where(gpos > 0, torch.gather(ends, -1, (gpos - 1).clamp(min=0)), torch.zeros_like(gpos))
+    last = gpos[..., -1:]
+    clipped = T - torch.gather(start, -1, torch.full_like(last, T - 1))
+    legal = (clipped[..., None] == gs).any(-1)
+    gpos = torch.where((gpos == last) & ~legal, last + (pos - start), gpos)
+    group = torch.empty_like(gpos).scatter_(-1, perm, gpos).expand(B, heads, T)               # key -> group
+    member = torch.empty_like(gpos).scatter_(-1, perm, pos - start).expand(B, heads, T)       # key -> place inside its group
+    counts = torch.zeros(B, heads, 2 * T, dtype=torch.int64).scatter_add_(-1, group, torch.ones_like(group))
+    assert all(int(c) in tuple(group_sizes) + (0,) or int(c) == 1 for c in counts.unique())
+    # codes, keys, queries
+    u = 2 * ints("exact.att.code", (B, heads, 2 * T, HD), 0, 1, sd) - 1
+    k = 8 * torch.gather(u, 2, group[..., None].expand(B, heads, T, HD))
+    chosen = _hashed_perm("exact.att.deal", (B, heads, T), sd)                                # query -> the key it is dealt
+    qgroup = torch.gather(group, -1, chosen)
+    q = 8 * torch.gather(u, 2, qgroup[..., None].expand(B, heads, T, HD))
+    # V: ints(-7..7) * 2^e, e hashed per (crop, token, head, 32-column block)
+    e = ints("exact.att.vexp", (B, T, heads, 3), 0, 4, sd).to(torch.int32).repeat_interleave(32, dim=-1)[..., :HD]
+    v = torch.ldexp(ints("exact.att.v", (B, T, heads, HD), -7, 7, sd), e).permute(0, 2, 1, 3)
+    size = lsz = None
+    if sizes == "hashed":
+        size = 1.0 + ints("exact.att.size", (B, T), 0, ATT_SIZE_MAX - 1, sd)
+    elif decides:
+        big = ints("exact.att.big", (B, 1, 2 * T), 0, 2, sd).long()                          # which of the three keys carries size 2
+        size = 1.0 + (member[:, :1] == torch.gather(big, -1, group[:, :1])).float()[:, 0]
+    else:
+        assert sizes is None
+    if size is not None:
+        lsz = size.double().log2()
+    # the exact P: own group, weighted by size where the sizes decide (the hashed sizes act on single keys and cancel)
+    own = (qgroup[..., :, None] == group[..., None, :]).double()
+    w = own * (size.double()[:, None, None, :] if decides else 1.0)
+    rowsum = w.sum(-1, keepdim=True)
+    assert all(float(r) in (1.0, 2.0, 4.0) for r in rowsum.unique())
+    weights = w / rowsum
+    expect = weights @ v.double()
+    # the gap: chosen logits against the rest, in log2 units at scale 2^-3
+    z = (q.double() @ k.double().transpose(-1, -2)) * ATT_C
+    assert bool((z[own.bool()] == 5120 * ATT_C).all())
+    if lsz is not None:
+        z = z + lsz[:, None, None, :]
+    top = torch.where(own.bool(), z, torch.full_like(z, float("inf"))).amin(-1)
+    rest = torch.where(own.bool(), torch.full_like(z, -float("inf")), z).amax(-1)
+    gap = float((top - rest).min()) if bool((~own.bool()).any()) else float("inf")
+    assert gap >= ATT_GAP, ((B, heads, T, group_sizes, sizes), gap)
+    if sizes == "hashed":
+        assert all(m == 1 for m in group_sizes), "hashed sizes leave P unchanged on dominant-key data only"
+    # coverage: every key is some query's chosen key, every query tile is there by construction (all T queries run)
+    hit = torch.zeros(B, heads, T, dtype=torch.int64).scatter_add_(-1, chosen, torch.ones_like(chosen))
+    assert bool((hit >= 1).all()), "a key index is nobody's chosen key"
+    qkv = torch.stack([q, k, v], 0).permute(1, 3, 0, 2, 4).reshape(B * T, 3 * heads * HD).contiguous()
+    for dt in (torch.bfloat16, torch.float16):
+        assert torch.equal(qkv.to(dt).float(), qkv)
+    assert torch.equal((expect * 4).round(), expect * 4) and float(expect.abs().max()) <= 7 * 16
+    return {"qkv": qkv, "size": None if size is None else size.reshape(B * T).contiguous(), "weights": weights,
+            "expect": expect.permute(0, 2, 1, 3).reshape(B * T, heads * HD).contiguous(), "gap": gap, "chosen": chosen,
+            "group": group, "q": q.double(), "k": k.double(), "v": v.double(), "log2size": lsz}
+
+
+def att_mx8_expect(expect, heads):
+    """(bytes (rows, heads*96), scales (heads*3, rows)) of the oracle quantiser on the exact fp32 rows, every head widened to
+    96 columns with zeros."""
+    from oracle import fp8_ref as Q
+    rows = expect.shape[0]
+    f = expect.float()
+    assert torch.equal(f.double(), expect)
+    pad = torch.zeros(rows, heads, ATT_HDP)
+    pad[:, :, :ATT_HD] = f.reshape(rows, heads, ATT_HD)
+    q8, sc = Q.mx8_quantize(pad.reshape(rows, heads * ATT_HDP))
+    assert bool((q8.reshape(rows, heads, ATT_HDP)[:, :, ATT_HD:] == 0).all())
+    return q8, sc
+
+
+def att_production_margin(case, scale, dtype):
+    """The dominant-key case at an ordinary scale: fma(m, c, -(m c)) is the rounding residual of m c, so p = exp2(residual)
+    is within about 1e-5 of 1 and the output v / p.  Emulates the two roundings (p to the operand type, which must give 1;
+    v / p to the output type, which must give v back for every V value in use, with the hardware exponential allowed an
+    error of 2^-21 relative on top) and returns (c, residual, delta)."""
+    c = np.float32(scale) * ATT_LOG2E
+    assert c.dtype == np.float32
+    m = np.float32(5120.0)
+    mneg = -(m * c)                                                       # fp32 product, rounded
+    res = float(np.float32(float(m) * float(c) + float(mneg)))            # the fma: exact in fp64, then one rounding
+    delta = abs(2.0 ** res - 1.0) + 2.0 ** -21
+    one = torch.tensor([1.0 + delta, 1.0 - delta], dtype=torch.float64)
+    assert torch.equal(one.float().to(dtype).double(), torch.ones(2, dtype=torch.float64)), "P would not round to 1"
+    vals = case["v"].unique()
+    for f in (1.0 / (1.0 + delta), 1.0 / (1.0 - delta)):
+        assert torch.equal((vals * f).float().to(dtype).double(), vals), "v / p would not round back to v"
+    # every other key still underflows: the gap at this scale
+    assert case["gap"] / ATT_C * float(c) - 1.0 >= ATT_GAP
+    return float(c), res, delta

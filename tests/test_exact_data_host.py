@@ -19,6 +19,10 @@ The MANO tail, the Detect decode and the RootNet layout kernels (the last sectio
 each fault of their catalogues is applied to the rule at every case the GPU tests run and must change more than half of the
 rows of the output it concerns; the decode's closeness bound is measured here, on the CPU, against float64.
 
+The fp8 epilogue data (ED.fp8_epilogue_case) meets FP8_FAULTS at every shape of both fp8 kernels, judged on its three expectations
+(fp32, bf16, GELU -> MXFP8 bytes and scales); the attention data (ED.attention_case) has a rule with a `fault` argument
+(tests/attention_rule.py) and the scale faults of the LayerNorm -> MXFP8 data for its MXFP8 form.
+
 Large problems are checked on a 256 x 256 subset of the output spread evenly over the rows and columns (so over every tile);
 a fault is an index map, applied to the full operand's indices before the subset is taken.  A fault that is the identity
 map at a shape (a rotation of K-tiles when K is one tile, a flip of a 1 x 1 kernel) is no fault there and is passed over;
@@ -545,6 +549,183 @@ def test_fp8_data_sees_every_fault():
         # the bytes the kernel takes are the integers the reference used
         assert torch.equal(x8.view(torch.float8_e4m3fn).float(), xi) and torch.equal(w8.view(torch.float8_e4m3fn).float(), wi)
         assert int(xs.min()) == 126 and int(xs.max()) == 129 and sorted(set(ws.tolist())) == [0.5, 1.0, 2.0]
+    met = set()
+    for (M, N, K) in FP8_EPILOGUE_SHAPES:
+        met |= _fp8_epilogue_catalogue(M, N, K)
+    assert met == {f[0] for f in FP8_FAULTS}
+
+
+FP8_EPILOGUE_SHAPES = sorted(set(ED.GEMM_FP8_ONE_TILE) | {s[:3] for s in ED.GEMM_FP8_PERSISTENT} | set(ED.GEMM_FP8_WIDE) | set(ED.GEMM_FP8_NO_BIAS))
+
+
+def _mx8_scale_faults(sc):
+    """The three scale faults of test_ln_mx8_scales_see_every_fault on scale bytes (blocks, rows): (name, faulty, applies)."""
+    nblk, M = sc.shape
+    return [("scales written [M][blocks]", sc.t().contiguous().view(nblk, M), nblk > 1 and M > 1),
+            ("scale of the neighbouring block", sc.roll(1, 0), nblk > 1),
+            ("scale of the neighbouring row", sc.roll(1, 1), M > 1)]
+
+
+FP8_PARTIAL_K = ("W: last K-tile replaced by the first", "X: K-tiles 0 and 1 swapped")
+FP8_PARTIAL_SHARE = 1.0 / 3.0
+
+
+def _fp8_gelu_bar(name, op, axis, m):
+    """The share of the GELU -> MXFP8 bytes in positive-bias columns a fault must change: VALUE_FAULT for every fault of
+    FP8_FAULTS -- those that re-pair every product of the K loop included (measured 0.42-0.67 at the listed shapes) -- except
+    the two that REPLACE part of K (one 64-wide tile; two tiles exchanged) where that part is under a third of K.  There the
+    sum moves by a fraction of its spread, and e4m3's three mantissa bits at 448 2^kb showed it in 0.09-0.35 of the bytes
+    (0.09 at K = 5120, one tile of 80); the bar is then the moved share of K itself, which the data meets everywhere with
+    room, so the sensitivity cannot vanish unnoticed.  The fp32 and bf16 expectations hold these two to HALF at every shape."""
+    if axis == 1 and op in ("x", "w"):
+        share = float((m != _ar(m.numel())).float().mean())
+        if share < FP8_PARTIAL_SHARE:
+            assert name in FP8_PARTIAL_K, name
+            return share
+    return VALUE_FAULT
+
+
+def _fp8_epilogue_catalogue(M, N, K):
+    """FP8_FAULTS against the three expectations of ED.fp8_epilogue_case: acc + bias + resid in fp32 and acc + bias rounded to
+    bf16 (more than HALF of the elements change), the GELU -> MXFP8 bytes in the positive-bias columns (at least _fp8_gelu_bar);
+    the three output-scale faults change at least SCALE_FAULT of the scale bytes; all-zero blocks exist where N >= 320."""
+    c = ED.fp8_epilogue_case(M, N, K)
+    ops = {k: c[k] for k in ("xs", "ws")}
+    ops["x"], ops["w"] = c["xi"], c["wi"]
+    sizes = {("x", 0): M, ("x", 1): K, ("w", 0): N, ("w", 1): K, ("xs", 0): K // 32, ("xs", 1): M, ("ws", 0): N}
+    bias, resid, gb, pos = c["bias"].double(), c["resid"].double(), c["gelu_bias"].double(), c["positive"]
+    assert int(pos.sum()) >= N // 4
+
+    def expectations(acc):
+        return acc + bias + resid, (acc + bias).float().to(torch.bfloat16), ED.fp8_gelu_expect(acc + gb)[0][:, pos]
+
+    ref = expectations(c["acc"])
+    assert torch.equal(ref[0].float().double(), ref[0]) and _rounds_in_bf16((c["acc"] + bias).float())
+    seen, low = set(), []
+    for name, op, axis, fn in FP8_FAULTS:
+        m = fn(sizes[(op, axis)])
+        if _is_identity(m):
+            continue
+        o = dict(ops)
+        o[op] = o[op].index_select(axis, m)
+        bad = expectations(ED.fp8_reference(o["x"], o["xs"], o["w"], o["ws"]))
+        fr = [float((b != r).float().mean()) for b, r in zip(bad, ref)]
+        seen.add(name)
+        if not (fr[0] > HALF and fr[1] > HALF and fr[2] >= _fp8_gelu_bar(name, op, axis, m)):
+            low.append((name, [round(f, 4) for f in fr]))
+    assert not low, ((M, N, K), low)
+    q, sc = ED.fp8_gelu_expect(c["acc"] + gb)
+    assert sc.shape == (N // 32, M)
+    for name, bad, applies in _mx8_scale_faults(sc):
+        assert applies
+        frac = float((bad != sc).float().mean())
+        assert frac >= SCALE_FAULT, ((M, N, K), name, frac)
+    zero = sc == 0
+    assert N < 320 or bool(zero.any()), (M, N, K)
+    assert bool((q.reshape(M, N // 32, 32)[zero.t()] & 0x7F == 0).all())                 # a zero-scale block is all zero bytes
+    assert max(len(set(r.tolist())) for r in sc) >= 2 and max(len(set(col.tolist())) for col in sc.t()) >= 2
+    # the bytes the kernel takes are the integers the reference used
+    assert torch.equal(c["x8"].view(torch.float8_e4m3fn).float(), c["xi"]) and torch.equal(c["w8"].view(torch.float8_e4m3fn).float(), c["wi"])
+    assert int(c["xs"].min()) == 126 and int(c["xs"].max()) == 129
+    assert set(c["ws"].tolist()) <= {0.25, 0.5, 1.0, 2.0, 4.0} and len(set(c["ws"].tolist())) >= 3
+    return seen
+
+
+# ------------------------------------------------------------------------------------------------ attention
+ATT_CASES = ([("dense", B, h, ED.ATT_T, gs, None) for (B, h, gs) in ED.ATT_DENSE] + [("f32", B, h, ED.ATT_T, gs, None) for (B, h, gs) in ED.ATT_F32]
+             + [("tome", ED.ATT_TOME_B, ED.ATT_TOME_HEADS, T, gs, sz) for T in ED.att_tome_tokens()
+                for (gs, sz) in (((1,), None), ((1,), "hashed"), ((1, 2, 4), None))]
+             + [("tome", ED.ATT_TOME_B, ED.ATT_TOME_HEADS, ED.ATT_TOME_DECIDES, (3,), "decides")])
+
+
+def _att_rows(out):
+    B, H, T, d = out.shape
+    return out.permute(0, 2, 1, 3).reshape(B * T, H * d)
+
+
+def test_attention_data_is_exact_and_sees_every_fault():
+    """At every case the exact attention tests run: the plain float64 rule gives the builder's closed form bit for bit (the
+    builder itself asserts the gap of 160 log2 units, that every key is some query's chosen key and that the result is
+    exact); each fault of attention_rule.FAULTS changes at least HALF of the output elements of the queries it concerns
+    (those with a chosen key whose V row, score or output row the fault moves -- a dropped tile concerns a twelfth of the
+    queries and cannot do more); every fault is met at every case with 192 tokens."""
+    import attention_rule as AR
+    for kind, B, H, T, gs, sz in ATT_CASES:
+        c = ED.attention_case(B, H, T, gs, sz)
+        assert c["gap"] >= ED.ATT_GAP
+        ref = AR.attention_rule(c["q"], c["k"], c["v"], ED.ATT_C, c["log2size"])
+        assert torch.equal(_att_rows(ref), c["expect"]), (kind, B, H, T, gs, sz)
+        ar = _ar(T)
+        met = set()
+        for fault in AR.FAULTS:
+            vmap = AR.v_key_map(fault, T)
+            if fault == "one key tile dropped":
+                tile = min(AR.DROPPED_TILE, (T - 1) // 16)
+                moved = (ar // 16 == tile)
+            elif not _is_identity(vmap) or fault in ("V read without the slot permutation", "V rows of neighbouring 16-key tiles swapped"):
+                moved = vmap != ar
+            else:
+                moved = None
+            if moved is not None:                                  # queries that put weight on a moved key
+                rows = (c["weights"] * moved.double()).sum(-1) > 0
+                # every key is some query's chosen key, so the concerned queries are at least the moved share of the keys
+                # in every (crop, head) -- half for the slot permutation, a twelfth for the dropped tile at 192 tokens -- and
+                # exactly that share where every group is one key
+                share, per_item = float(moved.double().mean()), rows.double().mean(-1)
+                assert float(per_item.min()) >= share - 1e-12, ((kind, B, H, T, gs, sz), fault, share)
+                assert len(gs) > 1 or gs == (3,) or bool((per_item == moved.double().mean()).all())
+                if T == ED.ATT_T:
+                    assert share == {"V read without the slot permutation": 0.5, "one key tile dropped": 1.0 / 12}.get(fault, 1.0)
+            elif fault.startswith("query rows"):
+                rows = ((ar // 16 ^ 1) * 16 + ar % 16 < T).expand(B, H, T)
+                if T < 32:
+                    continue
+                assert int(rows[0, 0].sum()) >= T // 32 * 32                 # every whole pair of query tiles
+            else:
+                rows = torch.ones(B, H, T, dtype=torch.bool)
+            if B * H == 1 or (fault == "head index off by one" and H == 1) or not bool(rows.any()):
+                continue
+            bad = AR.attention_rule(c["q"], c["k"], c["v"], ED.ATT_C, c["log2size"], fault=fault)
+            changed = (bad != ref) | bad.isnan()
+            frac = float(changed[rows].float().mean())
+            met.add(fault)
+            assert frac >= HALF, ((kind, B, H, T, gs, sz), fault, frac)
+        if T == ED.ATT_T:
+            assert met == set(AR.FAULTS), set(AR.FAULTS) - met
+        # every query tile of 16 appears (all T queries run), and key 0 and key T - 1 are chosen keys
+        assert all(bool((c["chosen"] == t).any(-1).all()) for t in (0, T - 1))
+        if sz == "decides":
+            w = sorted(set(c["weights"].unique().tolist()))
+            assert w == [0.0, 0.25, 0.5], w
+        if len(gs) > 1 and T >= 8:
+            assert set(c["weights"].unique().tolist()) >= {0.25, 0.5, 1.0}
+
+
+def test_attention_mx8_scales_see_every_fault():
+    """The MXFP8 form of every dense case: the three scale faults change at least SCALE_FAULT of the expected scale bytes; the
+    bytes take at least three values along the rows of some block and two along the blocks of some row; the 16 pad columns
+    of every head are zero bytes."""
+    for (B, H, gs) in ED.ATT_DENSE:
+        c = ED.attention_case(B, H, ED.ATT_T, gs)
+        q8, sc = ED.att_mx8_expect(c["expect"], H)
+        assert q8.shape == (B * ED.ATT_T, H * ED.ATT_HDP) and sc.shape == (H * 3, B * ED.ATT_T)
+        for name, bad, applies in _mx8_scale_faults(sc):
+            assert applies
+            frac = float((bad != sc).float().mean())
+            assert frac >= SCALE_FAULT, ((B, H, gs), name, frac)
+        assert max(len(set(r.tolist())) for r in sc) >= 3 and max(len(set(col.tolist())) for col in sc.t()) >= 2
+
+
+def test_attention_scales_and_production_margin():
+    """The dense scale times the kernel's fp32 log2(e) is exactly 2^-3; at the production scale 80^-0.5 the dominant-key output
+    still rounds to v in both 16-bit types (ED.att_production_margin emulates the two roundings)."""
+    import numpy as np
+    assert np.float32(ED.ATT_SCALE_DENSE) * ED.ATT_LOG2E == np.float32(2.0 ** -3)
+    B, H, gs = ED.ATT_PRODUCTION
+    case = ED.attention_case(B, H, ED.ATT_T, gs)
+    for dt in (torch.bfloat16, torch.float16):
+        c, res, delta = ED.att_production_margin(case, ED.ATT_HD ** -0.5, dt)
+        assert abs(res) <= 2.0 ** -14 and delta < 3e-5
 
 
 # ------------------------------------------------------------------------------------------------ convolution
@@ -1361,6 +1542,20 @@ def test_builders_refuse_data_that_is_not_exact(monkeypatch):
         ED.conv_case(1, 64, 8, 3, 8, 8)
     with pytest.raises(AssertionError):
         ED.fp8_case(16, 64, 128)
+
+
+def test_fp8_epilogue_builder_refuses_a_residual_that_is_not_exact(monkeypatch):
+    """fp8_case passes; the epilogue builder's own bound (bias and residual included) trips."""
+    monkeypatch.setattr(ED, "FP8_RESID_RANGE", 1 << 24)
+    ED.fp8_case(16, 64, 128, ED.FP8_EPILOGUE_WS_RANGE)
+    with pytest.raises(AssertionError):
+        ED.fp8_epilogue_case(16, 64, 128)
+
+
+def test_attention_builder_refuses_a_gap_it_cannot_reach(monkeypatch):
+    monkeypatch.setattr(ED, "ATT_GAP", 600.0)
+    with pytest.raises(AssertionError):
+        ED.attention_case(3, 4, 192, (1,))
 
 
 def test_assert_exact_locates_the_fault():

@@ -112,6 +112,34 @@ def test_attention_grid_is_host_arithmetic_and_not_sticky():
     assert lib.hm_attention_grid(640, 256) == 214
 
 
+def test_gemm_fp8_route_is_host_arithmetic_and_follows_the_options():
+    """hm_gemm_fp8_persistent reports the kernel hm_gemm_fp8 takes for a set of arguments (the launch dispatches on the same
+    function; no device work, so placeholder addresses do): the persistent one needs whole 256 x 256 tiles, at least 8, K >= 256,
+    a bias and HM_OPT_FP8_ONE_TILE unset; RESID_F32 also HM_OPT_FP8P_RESID; GELU_MX8 ldc % 16 == 0.  Refused arguments give -1."""
+    import ctypes as C
+    lib = L.load()
+    P = 1 << 20                                            # a 16-byte aligned placeholder
+
+    def route(M, N, K, epi, bias=True, ldc=None, ldr=None):
+        a = L.GemmFp8Args(P, P, P, P, P, P if bias else None, P if epi == L.HM_EPI_RESID_F32 else None,
+                          P if epi == L.HM_EPI_GELU_MX8 else None, M, N, K, K, K, ldc or N, ldr or N, epi, L.HM_DTYPE_BF16)
+        return lib.hm_gemm_fp8_persistent(C.byref(a))
+
+    S, R, G = L.HM_EPI_STORE, L.HM_EPI_RESID_F32, L.HM_EPI_GELU_MX8
+    assert route(512, 1024, 256, S) == 1 and route(512, 1024, 256, G) == 1 and route(512, 1024, 256, R) == 0
+    assert route(512, 1024, 256, S, bias=False) == 0                       # no bias: the one-tile kernel
+    assert route(512, 768, 256, S) == 0 and route(512, 1024, 128, S) == 0  # 6 tiles; K below 256
+    assert route(272, 320, 384, S) == 0 and route(528, 1024, 256, G) == 0  # no whole tiles
+    assert route(768, 768, 384, G, ldc=768 + 16) == 1 and route(768, 768, 384, G, ldc=768 + 8) == 0
+    assert route(768, 768, 384, S, ldc=768 + 8) == 1
+    with L.option(L.HM_OPT_FP8P_RESID, 1):
+        assert route(768, 768, 384, R, ldc=768 + 8, ldr=768 + 4) == 1 and route(768, 768, 384, R, bias=False) == 0
+        with L.option(L.HM_OPT_FP8_ONE_TILE, 1):
+            assert route(768, 768, 384, R) == 0 and route(768, 768, 384, S) == 0 and route(768, 768, 384, G) == 0
+    assert route(768, 768, 384, R) == 0 and route(768, 768, 384, S) == 1   # nothing sticky
+    assert route(16, 64, 100, S) == -1 and route(768, 768, 384, S, ldc=768 + 4) == -1
+
+
 def test_library_is_loaded_behind_torchs_hip_runtime():
     """Round 4: loaded BEFORE torch, libhamer_hip.so maps the system's libamdhip64 and the process ends up with two HIP runtimes
     (torch sees the GPU, the kernels here report "no ROCm-capable device": __graft_entry__.build() followed by smoke() in one
